@@ -15,11 +15,20 @@ no data-path collective; the per-column CAPE/CIN are gathered to rank 0 with one
 side stream.  (The reference's counterpart: dask chunks over the horizontal dims, pf.py:343-346, parcel_test.py:604.)
 
 Prints ONE JSON line on rank 0.  `roofline` is computed from HIP-event timings of the dominant kernel's launches inside
-the timed region; `cpu_baseline` times the CPU oracle (C restatement, OpenMP, all host cores) on a bounded sample of the
-same workload; `table_mode` / `rk4_mode` (c2, one GPU) are the same step in the reference's shipping moist mode (its
-lookup tables, pf.py:525-607) and with the RK4 stepper, measured after the headline's timed region.
+the timed region.  A plain run does only what that line's headline needs: set up, warm up (W steps after a
+--preroll-seconds pre-roll of the same step), time exactly K steps, write the last step's outputs if --dump-outputs DIR
+is given, print.  Everything else is measured only with --full:
+`cold_start` (the first W + K steps from an idle GPU, before the pre-roll); `cpu_baseline`, which times the CPU oracle
+(C restatement, OpenMP, all host cores) on a bounded sample of the same workload; `table_mode` / `rk4_mode` (c2, one
+GPU), the same step in the reference's shipping moist mode (its lookup tables, pf.py:525-607) and with the RK4 stepper,
+measured after the headline's timed region; and the legs below.
 
-Legs measured after the headline (never a reason to lose it: each one is guarded):
+--dump-outputs DIR writes what a caller of the timed path receives from its last timed step -- CAPE and CIN per parcel,
+the whole grid (rank 0: the gathered grid) -- as DIR/<parcel>_<cape|cin>.npy in the step's dtype; above 64 MB in all, the
+same seeded sample of columns of every array.  Inputs are generated from each config's fixed seed, so two builds run
+with the same arguments can be compared output for output.
+
+Legs measured after the headline with --full (never a reason to lose it: each one is guarded):
   one GPU, --config c2:  "c3" (BASELINE config 3 at full size: 128 x 4096 x 4096 f32, full profile + scalars), "c4_share" and
             "c5_share" (one of eight ranks' slab of configs 4 / 5; c5 = most-unstable + mixed-layer, as two passes and as the
             fused pass of xp_cape_cin_multi), each with kernel_ms, frac on SURVEY 8(d)'s algorithmic bytes and a strided
@@ -50,6 +59,29 @@ CONFIGS = {
     'c5': dict(nlev=100, nt=24, ny=2048, nx=2048, dtype='f32', parcels=('most_unstable', 'mixed_layer'), scaling='strong',
                seed=20250722, what='one synthetic 24-timestep x 100-level x 2048 x 2048 f32 grid, (time, y) cut into slabs'),
 }
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: above this in all, a seeded sample of the columns
+DUMP_SEED = 20251015
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: 1-D tensor of one length for all} as out_dir/<name>.npy in its own dtype (float32 / float64).  When
+    they exceed DUMP_MAX_BYTES in all, every array keeps the same fixed, seeded, sorted sample of its positions."""
+    import numpy as np
+    import torch
+    ncol = next(iter(arrays.values())).numel()
+    keep = min(ncol, DUMP_MAX_BYTES // sum(v.element_size() for v in arrays.values()))
+    idx = None
+    if keep < ncol:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(ncol, keep, replace=False)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if idx is not None:
+            v = v[idx.to(v.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), v.cpu().numpy())
+    return {'dir': out_dir, 'arrays': list(arrays), 'columns': int(keep), 'columns_total': int(ncol),
+            'sample': None if idx is None else f'numpy default_rng({DUMP_SEED}).choice(columns_total, columns), sorted'}
 
 
 def algorithmic_bytes_per_column(nlev, itemsize, n_out=2):
@@ -277,8 +309,14 @@ def main():
     ap.add_argument('--no-config-legs', action='store_true', help='skip the c3 / c4_share / c5_share / numpy / strong_c4 legs')
     ap.add_argument('--preroll-seconds', type=float, default=0.5,
                     help='untimed run of the same step before the W warmup + K timed steps, so that they see steady-state clocks '
-                         '(0: measure from an idle GPU; the first W + K steps are reported as cold_start either way)')
+                         '(0: measure from an idle GPU; with --full the first W + K steps are reported as cold_start either way)')
     ap.add_argument('--leg-scale', type=int, default=1, help='divide the column counts of the config legs by this (rehearsals, tests)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: cold_start, the other moist modes, the CPU baselines, '
+                         'the config legs and strong_c4 (--no-cpu / --no-table-leg / --no-config-legs select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the CAPE / CIN of the last timed step as DIR/<parcel>_<cape|cin>.npy (a seeded sample of '
+                         'the columns above 64 MB in all)')
     ap.add_argument('--dtype', default=None, choices=['f64', 'f32'])
     ap.add_argument('--moist', default='family', choices=['exact', 'family', 'table'],
                     help='family (headline) = the pseudo-adiabat ODE served from the adiabat-family table (xparcel.h: within 7.5e-7 K '
@@ -335,9 +373,9 @@ def main():
             dist.init_process_group(backend)
     cdev = dev if backend == 'nccl' else torch.device('cpu')       # where the gather buffers live
 
-    def run_cfg(cfg, moist, steps, warmup):
-        """One workload on this rank's slab: data in HBM, `warmup` untimed steps, then exactly `steps` steps between
-        barrier + synchronize fences, wall time = max over ranks."""
+    def run_cfg(cfg, moist, steps, warmup, preroll=0.0):
+        """One workload on this rank's slab: data in HBM, about `preroll` seconds of untimed steps (if > 0), `warmup`
+        untimed steps, then exactly `steps` steps between barrier + synchronize fences, wall time = max over ranks."""
         tdt = torch.float64 if cfg['dtype'] == 'f64' else torch.float32
         nlev, nx = cfg['nlev'], cfg['nx']
         rows = cfg['nt'] * cfg['ny']                               # the sharded axis: y, or the flattened (time, y)
@@ -419,9 +457,27 @@ def main():
                 dt = float(tmax.item())
             return dt, last
 
+        def outputs(last, steps):
+            """What a caller receives from the last of `steps` timed steps, by name: this rank's CAPE / CIN per parcel, or
+            with N > 1 the whole grid as gathered on rank 0 (None on the other ranks)."""
+            if world == 1:
+                return {f'{pc}_{k}': last[pc][k] for pc in parcels for k in ('cape', 'cin')}
+            if rank != 0:
+                return None
+            g = gathered[(steps - 1) & 1]
+            cols = [ncol] * world if cfg['scaling'] == 'weak' else [(e - s) * nx for s, e in (slab_bounds(rows, world, r) for r in range(world))]
+            return {f'{pc}_{k}': torch.cat([g[r, 2 * j + i, :cols[r]] for r in range(world)])
+                    for j, pc in enumerate(parcels) for i, k in enumerate(('cape', 'cin'))}
+
+        n_pre = 0
+        if preroll > 0:          # sized by two probe steps after the first one (same count on every rank: all-reduced time)
+            timed_steps(moist, 0, 1, None)
+            dtp, _ = timed_steps(moist, 2, 0, None)
+            n_pre = max(1, int(preroll / max(dtp / 2, 1e-6)))
+            timed_steps(moist, 0, n_pre, None)
         dt, last = timed_steps(moist, steps, warmup, kernel_ms)
         return dict(dt=dt, last=last, kernel_ms=kernel_ms, ncol=ncol, total_rows=total_rows, nlev=nlev, nx=nx, parcels=parcels,
-                    timed_steps=timed_steps, tdt=tdt)
+                    timed_steps=timed_steps, tdt=tdt, preroll_steps=n_pre, outputs=outputs)
 
     def strong_leg(c4):
         """SURVEY 8(e)'s fixed-grid point for this N: config 4's ONE grid cut into `world` y-slabs, the headline's protocol."""
@@ -438,15 +494,17 @@ def main():
         torch.cuda.empty_cache()
         return leg
 
-    h = run_cfg(cfg, a.moist, a.steps, a.warmup)
     # Steady state.  A run that starts on an idle GPU measures its clock ramp: on MI355X the first ~10 ms of this kernel run
     # ~7 % slower than the same kernel half a second later (and ~15 % slower than the boost the card reaches in between:
-    # DESIGN.md 7 "Clocks").  The driver's command line (--steps 20 --warmup 5) is 14 ms of GPU time in all.  So: the W + K
-    # steps just measured are reported as `cold_start`, then the same step runs untimed for --preroll-seconds, and W untimed
-    # + exactly K timed steps are taken again for `value`.  (Same number of extra steps on every rank: derived from the
-    # all-reduced cold time.)
+    # DESIGN.md 7 "Clocks").  The driver's command line (--steps 20 --warmup 5) is 14 ms of GPU time in all.  So the same
+    # step runs untimed for --preroll-seconds before the W untimed + exactly K timed steps of `value`.  A plain run sizes
+    # that pre-roll from two probe steps (run_cfg); with --full the first W + K steps are timed from the idle GPU and
+    # reported as `cold_start`, and the pre-roll is sized from them.  (Same number of extra steps on every rank: derived
+    # from an all-reduced time.)
+    h = run_cfg(cfg, a.moist, a.steps, a.warmup, preroll=0.0 if a.full else a.preroll_seconds)
+    n_pre = h['preroll_steps']
     cold = None
-    if a.preroll_seconds > 0:
+    if a.full and a.preroll_seconds > 0:
         ck = h['kernel_ms']
         cold = {'ms_per_step': h['dt'] / a.steps * 1e3,
                 'kernel_ms_by_parcel': {pc: sum(e0.elapsed_time(e1) for e0, e1 in v) / len(v) for pc, v in ck.items()}}
@@ -458,11 +516,17 @@ def main():
         cold['preroll_steps'] = n_pre
     dt, last, kernel_ms, ncol, total_rows = h['dt'], h['last'], h['kernel_ms'], h['ncol'], h['total_rows']
     nlev, nx, parcels = h['nlev'], h['nx'], h['parcels']
+    dumped = None
+    if a.dump_outputs:
+        arrays = h['outputs'](last, a.steps)
+        if arrays is not None:
+            dumped = dump_outputs(a.dump_outputs, arrays)
+            arrays = None
 
-    # N > 1 with the driver's command line (no --config): the fixed-grid curve of SURVEY 8(e) as a leg -- config 4's ONE
+    # N > 1 with the driver's command line (no --config) + --full: the fixed-grid curve of SURVEY 8(e) as a leg -- config 4's ONE
     # 128 x 8192 x 8192 f32 grid cut into N y-slabs, every rank generating its own slab in place
     strong = None
-    if world > 1 and a.config == 'c2' and not a.no_config_legs:
+    if world > 1 and a.config == 'c2' and a.full and not a.no_config_legs:
         c4 = dict(CONFIGS['c4'])
         c4['ny'] = max(world, c4['ny'] // max(1, a.leg_scale))
         head_keep = {pc: {'max_cape': float(last[pc]['cape'].max()), 'min_cin': float(last[pc]['cin'].min())} for pc in parcels}
@@ -504,16 +568,20 @@ def main():
                          'kernel_ms_by_parcel': per_parcel},
             'check': head_keep if strong is not None else {pc: {'max_cape': float(last[pc]['cape'].max()), 'min_cin': float(last[pc]['cin'].min())} for pc in parcels},
         }
+        if a.preroll_seconds > 0:
+            out['preroll'] = {'seconds': a.preroll_seconds, 'untimed_steps': n_pre, 'before': 'the W untimed + K timed steps of `value`'}
         if cold is not None:
             ck = cold['kernel_ms_by_parcel'][dom]
-            out['preroll'] = {'seconds': a.preroll_seconds, 'untimed_steps': cold['preroll_steps'], 'before': 'the W untimed + K timed steps of `value`', 'after': 'the W + K steps of `cold_start`'}
+            out['preroll']['after'] = 'the W + K steps of `cold_start`'
             out['cold_start'] = {'what': f"the first {a.warmup} + {a.steps} steps of this process, from an idle GPU (clock ramp), before the "
                                          f"{cold['preroll_steps']} untimed steps (~{a.preroll_seconds} s) that precede the steps `value` is taken from",
                                  'ms_per_step': cold['ms_per_step'], 'value': total_cols / (cold['ms_per_step'] * 1e-3), 'kernel_ms': ck,
                                  'frac': bytes_launch / (ck * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         if strong is not None:
             out['strong_c4'] = strong
-        if a.config == 'c2' and world == 1 and not a.no_table_leg and a.humidity == 'dewpoint':
+        if a.full and a.config == 'c2' and world == 1 and not a.no_table_leg and a.humidity == 'dewpoint':
             # the same step in the other two moist modes, measured after the headline's timed region: the reference's
             # shipping mode (its lookup tables) and the RK4 stepper
             legs = {'table': ('table_mode', "same step with the reference's lookup-table moist mode (pf.py:525-607; 31 MB index + 126 MB "
@@ -542,14 +610,14 @@ def main():
                         out[key]['table_generation_s'] = t_gen
                 except Exception as e:  # a report next to the headline, never a reason to lose it
                     out[key] = {'error': str(e)}
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             try:
                 sample = a.cpu_sample or ((1 << 20) if nlev <= 64 else (1 << 19))
                 out['cpu_baseline'] = cpu_baseline(cfg['seed'], nlev, sample, dom, a.moist)
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
                 out['cpu_baseline'] = {'value': None, 'unit': 'column-profiles/s', 'cores': 0, 'kind': 'port',
                                        'sample': f'failed: {e}'}
-        if a.config == 'c2' and world == 1 and not a.no_config_legs and a.humidity == 'dewpoint':
+        if a.full and a.config == 'c2' and world == 1 and not a.no_config_legs and a.humidity == 'dewpoint':
             h = last = None
             torch.cuda.empty_cache()
             try:

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-                          '--ny', '64', '--cpu-sample', '4096', '--leg-scale', '256'], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          '--ny', '64', '--cpu-sample', '4096', '--leg-scale', '256', '--full'], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -58,7 +59,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     env = dict(os.environ, XPARCEL_BENCH_SINGLE_DEVICE='1', XPARCEL_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29517', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--ny', '64',
-           '--no-cpu', '--leg-scale', '64']
+           '--no-cpu', '--leg-scale', '64', '--full']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -66,22 +67,49 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak' and d['value'] > 0 and 'cpu_baseline' not in d
     assert d['config']['columns_this_rank'] == 64 * 1024 and d['config']['columns_total'] == 2 * 64 * 1024
-    # the fixed-grid (strong-scaling) curve of SURVEY 8(e) rides along with the driver's command line as a leg
+    # the fixed-grid (strong-scaling) curve of SURVEY 8(e) rides along with the driver's command line + --full as a leg
     s4 = d['strong_c4']
     assert s4['scaling'] == 'strong' and s4['n_gpus'] == 2 and s4['columns_total'] == 128 * 8192 and s4['columns_this_rank'] == 64 * 8192
     assert s4['value'] > 0 and s4['check']['max_cape'] > 100.0
 
 
-def test_bench_fixed_grid_configs_two_ranks_rehearsal():
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline and nothing measured beside it; --dump-outputs writes the last timed
+    step's CAPE / CIN, whole (under 64 MB) and in the step's dtype, and the same arguments give the same arrays again."""
+    runs = []
+    for steps, tag in (('3', 'a'), ('5', 'b')):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', steps, '--warmup', '1',
+                              '--ny', '64', '--dump-outputs', str(tmp_path / tag)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 1e6 and d['dtype'] == 'f64'
+    assert d['preroll']['untimed_steps'] >= 1 and d['roofline']['kernel_ms'] > 0
+    for k in ('cold_start', 'table_mode', 'rk4_mode', 'cpu_baseline', 'cpu_baseline_numpy', 'c3', 'c4_share', 'c5_share', 'strong_c4'):
+        assert k not in d, k
+    assert d['dump_outputs']['columns'] == d['dump_outputs']['columns_total'] == 64 * 1024 and d['dump_outputs']['sample'] is None
+    for name in ('surface_cape', 'surface_cin'):
+        a, b = np.load(tmp_path / 'a' / (name + '.npy')), np.load(tmp_path / 'b' / (name + '.npy'))
+        assert a.dtype == np.float64 and a.shape == (64 * 1024,)
+        assert np.array_equal(a, b, equal_nan=True), name
+    assert float(np.max(np.load(tmp_path / 'a' / 'surface_cape.npy'))) == d['check']['surface']['max_cape']
+    assert float(np.min(np.load(tmp_path / 'a' / 'surface_cin.npy'))) == d['check']['surface']['min_cin']
+
+
+def test_bench_fixed_grid_configs_two_ranks_rehearsal(tmp_path):
     """--config c4 / c5: ONE fixed grid cut into y-slabs (strong scaling), two ranks on one GPU, uneven slabs; and the
-    one-rank run of the same reduced grid gives the same check values (the slabs reproduce the whole)."""
+    one-rank run of the same reduced grid gives the same check values and, gathered on rank 0, the same outputs (the slabs
+    reproduce the whole)."""
     env = dict(os.environ, XPARCEL_BENCH_SINGLE_DEVICE='1', XPARCEL_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     for cfgname, extra, rows in (('c4', ['--ny', '37', '--nx', '512'], 37), ('c5', ['--nt', '3', '--ny', '11', '--nx', '256'], 33)):
         res = {}
         for n in (1, 2):
             cmd = ([sys.executable] + (['-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                                         '127.0.0.1', '--master-port', '29519'] if n == 2 else []) +
-                   [os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1', '--config', cfgname, '--no-cpu'] + extra)
+                   [os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1', '--config', cfgname, '--no-cpu',
+                    '--dump-outputs', str(tmp_path / f'{cfgname}_{n}')] + extra)
             out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
             assert out.returncode == 0, out.stderr[-2000:]
             lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -94,3 +122,8 @@ def test_bench_fixed_grid_configs_two_ranks_rehearsal():
         assert 'REDUCED' in d1['config']['workload'] and cfgname in d1['config']['workload']
         if cfgname == 'c5':
             assert set(d1['roofline']['kernel_ms_by_parcel']) == {'most_unstable', 'mixed_layer'}
+        assert d1['dump_outputs']['arrays'] == d2['dump_outputs']['arrays']
+        assert d1['dump_outputs']['columns'] == d2['dump_outputs']['columns'] == d1['config']['columns_total']
+        for name in d1['dump_outputs']['arrays']:
+            a, b = np.load(tmp_path / f'{cfgname}_1' / (name + '.npy')), np.load(tmp_path / f'{cfgname}_2' / (name + '.npy'))
+            assert a.dtype == np.float32 and np.array_equal(a, b, equal_nan=True), (cfgname, name)
