@@ -548,6 +548,22 @@ def test_strided_device_views_through_the_raw_abi():
                             C.byref(so), None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
     assert np.array_equal(cape.cpu().numpy(), dense_mu['cape']) and np.array_equal(idx.cpu().numpy(), dense_mu['lfc_index'])
+    # the same views through xp_cape_cin_multi, one pass per parcel: densified once for both parcels, and in family mode
+    # one flags buffer shared by the two passes
+    pcs = (L.Parcel * 2)(pc, pc_mu)
+    for moist in ('exact', 'family'):
+        om = L.Opts(1, 1, 1, 0, L.MOIST[moist], L.XP_F64, 0, 0)
+        outs = [(torch.empty(ncol, dtype=torch.float64, device='cuda'), torch.empty(ncol, dtype=torch.int32, device='cuda'))
+                for _ in range(2)]
+        sos = (L.ScalarsOut * 2)()
+        for s, (c, i) in zip(sos, outs):
+            s.dtype, s.mem, s.cape, s.lfc_index = L.XP_F64, L.XP_MEM_DEVICE, c.data_ptr(), i.data_ptr()
+        L.check(lib.xp_cape_cin_multi(C.byref(mixed[0]), C.byref(mixed[1]), C.byref(mixed[2]), C.c_int32(2), pcs, C.byref(om),
+                                      sos, None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        for (name, depth), (c, i) in zip((('surface', 0.0), ('most_unstable', 300.0)), outs):
+            ref = xa.cape_cin_columns(p, t, td, parcel=name, depth=depth, moist=moist, want=('cape', 'lfc_index'))
+            assert np.array_equal(c.cpu().numpy(), ref['cape']) and np.array_equal(i.cpu().numpy(), ref['lfc_index']), (moist, name)
     o32 = L.Opts(1, 1, 1, 0, 0, L.XP_F32, 0, 0)
     assert lib.xp_cape_cin(C.byref(views[0]), C.byref(views[1]), C.byref(views[2]), C.byref(pc), C.byref(o32),
                            C.byref(so), None, None) == -1                 # XP_E_ARG: fp32 arithmetic not implemented

@@ -95,12 +95,19 @@ struct Stager {
     explicit Stager(void *stream) : s((hipStream_t)stream) {}
     // stream-ordered allocations: a host-array call stages ~25 buffers, and hipMalloc / hipFree would each synchronise
     ~Stager() { for (void *p : scratch) (void)hipFreeAsync(p, s); }
+    // device scratch for this call, released with the Stager
+    template <typename P> int alloc(size_t bytes, P **d) {
+        void *v = nullptr;
+        HIP_TRY(hipMallocAsync(&v, bytes ? bytes : 1, s));
+        scratch.push_back(v);
+        *d = (P *)v;
+        return 0;
+    }
     int in(const void *p, size_t bytes, int mem, const void **out) {
         *out = p;
         if (p == nullptr || mem == XP_MEM_DEVICE) return 0;
-        void *d = nullptr;
-        HIP_TRY(hipMallocAsync(&d, bytes ? bytes : 1, s));
-        scratch.push_back(d);
+        void *d;
+        if (int rc = alloc(bytes, &d)) return rc;
         HIP_TRY(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s));
         any_host = true;
         *out = d;
@@ -109,9 +116,8 @@ struct Stager {
     int out(void *p, size_t bytes, int mem, void **dev) {
         *dev = p;
         if (p == nullptr || mem == XP_MEM_DEVICE) return 0;
-        void *d = nullptr;
-        HIP_TRY(hipMallocAsync(&d, bytes ? bytes : 1, s));
-        scratch.push_back(d);
+        void *d;
+        if (int rc = alloc(bytes, &d)) return rc;
         back.push_back({p, d, bytes});
         any_host = true;
         *dev = d;
@@ -245,9 +251,15 @@ int check_view(const xp_view *v, const char *name) {
         return fail(XP_E_ARG, "%s: host views must be dense (nlev, ncol) C-order", name);
     return 0;
 }
-int same_shape(const xp_view *a, const xp_view *b, const char *what) {
-    if (a->nlev != b->nlev || a->ncol != b->ncol || a->dtype != b->dtype)
-        return fail(XP_E_ARG, "%s: views differ in shape or dtype", what);
+// the views of one call: each of them valid, all of them of the first one's shape and dtype
+struct Arg { const xp_view *v; const char *name; };
+int check_views(std::initializer_list<Arg> vs) {
+    for (const Arg &x : vs)
+        if (int rc = check_view(x.v, x.name)) return rc;
+    const Arg &a = *vs.begin();
+    for (const Arg &b : vs)
+        if (b.v->nlev != a.v->nlev || b.v->ncol != a.v->ncol || b.v->dtype != a.v->dtype)
+            return fail(XP_E_ARG, "%s/%s: views differ in shape or dtype", a.name, b.name);
     return 0;
 }
 int stage_view(Stager &st, const xp_view *v, xp::View *out) {
@@ -257,6 +269,11 @@ int stage_view(Stager &st, const xp_view *v, xp::View *out) {
     out->data = d; out->ls = v->lev_stride; out->cs = v->col_stride;
     return 0;
 }
+size_t rows_bytes(const xp_view *v, int64_t rows) { return (size_t)rows * (size_t)v->ncol * esize(v->dtype); }
+// an output laid out like view v (a device output keeps its input's strides), or as dense (rows, ncol)
+xp::OutView out_like(void *d, const xp_view *v) { return {d, v->lev_stride, v->col_stride}; }
+xp::OutView dense_out(void *d, int64_t ncol) { return {d, ncol, 1}; }
+
 // every entry point switches to the library's device for its duration and leaves the calling thread's current device
 // as it found it (the caller -- torch, say -- may be working on another one)
 struct DevGuard {
@@ -270,7 +287,22 @@ int ensure_init() {
     if (e != hipSuccess) return fail(XP_E_HIP, "hipSetDevice(%d): %s", g.device, hipGetErrorString(e));
     return 0;
 }
+// an entry point's prologue: the library's device, XP_E_NOT_INIT (rc) before any argument, the call's Stager
+struct Entry : DevGuard, Stager {
+    int rc;
+    explicit Entry(void *stream) : Stager(stream), rc(ensure_init()) {}
+};
 unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// f(T()) with T the element type of dtype: a generic lambda names a kernel once for both instantiations
+template <typename F> void by_dtype(int dtype, F &&f) {
+    if (dtype == XP_F64) f(double());
+    else f(float());
+}
+// one thread per element of an n-element grid, 256 per workgroup, on the call's stream; n == 0 launches nothing
+template <typename... P, typename... A> void launch(void (*k)(P...), int64_t n, const Stager &st, const A &...args) {
+    if (n > 0) hipLaunchKernelGGL(k, dim3(blocks(n)), dim3(256), 0, st.s, args...);
+}
 
 int stage_scalars(Stager &st, xp_scalars_out *s, int64_t ncol, xp::ScalarsOut *o) {
     memset(o, 0, sizeof(*o));
@@ -288,6 +320,29 @@ int stage_scalars(Stager &st, xp_scalars_out *s, int64_t ncol, xp::ScalarsOut *o
 #undef F_
 #undef I_
     return rc;
+}
+
+// The library's tables for one call, read under the lock that xp_init / xp_set_tables / xp_set_family_table replace
+// them under; table mode needs the reference-format tables loaded.
+struct TableSet { xp::Tables tb; const double *es, *fam; };
+int snapshot_tables(bool table_mode, TableSet *t) {
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (table_mode && !g.tables) return fail(XP_E_NO_TABLES, "Call load_moist_adiabat_lookups first.");
+    *t = {g.tb, g.es_tab, g.fam_tab};
+    return 0;
+}
+
+// Family mode runs persistent wavefronts (k_cape_cin / k_cape_cin_multi, PERSIST) on grids of at least this many
+// columns; mode is the parcel's XP_PARCEL_*, or -1 for the fused several-parcels kernel.  Measured per grid size
+// (profiles/r03_persist.txt, scripts/run_gpu_persist.py): equal to the ordinary launch up to two rounds of workgroups
+// (512 Ki columns), 10-13 % faster from three rounds on (768 Ki ... 2 Mi columns of 64 f64 levels; c2: 0.64 -> 0.575 ms)
+// -- a workgroup's sixteen wavefronts no longer wait for the slowest of them before the next sixteen tiles start.
+// XP_PERSIST_MIN_COLS (A/B) overrides every threshold; bench.py's persist_min_cols mirrors the single-parcel ones.
+bool persist(int mode, int64_t ncol) {
+    static const long long env = [] { const char *e = getenv("XP_PERSIST_MIN_COLS"); return e ? atoll(e) : -1ll; }();
+    const bool searching = mode < 0 || mode == XP_PARCEL_MOST_UNSTABLE || mode == XP_PARCEL_MIXED_LAYER;
+    const long long min_cols = env >= 0 ? env : searching ? (1ll << 19) : (3ll << 18);
+    return (long long)ncol >= min_cols && ncol < (1ll << 36);
 }
 
 // k_cape_cin's 96 instantiations are compiled in six translation units (xp_cape_tu.hip, one per dtype x moist mode) so
@@ -311,88 +366,169 @@ template <typename T> void launch_cape_pm(const xp::CapeArgs &a, int pm, bool pr
     }
 }
 
-int fill_common(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
-                const xp_opts *o, xp::CapeArgs *a) {
-    int rc;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(t, "temperature")) || (rc = check_view(td, "dewpoint"))) return rc;
-    if ((rc = same_shape(p, t, "pressure/temperature")) || (rc = same_shape(p, td, "pressure/dewpoint"))) return rc;
+// the options of a call that passes none (the reference's defaults)
+xp_opts default_opts() {
+    xp_opts o;
+    memset(&o, 0, sizeof(o));
+    o.virtual_temperature_correction = 1; o.lcl_interp = XP_LCL_INTERP_LOG; o.pos_cape_neg_cin = 1; o.compute = XP_F64;
+    return o;
+}
+int check_opts(const xp_opts &o) {
+    if (o.lcl_interp != XP_LCL_INTERP_LINEAR && o.lcl_interp != XP_LCL_INTERP_LOG)
+        return fail(XP_E_INTERP, "interpolator must be linear or log");
+    if (o.moist_mode != XP_MOIST_EXACT && o.moist_mode != XP_MOIST_TABLE && o.moist_mode != XP_MOIST_FAMILY)
+        return fail(XP_E_ARG, "bad moist_mode");
+    if (o.compute != XP_F64) return fail(XP_E_ARG, "xp_opts.compute: only XP_F64 arithmetic is implemented");
+    if (o.humidity != XP_HUM_DEWPOINT && o.humidity != XP_HUM_SPECIFIC) return fail(XP_E_ARG, "bad xp_opts.humidity");
+    return 0;
+}
+int check_parcel(const xp_parcel *parcel) {
     if (!parcel) return fail(XP_E_ARG, "parcel: null");
     if (parcel->mode < XP_PARCEL_SURFACE || parcel->mode > XP_PARCEL_EXPLICIT) return fail(XP_E_ARG, "parcel: bad mode");
+    if (parcel->mode == XP_PARCEL_EXPLICIT && (!parcel->pressure || !parcel->temperature || !parcel->dewpoint))
+        return fail(XP_E_ARG, "explicit parcel: null arrays");
+    return 0;
+}
+// the arguments of the CAPE family: p / T / Td, each of np parcels, the options
+int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o) {
+    if (int rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) return rc;
+    for (int i = 0; i < np; ++i)
+        if (int rc = check_parcel(parcels + i)) return rc;
+    return check_opts(o);
+}
+
+// the CAPE family's p / T / Td, options and tables, staged once per call however many parcels it lifts
+int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_opts &o, xp::CapeArgs *a) {
+    int rc;
+    TableSet ts;
     memset(a, 0, sizeof(*a));
-    if ((rc = stage_view(st, p, &a->p)) || (rc = stage_view(st, t, &a->t)) || (rc = stage_view(st, td, &a->td))) return rc;
+    if ((rc = snapshot_tables(o.moist_mode == XP_MOIST_TABLE, &ts)) || (rc = stage_view(st, p, &a->p)) ||
+        (rc = stage_view(st, t, &a->t)) || (rc = stage_view(st, td, &a->td))) return rc;
     a->nlev = p->nlev; a->ncol = p->ncol;
-    a->depth = parcel->depth;
-    {   // the library's tables: read under the lock that xp_init / xp_set_tables / xp_set_family_table replace them under
-        std::lock_guard<std::mutex> lk(g.mu);
-        a->es_tab = g.es_tab;
-        a->fam_tab = g.fam_tab;
-        a->tb = g.tb;
-    }
-    {   // fast level addressing (xp_kernels.hpp load3): common strides, non-negative, column offsets below 4 GiB
-        bool same = a->p.ls == a->t.ls && a->p.ls == a->td.ls && a->p.cs == a->t.cs && a->p.cs == a->td.cs;
-        bool fits = a->p.cs >= 0 && a->p.ls >= 0 &&
-                    (unsigned long long)a->p.cs * (unsigned long long)(p->ncol > 0 ? p->ncol : 1) * esize(p->dtype) < (1ull << 32);
-        a->off32 = 1;
-        if (!(same && fits)) {                               // rare: densify the three views on the device first
-            size_t n = (size_t)p->nlev * (size_t)p->ncol, bytes = n * esize(p->dtype);
-            xp::View *vs[3] = {&a->p, &a->t, &a->td};
-            for (int i = 0; i < 3 && n; ++i) {
-                void *d = nullptr;
-                HIP_TRY(hipMallocAsync(&d, bytes, st.s));
-                st.scratch.push_back(d);
-                if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_densify<double>), dim3(blocks((int64_t)n)), dim3(256), 0, st.s, *vs[i], p->nlev, p->ncol, (double *)d);
-                else hipLaunchKernelGGL((xp::k_densify<float>), dim3(blocks((int64_t)n)), dim3(256), 0, st.s, *vs[i], p->nlev, p->ncol, (float *)d);
-                vs[i]->data = d; vs[i]->ls = p->ncol; vs[i]->cs = 1;
-            }
-            if ((unsigned long long)(p->ncol > 0 ? p->ncol : 1) * esize(p->dtype) >= (1ull << 32))
-                return fail(XP_E_ARG, "more than 4 GiB per level row");
+    a->tb = ts.tb; a->es_tab = ts.es; a->fam_tab = ts.fam;
+    // fast level addressing (xp_kernels.hpp load3): common strides, non-negative, column offsets below 4 GiB
+    const bool same = a->p.ls == a->t.ls && a->p.ls == a->td.ls && a->p.cs == a->t.cs && a->p.cs == a->td.cs;
+    const unsigned long long row = (unsigned long long)(p->ncol > 0 ? p->ncol : 1) * esize(p->dtype);
+    a->off32 = 1;
+    if (!(same && a->p.cs >= 0 && a->p.ls >= 0 && (unsigned long long)a->p.cs * row < (1ull << 32))) {
+        if (row >= (1ull << 32)) return fail(XP_E_ARG, "more than 4 GiB per level row");
+        const int64_t n = p->nlev * p->ncol;                 // rare: densify the three views on the device first
+        for (xp::View *v : {&a->p, &a->t, &a->td}) {
+            void *d;
+            if (n == 0) break;
+            if ((rc = st.alloc(rows_bytes(p, p->nlev), &d))) return rc;
+            by_dtype(p->dtype, [&](auto z) { using T = decltype(z); launch(xp::k_densify<T>, n, st, *v, p->nlev, p->ncol, (T *)d); });
+            *v = {d, p->ncol, 1};
         }
     }
-    if (parcel->mode == XP_PARCEL_EXPLICIT) {
-        if (!parcel->pressure || !parcel->temperature || !parcel->dewpoint) return fail(XP_E_ARG, "explicit parcel: null arrays");
-        size_t b = (size_t)p->ncol * esize(p->dtype);
-        if ((rc = st.in(parcel->pressure, b, p->mem, &a->ex_p)) || (rc = st.in(parcel->temperature, b, p->mem, &a->ex_t)) ||
-            (rc = st.in(parcel->dewpoint, b, p->mem, &a->ex_td))) return rc;
+    a->vtc = o.virtual_temperature_correction; a->log_interp = o.lcl_interp == XP_LCL_INTERP_LOG;
+    a->pos_neg = o.pos_cape_neg_cin; a->post_zero = o.post_zero_cin; a->table_mode = o.moist_mode == XP_MOIST_TABLE;
+    a->hum = o.humidity == XP_HUM_SPECIFIC;
+    return 0;
+}
+// one parcel's part of the arguments: its depth, and the arrays of an explicit parcel (in the views' dtype and mem)
+int set_parcel(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeArgs *a) {
+    a->depth = parcel.depth;
+    a->ex_p = a->ex_t = a->ex_td = nullptr;
+    if (parcel.mode != XP_PARCEL_EXPLICIT) return 0;
+    const size_t b = rows_bytes(p, 1);
+    int rc;
+    if ((rc = st.in(parcel.pressure, b, p->mem, &a->ex_p)) || (rc = st.in(parcel.temperature, b, p->mem, &a->ex_t)) ||
+        (rc = st.in(parcel.dewpoint, b, p->mem, &a->ex_td))) return rc;
+    return 0;
+}
+int fill_common(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
+                const xp_opts &o, xp::CapeArgs *a) {
+    int rc;
+    if ((rc = check_cape(p, t, td, 1, parcel, o)) || (rc = stage_cape(st, p, t, td, o, a)) || (rc = set_parcel(st, *parcel, p, a)))
+        return rc;
+    return 0;
+}
+// one parcel's outputs: its scalars and, when asked for, its profile rows and lifted index
+int stage_cape_out(Stager &st, int dtype, xp_scalars_out *scalars, xp_profile_out *profile, xp::CapeArgs *a) {
+    int rc;
+    if ((rc = stage_scalars(st, scalars, a->ncol, &a->s)) || !profile) return rc;
+    if (profile->dtype != XP_F32 && profile->dtype != XP_F64) return fail(XP_E_ARG, "profile: bad dtype");
+    if (profile->nlev_out < a->nlev + 1) return fail(XP_E_ARG, "profile: nlev_out must be >= nlev + 1");
+    if (profile->mem == XP_MEM_HOST && !(profile->col_stride == 1 && profile->lev_stride == a->ncol))
+        return fail(XP_E_ARG, "profile: host arrays must be dense (nlev_out, ncol)");
+    void *src[6] = {profile->pressure, profile->temperature, profile->virtual_temperature,
+                    profile->environment_temperature, profile->environment_virtual_temperature,
+                    profile->environment_dewpoint};
+    size_t b = (size_t)profile->nlev_out * (size_t)a->ncol * esize(profile->dtype);
+    int rows = 0;                                            // how many of the six arrays are wanted
+    for (int v = 0; v < 6; ++v) {
+        if ((rc = st.out(src[v], b, profile->mem, &a->prof.v[v]))) return rc;
+        rows += a->prof.v[v] != nullptr;
     }
-    if (o) {
-        if (o->lcl_interp != XP_LCL_INTERP_LINEAR && o->lcl_interp != XP_LCL_INTERP_LOG)
-            return fail(XP_E_INTERP, "interpolator must be linear or log");
-        if (o->moist_mode != XP_MOIST_EXACT && o->moist_mode != XP_MOIST_TABLE && o->moist_mode != XP_MOIST_FAMILY)
-            return fail(XP_E_ARG, "bad moist_mode");
-        if (o->compute != XP_F64) return fail(XP_E_ARG, "xp_opts.compute: only XP_F64 arithmetic is implemented");
-        a->vtc = o->virtual_temperature_correction; a->log_interp = o->lcl_interp == XP_LCL_INTERP_LOG;
-        if (o->humidity != XP_HUM_DEWPOINT && o->humidity != XP_HUM_SPECIFIC) return fail(XP_E_ARG, "bad xp_opts.humidity");
-        a->pos_neg = o->pos_cape_neg_cin; a->post_zero = o->post_zero_cin; a->table_mode = o->moist_mode == XP_MOIST_TABLE;
-        a->hum = o->humidity == XP_HUM_SPECIFIC;
-    } else {
-        a->vtc = 1; a->log_interp = 1; a->pos_neg = 1; a->post_zero = 0; a->table_mode = 0; a->hum = 0;
-    }
-    if (a->table_mode) {
-        if (!g.tables) return fail(XP_E_NO_TABLES, "Call load_moist_adiabat_lookups first.");
+    a->prof.nlev_out = rows ? profile->nlev_out : 0;         // lifted index only: the kernel's row loops see an empty profile
+    a->prof.ls = profile->lev_stride; a->prof.cs = profile->col_stride;
+    a->prof.f64 = profile->dtype == XP_F64;
+    a->prof.native6 = rows == 6 && profile->dtype == dtype;
+    if (profile->lifted_index) {
+        if (!(profile->lifted_index_pressure > 0.0)) return fail(XP_E_ARG, "profile: lifted_index_pressure must be positive");
+        if ((rc = st.out(profile->lifted_index, (size_t)a->ncol * esize(profile->dtype), profile->mem, &a->prof.li))) return rc;
+        a->prof.li_x = log(profile->lifted_index_pressure);
     }
     return 0;
 }
+// family mode's scratch for cape_pass: which columns the RK4 pass redoes (null in the other modes)
+int family_flags(Stager &st, const xp_opts &o, int64_t ncol, int32_t **flags) {
+    *flags = nullptr;
+    if (o.moist_mode != XP_MOIST_FAMILY || ncol == 0) return 0;
+    return st.alloc(sizeof(int32_t) * (size_t)ncol, flags);
+}
+// one parcel's CAPE / CIN on staged arguments; the parcels of one call share the family flags (one stream orders them)
+void cape_pass(const Stager &st, xp::CapeArgs a, int dtype, int mode, bool profile, int32_t *flags) {
+    a.flags = flags;
+    a.persist = flags && persist(mode, a.ncol);
+    by_dtype(dtype, [&](auto z) { launch_cape_pm<decltype(z)>(a, mode, profile, st.s); });
+}
 
-}  // namespace
-
-namespace {
-template <typename T, int NV> void launch_interp_levels(int nt, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg, hipStream_t s) {
-    dim3 gr(blocks(ncol)), bl(256);
+template <typename T, int NV> void launch_interp_levels(int nt, const Stager &st, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg) {
     switch (nt) {
-        case 1: hipLaunchKernelGGL((xp::k_interp_levels<T, NV, 1>), gr, bl, 0, s, cv, m, nlev, ncol, lg); break;
-        case 2: hipLaunchKernelGGL((xp::k_interp_levels<T, NV, 2>), gr, bl, 0, s, cv, m, nlev, ncol, lg); break;
-        case 3: hipLaunchKernelGGL((xp::k_interp_levels<T, NV, 3>), gr, bl, 0, s, cv, m, nlev, ncol, lg); break;
-        default: hipLaunchKernelGGL((xp::k_interp_levels<T, NV, 4>), gr, bl, 0, s, cv, m, nlev, ncol, lg); break;
+        case 1: launch(xp::k_interp_levels<T, NV, 1>, ncol, st, cv, m, nlev, ncol, lg); break;
+        case 2: launch(xp::k_interp_levels<T, NV, 2>, ncol, st, cv, m, nlev, ncol, lg); break;
+        case 3: launch(xp::k_interp_levels<T, NV, 3>, ncol, st, cv, m, nlev, ncol, lg); break;
+        default: launch(xp::k_interp_levels<T, NV, 4>, ncol, st, cv, m, nlev, ncol, lg); break;
     }
 }
-template <typename T> void launch_interp_levels_v(int nv, int nt, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg, hipStream_t s) {
+template <typename T> void launch_interp_levels_v(int nv, int nt, const Stager &st, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg) {
     switch (nv) {
-        case 1: launch_interp_levels<T, 1>(nt, cv, m, nlev, ncol, lg, s); break;
-        case 2: launch_interp_levels<T, 2>(nt, cv, m, nlev, ncol, lg, s); break;
-        case 3: launch_interp_levels<T, 3>(nt, cv, m, nlev, ncol, lg, s); break;
-        default: launch_interp_levels<T, 4>(nt, cv, m, nlev, ncol, lg, s); break;
+        case 1: launch_interp_levels<T, 1>(nt, st, cv, m, nlev, ncol, lg); break;
+        case 2: launch_interp_levels<T, 2>(nt, st, cv, m, nlev, ncol, lg); break;
+        case 3: launch_interp_levels<T, 3>(nt, st, cv, m, nlev, ncol, lg); break;
+        default: launch_interp_levels<T, 4>(nt, st, cv, m, nlev, ncol, lg); break;
     }
 }
+// xp_interp_levels on checked views (xp_conv_properties calls it on its staged winds)
+int interp_levels(Stager &st, const xp_view *coords, int32_t nvar, const xp_view *const *variables, int32_t ntarget,
+                  const double *at, int32_t log_coords, void *const *out) {
+    xp::View cv;
+    xp::InterpMany m;
+    memset(&m, 0, sizeof(m));
+    int rc;
+    if ((rc = stage_view(st, coords, &cv))) return rc;
+    for (int v = 0; v < nvar; ++v) {
+        if ((rc = stage_view(st, variables[v], &m.x[v]))) return rc;
+        for (int j = 0; j < ntarget; ++j)
+            if ((rc = st.out(out[v * ntarget + j], rows_bytes(coords, 1), coords->mem, &m.out[v * ntarget + j]))) return rc;
+    }
+    for (int j = 0; j < ntarget; ++j) m.at[j] = at[j];
+    by_dtype(coords->dtype, [&](auto z) {
+        launch_interp_levels_v<decltype(z)>(nvar, ntarget, st, cv, m, coords->nlev, coords->ncol, (int)log_coords);
+    });
+    return 0;
+}
+
+bool multi_fused_ok(int32_t np, const xp_parcel *parcels, const xp_opts &o, const xp_profile_out *profiles) {
+    if (!(o.flags & XP_OPT_FUSE_PARCELS) || o.moist_mode != XP_MOIST_FAMILY || o.humidity != XP_HUM_DEWPOINT) return false;
+    if (np != 2 || profiles) return false;                                   // instantiated parcel counts (xp_multi_tu.hip)
+    for (int i = 0; i < np; ++i)
+        if (parcels[i].mode != XP_PARCEL_SURFACE && parcels[i].mode != XP_PARCEL_MOST_UNSTABLE && parcels[i].mode != XP_PARCEL_MIXED_LAYER) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -485,156 +621,103 @@ int xp_set_family_table(const double *tab, int64_t n_lnp, int64_t n_label) {
 
 int xp_cape_cin(const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel, const xp_opts *o,
                 xp_scalars_out *scalars, xp_profile_out *profile, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    Stager st(stream);
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    const xp_opts oo = o ? *o : default_opts();
     xp::CapeArgs a;
-    if ((rc = fill_common(st, p, t, td, parcel, o, &a))) return rc;
-    if ((rc = stage_scalars(st, scalars, a.ncol, &a.s))) return rc;
-    if (profile) {
-        if (profile->dtype != XP_F32 && profile->dtype != XP_F64) return fail(XP_E_ARG, "profile: bad dtype");
-        if (profile->nlev_out < a.nlev + 1) return fail(XP_E_ARG, "profile: nlev_out must be >= nlev + 1");
-        if (profile->mem == XP_MEM_HOST && !(profile->col_stride == 1 && profile->lev_stride == a.ncol))
-            return fail(XP_E_ARG, "profile: host arrays must be dense (nlev_out, ncol)");
-        void *src[6] = {profile->pressure, profile->temperature, profile->virtual_temperature,
-                        profile->environment_temperature, profile->environment_virtual_temperature,
-                        profile->environment_dewpoint};
-        size_t b = (size_t)profile->nlev_out * (size_t)a.ncol * esize(profile->dtype);
-        for (int v = 0; v < 6; ++v)
-            if ((rc = st.out(src[v], b, profile->mem, &a.prof.v[v]))) return rc;
-        a.prof.nlev_out = profile->nlev_out; a.prof.ls = profile->lev_stride; a.prof.cs = profile->col_stride;
-        bool rows = false;
-        for (int v = 0; v < 6; ++v) rows = rows || a.prof.v[v] != nullptr;
-        if (!rows) a.prof.nlev_out = 0;                    // lifted index only: the kernel's row loops see an empty profile
-        a.prof.f64 = profile->dtype == XP_F64;
-        bool all6 = true;
-        for (int v = 0; v < 6; ++v) all6 = all6 && a.prof.v[v] != nullptr;
-        a.prof.native6 = all6 && profile->dtype == p->dtype;
-        if (profile->lifted_index) {
-            if (!(profile->lifted_index_pressure > 0.0)) return fail(XP_E_ARG, "profile: lifted_index_pressure must be positive");
-            if ((rc = st.out(profile->lifted_index, (size_t)a.ncol * esize(profile->dtype), profile->mem, &a.prof.li))) return rc;
-            a.prof.li_x = log(profile->lifted_index_pressure);
-        }
-    }
-    void *flags = nullptr;
-    if (o && o->moist_mode == XP_MOIST_FAMILY && a.ncol > 0) {
-        HIP_TRY(hipMallocAsync(&flags, sizeof(int32_t) * (size_t)a.ncol, st.s));   // stream-ordered scratch: which columns need RK4
-        st.scratch.push_back(flags);                         // released by the Stager on every path out of this function
-        a.flags = (int32_t *)flags;
-        // larger grids run persistent wavefronts (k_cape_cin, PERSIST); XP_PERSIST_MIN_COLS: A/B.  Measured per grid size
-        // (profiles/r03_persist.txt, scripts/run_gpu_persist.py): equal to the ordinary launch up to two rounds of
-        // workgroups (512 Ki columns), 10-13 % faster from three rounds on (768 Ki ... 2 Mi columns of 64 f64 levels; c2:
-        // 0.64 -> 0.575 ms) -- a workgroup's sixteen wavefronts no longer wait for the slowest of them before the next
-        // sixteen tiles start.  (Round 2's kernels gained nothing from it below 4 Mi columns.)
-        static const long long persist_env = [] { const char *e = getenv("XP_PERSIST_MIN_COLS"); return e ? atoll(e) : -1ll; }();
-        const bool searching = parcel->mode == XP_PARCEL_MOST_UNSTABLE || parcel->mode == XP_PARCEL_MIXED_LAYER;
-        const long long persist_min = persist_env >= 0 ? persist_env : searching ? (1ll << 19) : (3ll << 18);
-        a.persist = (long long)a.ncol >= persist_min && a.ncol < (1ll << 36);
-    }
-    if (p->dtype == XP_F64) launch_cape_pm<double>(a, parcel->mode, profile != nullptr, st.s);
-    else launch_cape_pm<float>(a, parcel->mode, profile != nullptr, st.s);
+    int32_t *flags;
+    int rc;
+    if ((rc = fill_common(st, p, t, td, parcel, oo, &a)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
+        (rc = family_flags(st, oo, a.ncol, &flags))) return rc;
+    cape_pass(st, a, p->dtype, parcel->mode, profile != nullptr, flags);
     return st.finish();
 }
 
-namespace {
-bool multi_fused_ok(int32_t np, const xp_parcel *parcels, const xp_opts *o, const xp_profile_out *profiles) {
-    static const bool force = getenv("XP_MULTI_FUSED") != nullptr;           // A/B: fuse whenever possible
-    if (!o || o->moist_mode != XP_MOIST_FAMILY || o->humidity != XP_HUM_DEWPOINT) return false;
-    if (!force && !(o->flags & XP_OPT_FUSE_PARCELS)) return false;
-    if (np != 2) return false;                                               // instantiated parcel counts (xp_multi_tu.hip)
-    for (int i = 0; i < np; ++i) {
-        if (parcels[i].mode != XP_PARCEL_SURFACE && parcels[i].mode != XP_PARCEL_MOST_UNSTABLE && parcels[i].mode != XP_PARCEL_MIXED_LAYER) return false;
-        if (profiles) return false;
-    }
-    return true;
-}
-}  // namespace
-
 int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int32_t np, const xp_parcel *parcels,
                       const xp_opts *o, xp_scalars_out *scalars, xp_profile_out *profiles, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
     if (np < 1 || np > xp::MULTI_MAX) return fail(XP_E_ARG, "xp_cape_cin_multi: 1...%d parcels", xp::MULTI_MAX);
     if (!parcels || !scalars) return fail(XP_E_ARG, "xp_cape_cin_multi: null parcels / scalars");
-    if (!multi_fused_ok(np, parcels, o, profiles)) {
-        for (int i = 0; i < np; ++i) {
-            int rc = xp_cape_cin(p, t, td, &parcels[i], o, &scalars[i], profiles ? &profiles[i] : nullptr, stream);
-            if (rc) return rc;
-        }
-        return XP_OK;
+    const xp_opts oo = o ? *o : default_opts();
+    xp::CapeArgs a, pa[xp::MULTI_MAX];
+    int rc;
+    // every parcel is checked, and its outputs staged, before anything runs; p / T / Td are staged once
+    if ((rc = check_cape(p, t, td, np, parcels, oo)) || (rc = stage_cape(st, p, t, td, oo, &a))) return rc;
+    for (int i = 0; i < np; ++i) {
+        pa[i] = a;
+        if ((rc = set_parcel(st, parcels[i], p, &pa[i])) ||
+            (rc = stage_cape_out(st, p->dtype, &scalars[i], profiles ? &profiles[i] : nullptr, &pa[i]))) return rc;
     }
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    Stager st(stream);
+    const int64_t ncol = a.ncol;
+    if (!multi_fused_ok(np, parcels, oo, profiles)) {        // one pass per parcel
+        int32_t *flags;
+        if ((rc = family_flags(st, oo, ncol, &flags))) return rc;
+        for (int i = 0; i < np; ++i) cape_pass(st, pa[i], p->dtype, parcels[i].mode, profiles != nullptr, flags);
+        return st.finish();
+    }
     xp::MultiArgs m;
     memset(&m, 0, sizeof(m));
-    if ((rc = fill_common(st, p, t, td, &parcels[0], o, &m.base))) return rc;
+    m.base = a;
     m.np = np;
-    const int64_t ncol = m.base.ncol;
     for (int i = 0; i < np; ++i) {
         m.mode[i] = parcels[i].mode;                                         // XP_PARCEL_* == xp::PM_*
         m.depth[i] = parcels[i].depth;
-        if ((rc = stage_scalars(st, &scalars[i], ncol, &m.s[i]))) return rc;
+        m.s[i] = pa[i].s;
     }
     if (ncol == 0) return st.finish();
-    void *flags = nullptr;
-    HIP_TRY(hipMallocAsync(&flags, sizeof(int32_t) * (size_t)ncol * (size_t)np, st.s));
-    st.scratch.push_back(flags);
-    for (int i = 0; i < np; ++i) m.flags[i] = (int32_t *)flags + (size_t)i * (size_t)ncol;
-    static const long long persist_env = [] { const char *e = getenv("XP_PERSIST_MIN_COLS"); return e ? atoll(e) : -1ll; }();
-    m.base.persist = (long long)ncol >= (persist_env >= 0 ? persist_env : (1ll << 19)) && ncol < (1ll << 36);
-    const bool f64 = p->dtype == XP_F64;
-    if (f64) xp::launch_cape_multi<double, 2>(m, st.s); else xp::launch_cape_multi<float, 2>(m, st.s);
-    // columns a chain's family table could not serve: the single-parcel RK4 kernel redoes them, chain by chain
-    for (int i = 0; i < np; ++i) {
-        xp::CapeArgs b = m.base;
-        b.depth = m.depth[i]; b.s = m.s[i]; b.flags = m.flags[i]; b.only_flagged = 1; b.persist = 0;
-        if (f64) xp::launch_cape_mode<double, 0>(b, m.mode[i], false, st.s);
-        else xp::launch_cape_mode<float, 0>(b, m.mode[i], false, st.s);
-    }
+    int32_t *flags;
+    if ((rc = st.alloc(sizeof(int32_t) * (size_t)ncol * (size_t)np, &flags))) return rc;
+    for (int i = 0; i < np; ++i) m.flags[i] = flags + (size_t)i * (size_t)ncol;
+    m.base.persist = persist(-1, ncol);
+    by_dtype(p->dtype, [&](auto z) {
+        using T = decltype(z);
+        xp::launch_cape_multi<T, 2>(m, st.s);
+        // columns a chain's family table could not serve: the single-parcel RK4 kernel redoes them, chain by chain
+        for (int i = 0; i < np; ++i) {
+            xp::CapeArgs b = pa[i];
+            b.flags = m.flags[i]; b.only_flagged = 1;
+            xp::launch_cape_mode<T, 0>(b, m.mode[i], false, st.s);
+        }
+    });
     return st.finish();
 }
 
 int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_nans, xp_conv_out *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
     if (!in || !out) return fail(XP_E_ARG, "xp_conv_properties: null argument");
     const xp_view *p = in->pressure, *t = in->temperature, *q = in->specific_humidity, *z = in->height_asl;
     const xp_view *wu = in->wind_u, *wv = in->wind_v, *wh = in->wind_height_above_surface;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(t, "temperature")) || (rc = check_view(q, "specific_humidity")) ||
-        (rc = check_view(z, "height_asl")) || (rc = same_shape(p, t, "pressure/temperature")) ||
-        (rc = same_shape(p, q, "pressure/specific_humidity")) || (rc = same_shape(p, z, "pressure/height_asl"))) return rc;
-    if ((rc = check_view(wu, "wind_u")) || (rc = check_view(wv, "wind_v")) || (rc = check_view(wh, "wind_height_above_surface")) ||
-        (rc = same_shape(wu, wv, "wind_u/wind_v")) || (rc = same_shape(wu, wh, "wind_u/wind_height_above_surface"))) return rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {q, "specific_humidity"}, {z, "height_asl"}})) ||
+        (rc = check_views({{wu, "wind_u"}, {wv, "wind_v"}, {wh, "wind_height_above_surface"}}))) return rc;
     if (wu->ncol != p->ncol || wu->dtype != p->dtype || wu->mem != p->mem || t->mem != p->mem || q->mem != p->mem || z->mem != p->mem)
         return fail(XP_E_ARG, "xp_conv_properties: the views must agree in columns, dtype and mem");
     if (!in->surface_wind_u || !in->surface_wind_v) return fail(XP_E_ARG, "xp_conv_properties: null surface wind");
-    Stager st(stream);
     const int64_t nlev = p->nlev, ncol = p->ncol;
-    const size_t es = esize(p->dtype), cb = (size_t)ncol * es;
+    const size_t cb = rows_bytes(p, 1);
     const int mem = p->mem;
     if (ncol == 0) return XP_OK;
+    xp_opts oo = o ? *o : default_opts();
+    oo.humidity = XP_HUM_DEWPOINT;
+    if ((rc = check_opts(oo))) return rc;
     // inputs on the device (host views are dense by contract: staged as they are)
     xp_view dv[7];
     const xp_view *src[7] = {p, t, q, z, wu, wv, wh};
     for (int i = 0; i < 7; ++i) {
         dv[i] = *src[i];
         const void *d;
-        if ((rc = st.in(src[i]->data, (size_t)src[i]->nlev * (size_t)ncol * es, mem, &d))) return rc;
+        if ((rc = st.in(src[i]->data, rows_bytes(src[i], src[i]->nlev), mem, &d))) return rc;
         dv[i].data = d; dv[i].mem = XP_MEM_DEVICE;
     }
     const void *sfu, *sfv;
     if ((rc = st.in(in->surface_wind_u, cb, mem, &sfu)) || (rc = st.in(in->surface_wind_v, cb, mem, &sfv))) return rc;
     // scratch: the dewpoint grid and per-point temporaries
-    auto scratch = [&](size_t bytes, void **ptr) -> int {
-        HIP_TRY(hipMallocAsync(ptr, bytes ? bytes : 1, st.s));
-        st.scratch.push_back(*ptr);
-        return 0;
-    };
-    void *td = nullptr, *tmp = nullptr, *valid = nullptr;
+    void *td, *tmp;
+    int32_t *valid;
     enum { T850, T700, T500, TD850, Z700, Z500, HIU, HIV, MUP, MUTD, NTMP };
-    if ((rc = scratch((size_t)nlev * cb, &td)) || (rc = scratch((size_t)NTMP * cb, &tmp)) || (rc = scratch((size_t)ncol * 4, &valid))) return rc;
+    if ((rc = st.alloc((size_t)nlev * cb, &td)) || (rc = st.alloc((size_t)NTMP * cb, &tmp)) || (rc = st.alloc((size_t)ncol * 4, &valid))) return rc;
     auto tp = [&](int i) { return (void *)((char *)tmp + (size_t)i * cb); };
     // outputs: the caller's buffers when they live on the device, staged otherwise; results that are also inputs of the
     // per-point kernel need a buffer even when the caller does not want them
@@ -646,8 +729,7 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
                             out->shear_u, out->shear_v, out->shear_magnitude, (void *)out->positive_shear};
     for (int i = 0; i < 21; ++i) {
         const size_t b = i == 20 ? (size_t)ncol * 4 : cb;
-        if (want[i]) { if ((rc = st.out(want[i], b, mem, &o_[i]))) return rc; }
-        else if ((rc = scratch(b, &o_[i]))) return rc;
+        if ((rc = want[i] ? st.out(want[i], b, mem, &o_[i]) : st.alloc(b, &o_[i]))) return rc;
     }
     enum { O_MU_CAPE, O_MU_CIN, O_MU_W, O_MU_LI, O_MU_DCI, O_M1_CAPE, O_M1_CIN, O_M1_LI, O_M1_DCI, O_M5_CAPE, O_M5_CIN, O_M5_LI, O_M5_DCI,
            O_LAPSE, O_T500, O_FRZ, O_MLT, O_SHU, O_SHV, O_SHM, O_POS };
@@ -658,22 +740,18 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
     ca.q = {dv[2].data, dv[2].lev_stride, dv[2].col_stride}; ca.z = {dv[3].data, dv[3].lev_stride, dv[3].col_stride};
     ca.nlev = nlev; ca.ncol = ncol; ca.td = td;
     ca.t850 = tp(T850); ca.t700 = tp(T700); ca.t500 = tp(T500); ca.td850 = tp(TD850); ca.z700 = tp(Z700); ca.z500 = tp(Z500);
-    ca.freezing = o_[O_FRZ]; ca.melting = o_[O_MLT]; ca.valid = (int32_t *)valid;
-    if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_conv_columns<double>), dim3(blocks(ncol)), dim3(256), 0, st.s, ca);
-    else hipLaunchKernelGGL((xp::k_conv_columns<float>), dim3(blocks(ncol)), dim3(256), 0, st.s, ca);
+    ca.freezing = o_[O_FRZ]; ca.melting = o_[O_MLT]; ca.valid = valid;
+    by_dtype(p->dtype, [&](auto z_) { launch(xp::k_conv_columns<decltype(z_)>, ncol, st, ca); });
     // 2. the three parcels (pf.py:1984-2006), lifted index out of the same passes
     xp_view tdv = dv[0];
     tdv.data = td; tdv.lev_stride = ncol; tdv.col_stride = 1;
-    xp_opts oo;
-    if (o) oo = *o; else { memset(&oo, 0, sizeof(oo)); oo.virtual_temperature_correction = 1; oo.lcl_interp = XP_LCL_INTERP_LOG; oo.pos_cape_neg_cin = 1; oo.compute = XP_F64; }
-    oo.humidity = XP_HUM_DEWPOINT;
+    xp::CapeArgs a;
+    int32_t *flags;
+    if ((rc = stage_cape(st, &dv[0], &dv[1], &tdv, oo, &a)) || (rc = family_flags(st, oo, ncol, &flags))) return rc;
     const struct { int mode; double depth; int cape, cin, li; } pc[3] = {{XP_PARCEL_MOST_UNSTABLE, 250.0, O_MU_CAPE, O_MU_CIN, O_MU_LI},
                                                                         {XP_PARCEL_MIXED_LAYER, 100.0, O_M1_CAPE, O_M1_CIN, O_M1_LI},
                                                                         {XP_PARCEL_MIXED_LAYER, 50.0, O_M5_CAPE, O_M5_CIN, O_M5_LI}};
     for (int i = 0; i < 3; ++i) {
-        xp_parcel par;
-        memset(&par, 0, sizeof(par));
-        par.mode = pc[i].mode; par.depth = pc[i].depth;
         xp_scalars_out so;
         memset(&so, 0, sizeof(so));
         so.dtype = p->dtype; so.mem = XP_MEM_DEVICE; so.cape = o_[pc[i].cape]; so.cin = o_[pc[i].cin];
@@ -682,14 +760,17 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
         memset(&po, 0, sizeof(po));
         po.dtype = p->dtype; po.mem = XP_MEM_DEVICE; po.nlev_out = nlev + 1; po.lev_stride = ncol; po.col_stride = 1;
         po.lifted_index = o_[pc[i].li]; po.lifted_index_pressure = 500.0;
-        if ((rc = xp_cape_cin(&dv[0], &dv[1], &tdv, &par, &oo, &so, &po, stream))) return rc;
+        xp::CapeArgs b = a;
+        b.depth = pc[i].depth;
+        if ((rc = stage_cape_out(st, p->dtype, &so, &po, &b))) return rc;
+        cape_pass(st, b, p->dtype, pc[i].mode, true, flags);
     }
     // 3. wind at 6000 m above the surface (pf.py:2240-2243: linear interpolation in height)
     {
         const xp_view *vars[2] = {&dv[4], &dv[5]};
         const double at6 = 6000.0;
         void *outs[2] = {tp(HIU), tp(HIV)};
-        if ((rc = xp_interp_levels(&dv[6], 2, vars, 1, &at6, 0, outs, stream))) return rc;
+        if ((rc = interp_levels(st, &dv[6], 2, vars, 1, &at6, 0, outs))) return rc;
     }
     // 4. per point
     xp::ConvFinishArgs fa;
@@ -698,7 +779,7 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
     fa.mu_p = tp(MUP); fa.mu_td = tp(MUTD);
     fa.li[0] = o_[O_MU_LI]; fa.li[1] = o_[O_M1_LI]; fa.li[2] = o_[O_M5_LI];
     fa.t850 = tp(T850); fa.t700 = tp(T700); fa.t500 = tp(T500); fa.td850 = tp(TD850); fa.z700 = tp(Z700); fa.z500 = tp(Z500);
-    fa.hi_u = tp(HIU); fa.hi_v = tp(HIV); fa.sfc_u = sfu; fa.sfc_v = sfv; fa.valid = (const int32_t *)valid;
+    fa.hi_u = tp(HIU); fa.hi_v = tp(HIV); fa.sfc_u = sfu; fa.sfc_v = sfv; fa.valid = valid;
     fa.cape[0] = o_[O_MU_CAPE]; fa.cape[1] = o_[O_M1_CAPE]; fa.cape[2] = o_[O_M5_CAPE];
     fa.cin[0] = o_[O_MU_CIN]; fa.cin[1] = o_[O_M1_CIN]; fa.cin[2] = o_[O_M5_CIN];
     fa.li_out[0] = o_[O_MU_LI]; fa.li_out[1] = o_[O_M1_LI]; fa.li_out[2] = o_[O_M5_LI];
@@ -706,325 +787,244 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
     fa.mu_mixing_ratio = o_[O_MU_W]; fa.dci[0] = o_[O_MU_DCI]; fa.dci[1] = o_[O_M1_DCI]; fa.dci[2] = o_[O_M5_DCI];
     fa.lapse = o_[O_LAPSE]; fa.temp_500 = o_[O_T500]; fa.shear_u = o_[O_SHU]; fa.shear_v = o_[O_SHV]; fa.shear_mag = o_[O_SHM];
     fa.positive_shear = (int32_t *)o_[O_POS];
-    if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_conv_finish<double>), dim3(blocks(ncol)), dim3(256), 0, st.s, fa);
-    else hipLaunchKernelGGL((xp::k_conv_finish<float>), dim3(blocks(ncol)), dim3(256), 0, st.s, fa);
+    by_dtype(p->dtype, [&](auto z_) { launch(xp::k_conv_finish<decltype(z_)>, ncol, st, fa); });
     return st.finish();
 }
 
 int xp_select_parcel(const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
                      xp_scalars_out *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    Stager st(stream);
+    Entry st(stream);
+    if (st.rc) return st.rc;
     xp::CapeArgs a;
-    if ((rc = fill_common(st, p, t, td, parcel, nullptr, &a))) return rc;
+    int rc;
+    if ((rc = fill_common(st, p, t, td, parcel, default_opts(), &a))) return rc;
     if (parcel->mode != XP_PARCEL_MOST_UNSTABLE && parcel->mode != XP_PARCEL_MIXED_LAYER)
         return fail(XP_E_ARG, "xp_select_parcel: mode must be most-unstable or mixed-layer");
     if ((rc = stage_scalars(st, out, a.ncol, &a.s))) return rc;
-    if (a.ncol) {
-        dim3 gr(blocks(a.ncol)), bl(256);
-        if (p->dtype == XP_F64) {
-            if (parcel->mode == XP_PARCEL_MOST_UNSTABLE) hipLaunchKernelGGL((xp::k_select_parcel<double, xp::PM_MU>), gr, bl, 0, st.s, a);
-            else hipLaunchKernelGGL((xp::k_select_parcel<double, xp::PM_ML>), gr, bl, 0, st.s, a);
-        } else {
-            if (parcel->mode == XP_PARCEL_MOST_UNSTABLE) hipLaunchKernelGGL((xp::k_select_parcel<float, xp::PM_MU>), gr, bl, 0, st.s, a);
-            else hipLaunchKernelGGL((xp::k_select_parcel<float, xp::PM_ML>), gr, bl, 0, st.s, a);
-        }
-    }
+    by_dtype(p->dtype, [&](auto z) {
+        using T = decltype(z);
+        if (parcel->mode == XP_PARCEL_MOST_UNSTABLE) launch(xp::k_select_parcel<T, xp::PM_MU>, a.ncol, st, a);
+        else launch(xp::k_select_parcel<T, xp::PM_ML>, a.ncol, st, a);
+    });
     return st.finish();
 }
 
 int xp_mixed_layer(const xp_view *p, const xp_view *v, double depth, void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(v, "variable")) || (rc = same_shape(p, v, "pressure/variable"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {v, "variable"}}))) return rc;
     if (!out) return fail(XP_E_ARG, "xp_mixed_layer: null output");
-    Stager st(stream);
     xp::View pv, vv;
     void *od;
-    if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, v, &vv)) ||
-        (rc = st.out(out, (size_t)p->ncol * esize(p->dtype), p->mem, &od))) return rc;
-    if (p->ncol) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_mixed_layer<double>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, vv, p->nlev, p->ncol, depth, od, 1);
-        else hipLaunchKernelGGL((xp::k_mixed_layer<float>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, vv, p->nlev, p->ncol, depth, od, 0);
-    }
+    if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, v, &vv)) || (rc = st.out(out, rows_bytes(p, 1), p->mem, &od))) return rc;
+    by_dtype(p->dtype, [&](auto z) { launch(xp::k_mixed_layer<decltype(z)>, p->ncol, st, pv, vv, p->nlev, p->ncol, depth, od, (int)(p->dtype == XP_F64)); });
     return st.finish();
 }
 
 int xp_lcl(int64_t n, int32_t dtype, int32_t mem, const void *pp, const void *pt, const void *ptd, void *lp, void *lt,
            void *ltv, int32_t *status, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
     if (n < 0 || !pp || !pt || !ptd) return fail(XP_E_ARG, "xp_lcl: null input");
     if (dtype != XP_F32 && dtype != XP_F64) return fail(XP_E_ARG, "xp_lcl: bad dtype");
-    Stager st(stream);
     size_t b = (size_t)n * esize(dtype);
     const void *dp, *dt, *dtd;
     void *op, *ot, *otv, *os;
+    int rc;
     if ((rc = st.in(pp, b, mem, &dp)) || (rc = st.in(pt, b, mem, &dt)) || (rc = st.in(ptd, b, mem, &dtd)) ||
         (rc = st.out(lp, b, mem, &op)) || (rc = st.out(lt, b, mem, &ot)) || (rc = st.out(ltv, b, mem, &otv)) ||
         (rc = st.out(status, (size_t)n * 4, mem, &os))) return rc;
-    if (n) {
-        if (dtype == XP_F64) hipLaunchKernelGGL((xp::k_lcl<double>), dim3(blocks(n)), dim3(256), 0, st.s, n, dp, dt, dtd, op, ot, otv, (int32_t *)os);
-        else hipLaunchKernelGGL((xp::k_lcl<float>), dim3(blocks(n)), dim3(256), 0, st.s, n, dp, dt, dtd, op, ot, otv, (int32_t *)os);
-    }
+    by_dtype(dtype, [&](auto z) { launch(xp::k_lcl<decltype(z)>, n, st, n, dp, dt, dtd, op, ot, otv, (int32_t *)os); });
     return st.finish();
 }
 
 int xp_dry_lapse(const xp_view *p, const void *pt, const void *pp, void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
     if ((rc = check_view(p, "pressure"))) return rc;
     if (!pt || !out) return fail(XP_E_ARG, "xp_dry_lapse: null argument");
-    Stager st(stream);
-    xp::View pv; xp::OutView ov;
-    size_t cb = (size_t)p->ncol * esize(p->dtype), fb = cb * (size_t)p->nlev;
+    xp::View pv;
     const void *dt, *dp;
     void *od;
-    if ((rc = stage_view(st, p, &pv)) || (rc = st.in(pt, cb, p->mem, &dt)) || (rc = st.in(pp, cb, p->mem, &dp)) ||
-        (rc = st.out(out, fb, p->mem, &od))) return rc;
-    ov.data = od; ov.ls = p->lev_stride; ov.cs = p->col_stride;
-    if (p->ncol) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_dry_lapse<double>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, p->nlev, p->ncol, dt, dp, ov);
-        else hipLaunchKernelGGL((xp::k_dry_lapse<float>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, p->nlev, p->ncol, dt, dp, ov);
-    }
+    if ((rc = stage_view(st, p, &pv)) || (rc = st.in(pt, rows_bytes(p, 1), p->mem, &dt)) || (rc = st.in(pp, rows_bytes(p, 1), p->mem, &dp)) ||
+        (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
+    by_dtype(p->dtype, [&](auto z) { launch(xp::k_dry_lapse<decltype(z)>, p->ncol, st, pv, p->nlev, p->ncol, dt, dp, out_like(od, p)); });
     return st.finish();
 }
 
+// component entry points: XP_MOIST_FAMILY is served by the RK4 stepper of their kernels
 int xp_moist_lapse(const xp_view *p, const void *pt, const void *pp, int32_t moist_mode, void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
     if ((rc = check_view(p, "pressure"))) return rc;
     if (!pt || !out) return fail(XP_E_ARG, "xp_moist_lapse: null argument");
-    if (moist_mode == XP_MOIST_TABLE && !g.tables) return fail(XP_E_NO_TABLES, "Call load_moist_adiabat_lookups first.");
-    Stager st(stream);
-    xp::View pv; xp::OutView ov;
-    size_t cb = (size_t)p->ncol * esize(p->dtype), fb = cb * (size_t)p->nlev;
+    const int tm = moist_mode == XP_MOIST_TABLE;
+    TableSet ts;
+    xp::View pv;
     const void *dt, *dp;
     void *od;
-    if ((rc = stage_view(st, p, &pv)) || (rc = st.in(pt, cb, p->mem, &dt)) || (rc = st.in(pp, cb, p->mem, &dp)) ||
-        (rc = st.out(out, fb, p->mem, &od))) return rc;
-    ov.data = od; ov.ls = p->lev_stride; ov.cs = p->col_stride;
-    xp::Tables tb = g.tb;
-    int tm = moist_mode == XP_MOIST_TABLE;   /* XP_MOIST_FAMILY is served by the RK4 stepper in the component kernels */
-    if (p->ncol) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_moist_lapse<double>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, p->nlev, p->ncol, dt, dp, tm, tb, (const double *)g.es_tab, ov);
-        else hipLaunchKernelGGL((xp::k_moist_lapse<float>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, p->nlev, p->ncol, dt, dp, tm, tb, (const double *)g.es_tab, ov);
-    }
+    if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &pv)) || (rc = st.in(pt, rows_bytes(p, 1), p->mem, &dt)) ||
+        (rc = st.in(pp, rows_bytes(p, 1), p->mem, &dp)) || (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
+    by_dtype(p->dtype, [&](auto z) {
+        launch(xp::k_moist_lapse<decltype(z)>, p->ncol, st, pv, p->nlev, p->ncol, dt, dp, tm, ts.tb, ts.es, out_like(od, p));
+    });
     return st.finish();
 }
 
 int xp_parcel_profile(const xp_view *p, const void *pp, const void *pt, const void *ptd, int32_t moist_mode,
                       void *t_out, void *tv_out, void *lp, void *lt, void *ltv, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
     if ((rc = check_view(p, "pressure"))) return rc;
     if (!pp || !pt || !ptd) return fail(XP_E_ARG, "xp_parcel_profile: null parcel");
-    if (moist_mode == XP_MOIST_TABLE && !g.tables) return fail(XP_E_NO_TABLES, "Call load_moist_adiabat_lookups first.");
-    Stager st(stream);
-    xp::View pv; xp::OutView ot, otv;
-    size_t cb = (size_t)p->ncol * esize(p->dtype), fb = cb * (size_t)p->nlev;
+    const int tm = moist_mode == XP_MOIST_TABLE;
+    TableSet ts;
+    xp::View pv;
+    const size_t cb = rows_bytes(p, 1), fb = rows_bytes(p, p->nlev);
     const void *dpp, *dpt, *dptd;
     void *d1, *d2, *d3, *d4, *d5;
-    if ((rc = stage_view(st, p, &pv)) || (rc = st.in(pp, cb, p->mem, &dpp)) || (rc = st.in(pt, cb, p->mem, &dpt)) ||
-        (rc = st.in(ptd, cb, p->mem, &dptd)) || (rc = st.out(t_out, fb, p->mem, &d1)) || (rc = st.out(tv_out, fb, p->mem, &d2)) ||
-        (rc = st.out(lp, cb, p->mem, &d3)) || (rc = st.out(lt, cb, p->mem, &d4)) || (rc = st.out(ltv, cb, p->mem, &d5))) return rc;
-    ot.data = d1; ot.ls = p->lev_stride; ot.cs = p->col_stride;
-    otv.data = d2; otv.ls = p->lev_stride; otv.cs = p->col_stride;
-    xp::Tables tb = g.tb;
-    int tm = moist_mode == XP_MOIST_TABLE;   /* XP_MOIST_FAMILY is served by the RK4 stepper in the component kernels */
-    if (p->ncol) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_parcel_profile<double>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, p->nlev, p->ncol, dpp, dpt, dptd, tm, tb, (const double *)g.es_tab, ot, otv, d3, d4, d5);
-        else hipLaunchKernelGGL((xp::k_parcel_profile<float>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, p->nlev, p->ncol, dpp, dpt, dptd, tm, tb, (const double *)g.es_tab, ot, otv, d3, d4, d5);
-    }
+    if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &pv)) || (rc = st.in(pp, cb, p->mem, &dpp)) ||
+        (rc = st.in(pt, cb, p->mem, &dpt)) || (rc = st.in(ptd, cb, p->mem, &dptd)) || (rc = st.out(t_out, fb, p->mem, &d1)) ||
+        (rc = st.out(tv_out, fb, p->mem, &d2)) || (rc = st.out(lp, cb, p->mem, &d3)) || (rc = st.out(lt, cb, p->mem, &d4)) ||
+        (rc = st.out(ltv, cb, p->mem, &d5))) return rc;
+    by_dtype(p->dtype, [&](auto z) {
+        launch(xp::k_parcel_profile<decltype(z)>, p->ncol, st, pv, p->nlev, p->ncol, dpp, dpt, dptd, tm, ts.tb, ts.es,
+               out_like(d1, p), out_like(d2, p), d3, d4, d5);
+    });
     return st.finish();
 }
 
 int xp_lfc_el(const xp_view *p, const xp_view *par, const xp_view *env, const void *lcl_p, const void *lcl_t,
               xp_scalars_out *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(par, "parcel_temperature")) || (rc = check_view(env, "temperature")) ||
-        (rc = same_shape(p, par, "pressure/parcel_temperature")) || (rc = same_shape(p, env, "pressure/temperature"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {par, "parcel_temperature"}, {env, "temperature"}}))) return rc;
     if (!lcl_p || !lcl_t || !out) return fail(XP_E_ARG, "xp_lfc_el: null argument");
-    Stager st(stream);
     xp::View pv, pav, ev;
     xp::ScalarsOut so;
-    size_t cb = (size_t)p->ncol * esize(p->dtype);
     const void *dlp, *dlt;
     if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, par, &pav)) || (rc = stage_view(st, env, &ev)) ||
-        (rc = st.in(lcl_p, cb, p->mem, &dlp)) || (rc = st.in(lcl_t, cb, p->mem, &dlt)) ||
+        (rc = st.in(lcl_p, rows_bytes(p, 1), p->mem, &dlp)) || (rc = st.in(lcl_t, rows_bytes(p, 1), p->mem, &dlt)) ||
         (rc = stage_scalars(st, out, p->ncol, &so))) return rc;
-    if (p->ncol) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_lfc_el<double>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, pav, ev, p->nlev, p->ncol, dlp, dlt, so);
-        else hipLaunchKernelGGL((xp::k_lfc_el<float>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, pav, ev, p->nlev, p->ncol, dlp, dlt, so);
-    }
+    by_dtype(p->dtype, [&](auto z) { launch(xp::k_lfc_el<decltype(z)>, p->ncol, st, pv, pav, ev, p->nlev, p->ncol, dlp, dlt, so); });
     return st.finish();
 }
 
 int xp_cape_cin_base(const xp_view *p, const xp_view *env, const xp_view *par, const void *lfc_p, const void *el_p,
                      const xp_opts *o, void *cape, void *cin, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(par, "parcel_temperature")) || (rc = check_view(env, "temperature")) ||
-        (rc = same_shape(p, par, "pressure/parcel_temperature")) || (rc = same_shape(p, env, "pressure/temperature"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {par, "parcel_temperature"}, {env, "temperature"}}))) return rc;
     if (!lfc_p || !el_p) return fail(XP_E_ARG, "xp_cape_cin_base: null argument");
-    Stager st(stream);
     xp::View pv, pav, ev;
-    size_t cb = (size_t)p->ncol * esize(p->dtype);
+    const size_t cb = rows_bytes(p, 1);
     const void *dl, *de;
     void *dc, *dn;
     if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, par, &pav)) || (rc = stage_view(st, env, &ev)) ||
         (rc = st.in(lfc_p, cb, p->mem, &dl)) || (rc = st.in(el_p, cb, p->mem, &de)) || (rc = st.out(cape, cb, p->mem, &dc)) ||
         (rc = st.out(cin, cb, p->mem, &dn))) return rc;
-    int pn = o ? o->pos_cape_neg_cin : 1, pz = o ? o->post_zero_cin : 0;
-    if (p->ncol) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_cape_cin_base<double>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, ev, pav, p->nlev, p->ncol, dl, de, pn, pz, dc, dn);
-        else hipLaunchKernelGGL((xp::k_cape_cin_base<float>), dim3(blocks(p->ncol)), dim3(256), 0, st.s, pv, ev, pav, p->nlev, p->ncol, dl, de, pn, pz, dc, dn);
-    }
+    const xp_opts oo = o ? *o : default_opts();
+    by_dtype(p->dtype, [&](auto z) {
+        launch(xp::k_cape_cin_base<decltype(z)>, p->ncol, st, pv, ev, pav, p->nlev, p->ncol, dl, de, oo.pos_cape_neg_cin, oo.post_zero_cin, dc, dn);
+    });
     return st.finish();
 }
 
 int xp_wet_bulb_temperature(const xp_view *p, const xp_view *t, const xp_view *td, int32_t moist_mode, void *out,
                             void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(t, "temperature")) || (rc = check_view(td, "dewpoint")) ||
-        (rc = same_shape(p, t, "pressure/temperature")) || (rc = same_shape(p, td, "pressure/dewpoint"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}}))) return rc;
     if (!out) return fail(XP_E_ARG, "xp_wet_bulb_temperature: null output");
-    if (moist_mode == XP_MOIST_TABLE && !g.tables) return fail(XP_E_NO_TABLES, "Call load_moist_adiabat_lookups first.");
-    Stager st(stream);
-    xp::View pv, tv, tdv; xp::OutView ov;
+    const int tm = moist_mode == XP_MOIST_TABLE;
+    TableSet ts;
+    xp::View pv, tv, tdv;
     void *od;
-    if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, t, &tv)) || (rc = stage_view(st, td, &tdv)) ||
-        (rc = st.out(out, (size_t)p->nlev * (size_t)p->ncol * esize(p->dtype), p->mem, &od))) return rc;
-    ov.data = od; ov.ls = p->lev_stride; ov.cs = p->col_stride;
-    xp::Tables tb = g.tb;
-    int tm = moist_mode == XP_MOIST_TABLE;   /* XP_MOIST_FAMILY is served by the RK4 stepper in the component kernels */
-    int64_t n = p->nlev * p->ncol;
-    if (n) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_wet_bulb<double>), dim3(blocks(n)), dim3(256), 0, st.s, pv, tv, tdv, p->nlev, p->ncol, tm, tb, (const double *)g.es_tab, ov);
-        else hipLaunchKernelGGL((xp::k_wet_bulb<float>), dim3(blocks(n)), dim3(256), 0, st.s, pv, tv, tdv, p->nlev, p->ncol, tm, tb, (const double *)g.es_tab, ov);
-    }
+    if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &pv)) || (rc = stage_view(st, t, &tv)) ||
+        (rc = stage_view(st, td, &tdv)) || (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
+    by_dtype(p->dtype, [&](auto z) {
+        launch(xp::k_wet_bulb<decltype(z)>, p->nlev * p->ncol, st, pv, tv, tdv, p->nlev, p->ncol, tm, ts.tb, ts.es, out_like(od, p));
+    });
     return st.finish();
 }
 
 int xp_interp_level(const xp_view *coords, const xp_view *x, const void *at, int32_t at_is_scalar, int32_t log_coords,
                     void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(coords, "coords")) || (rc = check_view(x, "variable")) || (rc = same_shape(coords, x, "coords/variable"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{coords, "coords"}, {x, "variable"}}))) return rc;
     if (!at || !out) return fail(XP_E_ARG, "xp_interp_level: null argument");
-    Stager st(stream);
     xp::View cv, xv;
     const void *da;
     void *od;
-    size_t cb = (size_t)coords->ncol * esize(coords->dtype);
     if ((rc = stage_view(st, coords, &cv)) || (rc = stage_view(st, x, &xv)) ||
-        (rc = st.in(at, at_is_scalar ? esize(coords->dtype) : cb, coords->mem, &da)) ||
-        (rc = st.out(out, cb, coords->mem, &od))) return rc;
-    if (coords->ncol) {
-        if (coords->dtype == XP_F64) hipLaunchKernelGGL((xp::k_interp_level<double>), dim3(blocks(coords->ncol)), dim3(256), 0, st.s, cv, xv, coords->nlev, coords->ncol, da, (int)at_is_scalar, (int)log_coords, od);
-        else hipLaunchKernelGGL((xp::k_interp_level<float>), dim3(blocks(coords->ncol)), dim3(256), 0, st.s, cv, xv, coords->nlev, coords->ncol, da, (int)at_is_scalar, (int)log_coords, od);
-    }
+        (rc = st.in(at, at_is_scalar ? esize(coords->dtype) : rows_bytes(coords, 1), coords->mem, &da)) ||
+        (rc = st.out(out, rows_bytes(coords, 1), coords->mem, &od))) return rc;
+    by_dtype(coords->dtype, [&](auto z) {
+        launch(xp::k_interp_level<decltype(z)>, coords->ncol, st, cv, xv, coords->nlev, coords->ncol, da, (int)at_is_scalar, (int)log_coords, od);
+    });
     return st.finish();
 }
 
 int xp_interp_levels(const xp_view *coords, int32_t nvar, const xp_view *const *variables, int32_t ntarget, const double *at,
                      int32_t log_coords, void *const *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
     if (nvar < 1 || nvar > 4 || ntarget < 1 || ntarget > 4) return fail(XP_E_ARG, "xp_interp_levels: 1..4 variables and 1..4 coordinates");
     if (!variables || !at || !out) return fail(XP_E_ARG, "xp_interp_levels: null argument");
-    if ((rc = check_view(coords, "coords"))) return rc;
-    Stager st(stream);
-    xp::View cv;
-    xp::InterpMany m;
-    memset(&m, 0, sizeof(m));
-    if ((rc = stage_view(st, coords, &cv))) return rc;
-    size_t cb = (size_t)coords->ncol * esize(coords->dtype);
-    for (int v = 0; v < nvar; ++v) {
-        if ((rc = check_view(variables[v], "variable")) || (rc = same_shape(coords, variables[v], "coords/variable")) ||
-            (rc = stage_view(st, variables[v], &m.x[v]))) return rc;
-        for (int j = 0; j < ntarget; ++j)
-            if ((rc = st.out(out[v * ntarget + j], cb, coords->mem, &m.out[v * ntarget + j]))) return rc;
-    }
-    for (int j = 0; j < ntarget; ++j) m.at[j] = at[j];
-    if (coords->ncol) {
-        if (coords->dtype == XP_F64) launch_interp_levels_v<double>(nvar, ntarget, cv, m, coords->nlev, coords->ncol, (int)log_coords, st.s);
-        else launch_interp_levels_v<float>(nvar, ntarget, cv, m, coords->nlev, coords->ncol, (int)log_coords, st.s);
-    }
+    int rc;
+    for (int v = 0; v < nvar; ++v)
+        if ((rc = check_views({{coords, "coords"}, {variables[v], "variable"}}))) return rc;
+    if ((rc = interp_levels(st, coords, nvar, variables, ntarget, at, log_coords, out))) return rc;
     return st.finish();
 }
 
 int xp_dewpoint_from_specific_humidity(const xp_view *p, const xp_view *t, const xp_view *q, void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(p, "pressure")) || (rc = check_view(t, "temperature")) || (rc = check_view(q, "specific_humidity")) ||
-        (rc = same_shape(p, t, "pressure/temperature")) || (rc = same_shape(p, q, "pressure/specific_humidity"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {q, "specific_humidity"}}))) return rc;
     if (!out) return fail(XP_E_ARG, "xp_dewpoint_from_specific_humidity: null output");
-    Stager st(stream);
-    xp::View pv, tv, qv; xp::OutView ov;
+    xp::View pv, tv, qv;
     void *od;
     if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, t, &tv)) || (rc = stage_view(st, q, &qv)) ||
-        (rc = st.out(out, (size_t)p->nlev * (size_t)p->ncol * esize(p->dtype), p->mem, &od))) return rc;
-    ov.data = od; ov.ls = p->lev_stride; ov.cs = p->col_stride;
-    int64_t n = p->nlev * p->ncol;
-    if (n) {
-        if (p->dtype == XP_F64) hipLaunchKernelGGL((xp::k_dewpoint_from_q<double>), dim3(blocks(n)), dim3(256), 0, st.s, pv, tv, qv, p->nlev, p->ncol, ov);
-        else hipLaunchKernelGGL((xp::k_dewpoint_from_q<float>), dim3(blocks(n)), dim3(256), 0, st.s, pv, tv, qv, p->nlev, p->ncol, ov);
-    }
+        (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
+    by_dtype(p->dtype, [&](auto z) { launch(xp::k_dewpoint_from_q<decltype(z)>, p->nlev * p->ncol, st, pv, tv, qv, p->nlev, p->ncol, out_like(od, p)); });
     return st.finish();
 }
 
 int xp_crossing_level(const xp_view *x, const xp_view *a, double value, void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(x, "x")) || (rc = check_view(a, "a")) || (rc = same_shape(x, a, "x/a"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{x, "x"}, {a, "a"}}))) return rc;
     if (!out) return fail(XP_E_ARG, "xp_crossing_level: null output");
-    Stager st(stream);
     xp::View xv, av;
     void *od;
-    if ((rc = stage_view(st, x, &xv)) || (rc = stage_view(st, a, &av)) ||
-        (rc = st.out(out, (size_t)x->ncol * esize(x->dtype), x->mem, &od))) return rc;
-    if (x->ncol) {
-        if (x->dtype == XP_F64) hipLaunchKernelGGL((xp::k_crossing_level<double>), dim3(blocks(x->ncol)), dim3(256), 0, st.s, xv, av, x->nlev, x->ncol, value, od);
-        else hipLaunchKernelGGL((xp::k_crossing_level<float>), dim3(blocks(x->ncol)), dim3(256), 0, st.s, xv, av, x->nlev, x->ncol, value, od);
-    }
+    if ((rc = stage_view(st, x, &xv)) || (rc = stage_view(st, a, &av)) || (rc = st.out(out, rows_bytes(x, 1), x->mem, &od))) return rc;
+    by_dtype(x->dtype, [&](auto z) { launch(xp::k_crossing_level<decltype(z)>, x->ncol, st, xv, av, x->nlev, x->ncol, value, od); });
     return st.finish();
 }
 
 int xp_mixing_ratio(const xp_view *t, const xp_view *td, const xp_view *p, void *out, void *stream) {
-    DevGuard dg_;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = check_view(t, "temperature")) || (rc = check_view(td, "dewpoint")) || (rc = check_view(p, "pressure")) ||
-        (rc = same_shape(t, td, "temperature/dewpoint")) || (rc = same_shape(t, p, "temperature/pressure"))) return rc;
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{t, "temperature"}, {td, "dewpoint"}, {p, "pressure"}}))) return rc;
     if (!out) return fail(XP_E_ARG, "xp_mixing_ratio: null output");
-    Stager st(stream);
-    xp::View tv, tdv, pv; xp::OutView ov;
+    xp::View tv, tdv, pv;
     void *od;
     if ((rc = stage_view(st, t, &tv)) || (rc = stage_view(st, td, &tdv)) || (rc = stage_view(st, p, &pv)) ||
-        (rc = st.out(out, (size_t)t->nlev * (size_t)t->ncol * esize(t->dtype), t->mem, &od))) return rc;
-    ov.data = od; ov.ls = t->lev_stride; ov.cs = t->col_stride;
-    int64_t n = t->nlev * t->ncol;
-    if (n) {
-        if (t->dtype == XP_F64) hipLaunchKernelGGL((xp::k_mixing_ratio<double>), dim3(blocks(n)), dim3(256), 0, st.s, tv, tdv, pv, t->nlev, t->ncol, ov);
-        else hipLaunchKernelGGL((xp::k_mixing_ratio<float>), dim3(blocks(n)), dim3(256), 0, st.s, tv, tdv, pv, t->nlev, t->ncol, ov);
-    }
+        (rc = st.out(out, rows_bytes(t, t->nlev), t->mem, &od))) return rc;
+    by_dtype(t->dtype, [&](auto z) { launch(xp::k_mixing_ratio<decltype(z)>, t->nlev * t->ncol, st, tv, tdv, pv, t->nlev, t->ncol, out_like(od, t)); });
     return st.finish();
 }
 
