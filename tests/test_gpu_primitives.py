@@ -274,6 +274,111 @@ def test_device_tensors_and_fp32(xa):
     assert s.is_cuda and s.shape == (p.shape[1],)
 
 
+def _wrapper_calls(xa, dtype):
+    """(name, function, arguments) of every array wrapper of numpy_api, on NumPy inputs of `dtype`."""
+    p, t, td = (v.astype(dtype) for v in _columns(nlev=24, ncol=60, seed=23, nan_fraction=0.05))
+    nlev, ncol = p.shape
+    rng = np.random.default_rng(5)
+    z = np.cumsum(np.full_like(p, 400.0), axis=0) + rng.uniform(0, 50, ncol).astype(dtype)
+    q = np.full_like(p, 0.006)
+    wh = (np.linspace(50.0, 9000.0, 10)[:, None] + rng.uniform(0, 40, (1, ncol))).astype(dtype)
+    wu, wv = (wh * 2.5e-3 + rng.normal(0, 3, wh.shape)).astype(dtype), (rng.normal(0, 3, wh.shape)).astype(dtype)
+    su, sv = rng.normal(2, 2, ncol).astype(dtype), rng.normal(0, 2, ncol).astype(dtype)
+    dat = {'pressure': p, 'temperature': t, 'specific_humidity': q, 'height_asl': z, 'wind_u': wu, 'wind_v': wv,
+           'wind_height_above_surface': wh, 'surface_wind_u': su, 'surface_wind_v': sv}
+    prof = xa.parcel_profile(p, p[0], t[0], td[0], moist='exact')
+    ce = xa.cape_cin_columns(p, t, td, want=('lfc_pressure', 'el_pressure'), moist='exact')
+    cp = xa.conv_properties(dat, moist='exact')
+    pn = np.where(np.arange(nlev)[:, None] < rng.integers(0, 4, ncol), np.nan, p).astype(dtype)
+    mask = rng.uniform(size=(nlev - 1, ncol)) < 0.7
+    at = np.linspace(1050.0, 150.0, 7).astype(dtype)[:, None] + np.zeros((1, ncol), dtype)
+    calls = [
+        ('cape_cin_columns', xa.cape_cin_columns, (p, t, td), dict(want_profile=True, lifted_index_at=500.0, moist='exact')),
+        ('cape_cin_columns explicit', xa.cape_cin_columns, (p, t, td),
+         dict(parcel='explicit', parcel_values=(p[1], t[1], td[1]), moist='exact')),
+        ('cape_cin_multi', xa.cape_cin_multi, (p, t, td, [('most_unstable', 300), ('mixed_layer', 100)]),
+         dict(lifted_index_at=500.0, moist='family')),
+        ('most_unstable_parcel', xa.most_unstable_parcel, (p, t, td), {}),
+        ('mixed_parcel', xa.mixed_parcel, (p, t, td), {}),
+        ('mixed_layer', xa.mixed_layer, ({'pressure': p, 'temperature': t, 'dewpoint': td},), {}),
+        ('lcl', xa.lcl, (p[0], t[0], td[0]), {}),
+        ('dry_lapse', xa.dry_lapse, (p, t[0]), {}),
+        ('moist_lapse', xa.moist_lapse, (p, t[0], p[0]), dict(moist='exact')),
+        ('parcel_profile', xa.parcel_profile, (p, p[0], t[0], td[0]), dict(moist='exact')),
+        ('lfc_el', xa.lfc_el, (p, prof['temperature'], t, prof['lcl_pressure'], prof['lcl_temperature']), {}),
+        ('cape_cin_base', xa.cape_cin_base, (p, t, ce['lfc_pressure'], ce['el_pressure'], prof['temperature']), {}),
+        ('wet_bulb_temperature', xa.wet_bulb_temperature, (p, t, td), dict(moist='exact')),
+        ('interp_level scalar', xa.interp_level, (p, t, 500.0), dict(log=True)),
+        ('interp_level per column', xa.interp_level, (p, t, p[3] * 0.9), {}),
+        ('interp_levels', xa.interp_levels, (p, [t, td, z], [850.0, 500.0]), dict(log=True)),
+        ('dewpoint_from_specific_humidity', xa.dewpoint_from_specific_humidity, (p, t, q), {}),
+        ('mixing_ratio', xa.mixing_ratio, (t, td, p), {}),
+        ('crossing_level', xa.crossing_level, (z, t, 273.15), {}),
+        ('insert_level', xa.insert_level, ({'pressure': p, 'temperature': t},
+                                           {'pressure': prof['lcl_pressure'], 'temperature': prof['lcl_temperature']}), {}),
+        ('find_intersections', xa.find_intersections, (p, t, td), dict(log_x=True)),
+        ('trapz', xa.trapz, (t - td - 8.0, p), dict(mask=mask)),
+        ('trap_around_zeros', xa.trap_around_zeros, (p, t - td - 8.0), {}),
+        ('bound_pressure', xa.bound_pressure, (p, 700.0), {}),
+        ('get_layer', xa.get_layer, ({'pressure': p, 'temperature': t},), dict(depth=100)),
+        ('shift_out_nans', xa.shift_out_nans, ({'pressure': pn, 'temperature': t}, 'pressure'), {}),
+        ('from_most_unstable_parcel', xa.from_most_unstable_parcel, (p, t, td), {}),
+        ('mix_layer', xa.mix_layer, (p, t, td), {}),
+        ('interp1d', xa.interp1d, (at, np.ascontiguousarray(p[::-1]), np.ascontiguousarray(t[::-1])), {}),
+        ('wind_shear', xa.wind_shear, (su, sv, wu, wv, wh), {}),
+        ('significant_hail_parameter', xa.significant_hail_parameter,
+         tuple(cp[k] for k in ('mu_cape', 'mu_mixing_ratio', 'lapse_rate_700_500', 'temp_500', 'shear_magnitude',
+                               'freezing_level')), {}),
+        ('conv_properties', xa.conv_properties, (dat,), dict(moist='exact')),
+        ('conv_properties_composed', xa.conv_properties_composed, (dat,), dict(moist='exact')),
+        ('min_conv_properties', xa.min_conv_properties, (dat,), dict(moist='exact')),
+        ('storm_proxies', xa.storm_proxies, (cp,), {}),
+    ]
+    # lcl() takes NumPy input as float64 and the composed bundles upload it as float64: only float64 tensors match that
+    return calls if dtype == np.float64 else [c for c in calls if c[0] not in ('lcl', 'conv_properties_composed',
+                                                                                 'min_conv_properties')]
+
+
+def _leaves(r):
+    if isinstance(r, dict):
+        return [x for k in r for x in _leaves(r[k])]
+    if isinstance(r, (list, tuple)):
+        return [x for v in r for x in _leaves(v)]
+    return [r]
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_every_wrapper_on_device_tensors_and_cpu_tensors(xa, dtype):
+    """Each array wrapper once on NumPy arrays, once on CUDA tensors and once on CPU tensors: bit-identical results, of
+    the same dtype and shape, on the device for CUDA inputs and on the host (NumPy) for the other two."""
+    import torch
+
+    def conv(x, to):
+        if isinstance(x, dict):
+            return {k: conv(v, to) for k, v in x.items()}
+        if isinstance(x, (list, tuple)):
+            return type(x)(conv(v, to) for v in x)
+        return torch.as_tensor(x).to(to) if isinstance(x, np.ndarray) else x
+
+    for name, fn, args, kw in _wrapper_calls(xa, dtype):
+        host = _leaves(fn(*args, **kw))
+        for to in ('cuda', 'cpu'):
+            got = _leaves(fn(*conv(args, to), **kw))
+            assert len(got) == len(host), (name, to)
+            for i, (g, h) in enumerate(zip(got, host)):
+                assert isinstance(h, np.ndarray), (name, i, type(h))
+                if name in ('from_most_unstable_parcel', 'mix_layer') and i == len(host) - 1:
+                    assert isinstance(g, np.ndarray) and g.dtype == bool         # the kept-level mask is host memory
+                elif to == 'cuda':
+                    assert torch.is_tensor(g) and g.is_cuda, (name, i)
+                    assert g.dtype == torch.from_numpy(h).dtype, (name, i, g.dtype, h.dtype)
+                    g = g.cpu().numpy()
+                else:
+                    assert isinstance(g, np.ndarray), (name, i, type(g))
+                assert g.dtype == h.dtype and g.shape == h.shape, (name, to, i, g.dtype, h.dtype, g.shape, h.shape)
+                assert np.array_equal(g, h, equal_nan=g.dtype.kind == 'f'), (name, to, i)
+
+
 # -- the xarray-facing mirror (reference signatures, Dataset / DataArray in and out) ---------------------------------------
 def _da(values, dims, name=None, **coords):
     from xarray_parcel_amd._xr import DataArray

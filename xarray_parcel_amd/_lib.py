@@ -101,6 +101,53 @@ class Tables(C.Structure):
                 ('index', C.c_void_p), ('adiabats', C.c_void_p)]
 
 
+_i32, _i64, _f64, _ptr = C.c_int32, C.c_int64, C.c_double, C.c_void_p
+_V, _P, _O, _S, _PO = (C.POINTER(s) for s in (View, Parcel, Opts, ScalarsOut, ProfileOut))
+
+# argtypes of every entry point, in the order of include/xparcel.h.  Data pointers (void *, double *, int32_t * outputs,
+# uint8_t * masks) are _ptr: it takes an address, None, or any ctypes pointer, array or byref(); a struct pointer takes the
+# struct itself (passed by reference), byref() or an array of structs.  Every entry point returns int except xp_last_error.
+# The trailing _ptr of the compute entry points is the hipStream_t.
+ARGTYPES = {
+    'xp_version': (),
+    'xp_init': (_i32,),
+    'xp_set_tables': (C.POINTER(Tables),),
+    'xp_tables_loaded': (),
+    'xp_family_table': (_ptr, C.POINTER(_i64), C.POINTER(_i64)),
+    'xp_set_family_table': (_ptr, _i64, _i64),
+    'xp_cape_cin': (_V, _V, _V, _P, _O, _S, _PO, _ptr),
+    'xp_cape_cin_multi': (_V, _V, _V, _i32, _P, _O, _S, _PO, _ptr),
+    'xp_lcl': (_i64, _i32, _i32) + (_ptr,) * 8,
+    'xp_dry_lapse': (_V, _ptr, _ptr, _ptr, _ptr),
+    'xp_moist_lapse': (_V, _ptr, _ptr, _i32, _ptr, _ptr),
+    'xp_parcel_profile': (_V, _ptr, _ptr, _ptr, _i32) + (_ptr,) * 6,
+    'xp_lfc_el': (_V, _V, _V, _ptr, _ptr, _S, _ptr),
+    'xp_cape_cin_base': (_V, _V, _V, _ptr, _ptr, _O, _ptr, _ptr, _ptr),
+    'xp_select_parcel': (_V, _V, _V, _P, _S, _ptr),
+    'xp_mixed_layer': (_V, _V, _f64, _ptr, _ptr),
+    'xp_wet_bulb_temperature': (_V, _V, _V, _i32, _ptr, _ptr),
+    'xp_interp_level': (_V, _V, _ptr, _i32, _i32, _ptr, _ptr),
+    'xp_interp_levels': (_V, _i32, C.POINTER(_V), _i32, _ptr, _i32, C.POINTER(_ptr), _ptr),
+    'xp_dewpoint_from_specific_humidity': (_V, _V, _V, _ptr, _ptr),
+    'xp_crossing_level': (_V, _V, _f64, _ptr, _ptr),
+    'xp_mixing_ratio': (_V, _V, _V, _ptr, _ptr),
+    'xp_conv_properties': (C.POINTER(ConvIn), _O, _i32, C.POINTER(ConvOut), _ptr),
+    'xp_insert_level': (_V, _V, _ptr, _ptr, _f64, _ptr, _ptr),
+    'xp_find_intersections': (_V, _V, _V, _i32, C.POINTER(_ptr), _ptr),
+    'xp_trapz': (_V, _V, _ptr, _i32, _i32, _ptr, _ptr),
+    'xp_trap_around_zeros': (_V, _V, _i32, C.POINTER(_ptr), _ptr, _ptr),
+    'xp_bound_pressure': (_V, _ptr, _ptr, _ptr),
+    'xp_get_layer': (_V, _V, _f64, _i32, _i32, _ptr, _ptr),
+    'xp_shift_out_nans': (_V, _V, _ptr, _ptr),
+    'xp_rebase_profile': (_V, _V, _V, _P, _ptr, _ptr, _ptr, _S, _ptr, C.POINTER(_i64), _ptr),
+    'xp_interp1d': (_V, _V, _V, _ptr, _ptr),
+    'xp_wind_shear': (_V, _V, _V, _ptr, _ptr, _f64) + (_ptr,) * 5,
+    'xp_significant_hail_parameter': (_i64, _i32, _i32) + (_ptr,) * 8,
+    'xp_storm_proxies': (_i64, _i32, _i32, C.POINTER(ProxiesIn), C.POINTER(ProxiesOut), _ptr),
+    'xp_last_error': (),
+}
+
+
 class XParcelError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libxparcel error {code}: {msg}')
@@ -202,10 +249,11 @@ def load():
                 import torch  # noqa: F401
             except Exception:
                 pass
-            _lib = C.CDLL(LIB_PATH)
-            _lib.xp_last_error.restype = C.c_char_p
+            lib = C.CDLL(LIB_PATH)
             for s in SYMBOLS:
-                getattr(_lib, s)
+                f = getattr(lib, s)
+                f.argtypes, f.restype = ARGTYPES[s], C.c_char_p if s == 'xp_last_error' else C.c_int
+            _lib = lib
     return _lib
 
 

@@ -2,8 +2,8 @@
 Array-level host API over libxparcel: the reference's function names
 (modules/parcel_functions.py, "pf.py") on plain arrays.
 
-Inputs are NumPy arrays (host memory, staged through the library) or torch CUDA
-tensors (used in place, on torch's current stream), laid out (nlev, ...) with the
+Inputs are NumPy arrays or torch CPU tensors (host memory, staged through the library)
+or torch CUDA tensors (used in place, on torch's current stream), laid out (nlev, ...) with the
 vertical first: (nlev,), (nlev, ncol) or (nlev, ny, nx).  Per-column results come
 back with the horizontal shape of the input; profiles as (nlev+1, ...).  Returned
 containers are plain dicts -- the xarray-facing mirrors in parcel_functions.py
@@ -12,6 +12,7 @@ wrap them into Datasets.
 There is no CPU path here: every function ends in a kernel launch.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -21,6 +22,7 @@ L_EPS = 0.6219569100577033        # Mw / Md (metpy.constants, 1.4.1)
 
 try:  # torch is plumbing (device memory, streams); the API also works without it on host arrays
     import torch
+    _TORCH_DTYPE = {np.float64: torch.float64, np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
 except Exception:  # pragma: no cover
     torch = None
 
@@ -29,113 +31,100 @@ def _is_torch(x):
     return torch is not None and isinstance(x, torch.Tensor)
 
 
-import threading as _threading
-
-_CTX = _threading.local()      # .device: the torch device of the call being assembled on this thread (None: host arrays)
-
-
-def _ctx_device():
-    return getattr(_CTX, 'device', None)
+def _ptr(a):
+    return a.data_ptr() if _is_torch(a) else a.ctypes.data
 
 
-class _Arr:
-    """Uniform handle on a NumPy array or torch CUDA tensor, flattened to (nlev, ncol)."""
+class _Call:
+    """One library call being assembled from its array inputs, which decide, once:
+    - dtype: float64 if any torch input is float64 or any other input is not float32, float32 otherwise;
+    - memory space: the device if and only if some input is a CUDA tensor -- NumPy arrays, scalars and CPU tensors are then
+      uploaded to that tensor's device; otherwise every input, CPU tensors included, is staged as host memory.  Outputs
+      live in the same space;
+    - device and stream: the library runs on that device, on torch's current stream of that device (not of torch's
+      current device); host calls use the NULL stream.
+    `ins` holds the inputs in that dtype and space.  Every array the call stages is kept alive as long as the call."""
 
-    def __init__(self, x, dtype=None, like=None):
-        if _is_torch(x):
-            if not x.is_cuda:
-                x = x.to(_ctx_device() or 'cuda')
-            if dtype is not None:
-                x = x.to(dtype=torch.float64 if dtype == np.float64 else torch.float32)
-            elif x.dtype not in (torch.float32, torch.float64):
-                x = x.to(torch.float64)
-            self.t = x.contiguous()
-            self.dev = True
-            self.np_dtype = np.float64 if self.t.dtype == torch.float64 else np.float32
-            self.shape = tuple(self.t.shape)
-            self.ptr = self.t.data_ptr()
+    def __init__(self, *xs):
+        devs = [x.device for x in xs if _is_torch(x) and x.is_cuda]
+        assert all(d == devs[0] for d in devs), 'all device tensors of one call must live on the same GPU'
+        self.device = devs[0] if devs else None
+        f64 = any(x.dtype == torch.float64 if _is_torch(x) else np.asarray(x).dtype != np.float32 for x in xs)
+        self.dtype = np.float64 if f64 else np.float32
+        self.xp_dtype = L.XP_F64 if f64 else L.XP_F32
+        self.mem = L.XP_MEM_HOST if self.device is None else L.XP_MEM_DEVICE
+        self._keep = []
+        self.ins = [self.array(x) for x in xs]
+        # the grid: the first input, (nlev, ...) with `hshape` the horizontal shape of its ncol columns
+        shape = tuple(self.ins[0].shape)
+        self.nlev, self.hshape = (shape[0], shape[1:]) if shape else (1, ())
+        self.ncol = int(np.prod(self.hshape))
+
+    def array(self, x, dtype=None):
+        """x as a contiguous array of `dtype` (default: the call's) in the call's memory space."""
+        dtype = dtype or self.dtype
+        if self.device is None:
+            a = x.detach().to('cpu', _TORCH_DTYPE[dtype]).numpy() if _is_torch(x) else x
+            a = np.ascontiguousarray(np.asarray(a, dtype=dtype))
         else:
-            a = np.asarray(x)
-            if dtype is not None:
-                a = a.astype(dtype, copy=False)
-            elif a.dtype not in (np.float32, np.float64):
-                a = a.astype(np.float64)
-            self.a = np.ascontiguousarray(a)
-            self.dev = False
-            self.np_dtype = self.a.dtype.type
-            self.shape = self.a.shape
-            self.ptr = self.a.ctypes.data
+            a = x if _is_torch(x) else torch.as_tensor(np.asarray(x, dtype=dtype))
+            a = a.to(self.device, _TORCH_DTYPE[dtype]).contiguous()
+        self._keep.append(a)
+        return a
 
-    @property
-    def xp_dtype(self):
-        return L.XP_F64 if self.np_dtype == np.float64 else L.XP_F32
+    def per_col(self, x):
+        """Per-column argument (a scalar, broadcast, or one value per column of the grid) -> ncol elements."""
+        if not _is_torch(x):
+            x = np.asarray(x, dtype=self.dtype).reshape(-1)
+            if x.size == 1 and self.ncol != 1:
+                x = np.full(self.ncol, x[0], dtype=self.dtype)
+        a = self.array(x).reshape(-1)
+        assert int(np.prod(a.shape)) == self.ncol, 'per-column argument does not match the grid'
+        return a
 
-    @property
-    def mem(self):
-        return L.XP_MEM_DEVICE if self.dev else L.XP_MEM_HOST
+    def mask(self, m, shape):
+        """bool / integer mask -> dense uint8 of `shape`."""
+        return self.array(((m != 0) if _is_torch(m) else (np.asarray(m) != 0)).reshape(shape), np.uint8)
 
+    def view(self, a, nlev=None, ncol=None):
+        """xp_view of a staged array, (nlev, ...) as (nlev, ncol) unless given."""
+        nlev = a.shape[0] if nlev is None else nlev
+        ncol = int(np.prod(a.shape[1:])) if ncol is None else ncol
+        return L.View(_ptr(a), self.xp_dtype, self.mem, nlev, ncol, ncol, 1)
 
-def _stream(dev):
-    """torch's current stream on the device the call's tensors live on (not on torch's current device)."""
-    if dev and torch is not None:
-        return C.c_void_p(torch.cuda.current_stream(_ctx_device()).cuda_stream)
-    return C.c_void_p(0)
+    def out(self, shape, dtype=None):
+        dtype = dtype or self.dtype
+        if self.device is None:
+            return np.empty(shape, dtype=dtype)
+        return torch.empty(shape, dtype=_TORCH_DTYPE[dtype], device=self.device)
 
+    def scalars(self, names, shape):
+        """xp_scalars_out with an output of `shape` for each of `names` (int32 for indices and status)."""
+        so = L.ScalarsOut(dtype=self.xp_dtype, mem=self.mem)
+        out = {k: self.out(shape, np.int32 if k in L.SCALAR_I else None) for k in names}
+        for k, a in out.items():
+            setattr(so, k, _ptr(a))
+        return so, out
 
-def _device_of(h):
-    if h.dev:
-        return h.t.device.index
-    return None
+    def profile(self, names, nlev_out, shape, lifted_index_at=None):
+        """xp_profile_out with an (nlev_out,) + shape output for each of `names` and, with lifted_index_at, the lifted index
+        (one per column, under 'lifted_index')."""
+        ncol = int(np.prod(shape))
+        po = L.ProfileOut(dtype=self.xp_dtype, mem=self.mem, nlev_out=nlev_out, lev_stride=ncol, col_stride=1)
+        out = {k: self.out((nlev_out,) + shape) for k in names}
+        for k, a in out.items():
+            setattr(po, k, _ptr(a))
+        if lifted_index_at is not None:
+            out['lifted_index'] = self.out(shape)
+            po.lifted_index, po.lifted_index_pressure = _ptr(out['lifted_index']), float(lifted_index_at)
+        return po, out
 
-
-def _common(*xs):
-    """Bring inputs to one dtype / one memory space; return handles + (nlev, ncol, hshape)."""
-    devs = [x.device for x in xs if _is_torch(x) and x.is_cuda]
-    any_dev = bool(devs)
-    assert all(d == devs[0] for d in devs), 'all device tensors of one call must live on the same GPU'
-    _CTX.device = devs[0] if any_dev else None
-    f64 = any((_is_torch(x) and x.dtype == torch.float64) or
-              (not _is_torch(x) and np.asarray(x).dtype != np.float32) for x in xs)
-    dt = np.float64 if f64 else np.float32
-    hs = []
-    for x in xs:
-        if any_dev and not _is_torch(x):
-            x = torch.as_tensor(np.asarray(x, dtype=dt)).to(devs[0])
-        hs.append(_Arr(x, dtype=dt))
-    return hs, dt, any_dev
-
-
-def _view(h, nlev, ncol):
-    return L.View(h.ptr, h.xp_dtype, h.mem, nlev, ncol, ncol, 1)
-
-
-def _alloc(shape, np_dtype, dev, like=None):
-    if dev:
-        td = {np.float64: torch.float64, np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}[np_dtype]
-        t = torch.empty(shape, dtype=td, device=like.t.device if like is not None else 'cuda')
-        return t, t.data_ptr()
-    a = np.empty(shape, dtype=np_dtype)
-    return a, a.ctypes.data
-
-
-def _vert_shape(h):
-    nlev = h.shape[0]
-    hshape = tuple(h.shape[1:])
-    ncol = int(np.prod(hshape)) if hshape else 1
-    return nlev, ncol, hshape
-
-
-def _per_col(x, ncol, dt, dev, like):
-    """Per-column input (scalar or array of hshape) -> handle of ncol elements."""
-    if _is_torch(x):
-        h = _Arr((x.to(like.t.device) if dev else x).reshape(-1), dtype=dt)
-    else:
-        a = np.asarray(x, dtype=dt).reshape(-1)
-        if a.size == 1 and ncol != 1:
-            a = np.full(ncol, a[0], dtype=dt)
-        h = _Arr(torch.as_tensor(a).to(like.t.device) if dev else a, dtype=dt)
-    assert int(np.prod(h.shape)) == ncol, 'per-column argument does not match the grid'
-    return h
+    def run(self, name, *args):
+        """Launch entry point `name` on the call's device and stream; arrays are passed as their addresses."""
+        lib = L.init(None if self.device is None else self.device.index)
+        stream = None if self.device is None else torch.cuda.current_stream(self.device).cuda_stream
+        args = [_ptr(a) if isinstance(a, np.ndarray) or _is_torch(a) else a for a in args]
+        L.check(getattr(lib, name)(*args, stream))
 
 
 def _opts(virtual_temperature_correction=True, lcl_interp='log', pos_cape_neg_cin=True, post_zero_cin=False,
@@ -166,49 +155,26 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     with the scalars, computed in the same pass -- no profile array has to exist for it.
     humidity='specific' (keyword): `dewpoint` holds specific humidity [kg/kg] and is converted on load
     (parcel_test.py:262-266 fused into the pass)."""
-    (p, t, td), dt, dev = _common(pressure, temperature, dewpoint)
+    c = _Call(pressure, temperature, dewpoint)
+    p, t, td = c.ins
     assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
     o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
     if depth is None:
         depth = 300.0 if parcel == 'most_unstable' else 100.0                # pf.py:1558, 1652
     pc = L.Parcel(L.PARCEL[parcel], 0, float(depth), None, None, None)
-    keep = []
     if parcel == 'explicit':
-        hs = [_per_col(x, ncol, dt, dev, p) for x in parcel_values]
-        keep += hs
-        pc.pressure, pc.temperature, pc.dewpoint = hs[0].ptr, hs[1].ptr, hs[2].ptr
-    names = L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want)
-    so = L.ScalarsOut()
-    so.dtype = p.xp_dtype
-    so.mem = p.mem
-    out = {}
-    for k in names:
-        arr, ptr = _alloc((ncol,), np.int32 if k in L.SCALAR_I else dt, dev, p)
-        setattr(so, k, ptr)
-        out[k] = arr
+        pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in parcel_values)
+    so, res = c.scalars(L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want), c.hshape)
     po = None
     if want_profile or lifted_index_at is not None:
-        po = L.ProfileOut()
-        po.dtype, po.mem, po.nlev_out, po.lev_stride, po.col_stride = p.xp_dtype, p.mem, nlev + 1, ncol, 1
-        prof = {}
-        if lifted_index_at is not None:
-            arr, ptr = _alloc((ncol,), dt, dev, p)
-            po.lifted_index, po.lifted_index_pressure = ptr, float(lifted_index_at)
-            out['lifted_index'] = arr
         pvars = L.PROFILE_VARS if want_profile is True else tuple(want_profile or ())
         assert all(k in L.PROFILE_VARS for k in pvars), f'profile variables are {L.PROFILE_VARS}'
-        for k in pvars:
-            arr, ptr = _alloc((nlev + 1, ncol), dt, dev, p)
-            setattr(po, k, ptr)
-            prof[k] = arr
-    L.check(lib.xp_cape_cin(C.byref(_view(p, nlev, ncol)), C.byref(_view(t, nlev, ncol)),
-                            C.byref(_view(td, nlev, ncol)), C.byref(pc), C.byref(o), C.byref(so),
-                            C.byref(po) if po is not None else None, _stream(dev)))
-    res = {k: v.reshape(hshape) for k, v in out.items()}
+        po, prof = c.profile(pvars, c.nlev + 1, c.hshape, lifted_index_at)
+        if lifted_index_at is not None:
+            res['lifted_index'] = prof.pop('lifted_index')
+    c.run('xp_cape_cin', c.view(p), c.view(t), c.view(td), pc, o, so, po)
     if want_profile:
-        res['profile'] = {k: v.reshape((nlev + 1,) + hshape) for k, v in prof.items()}
+        res['profile'] = prof
     return res
 
 
@@ -219,10 +185,9 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
     (pf.py:1984-2006).  Returns one dict per parcel, bit-identical to what cape_cin_columns() returns for it.
     fused=True (XP_OPT_FUSE_PARCELS; moist='family', two parcels): one pass over the grid for both -- same numbers,
     measured slower than a pass per parcel on MI355X, hence opt-in."""
-    (p, t, td), dt, dev = _common(pressure, temperature, dewpoint)
+    c = _Call(pressure, temperature, dewpoint)
+    p, t, td = c.ins
     assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
     o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
     o.flags = L.OPT_FUSE_PARCELS if fused else 0
     specs = []
@@ -234,26 +199,18 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
         specs.append((name, float(depth)))
     n = len(specs)
     pcs = (L.Parcel * n)(*[L.Parcel(L.PARCEL[nm], 0, dp, None, None, None) for nm, dp in specs])
+    names = L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want)
     sos = (L.ScalarsOut * n)()
     pos = (L.ProfileOut * n)() if lifted_index_at is not None else None
-    names = L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want)
     outs = []
     for i in range(n):
-        sos[i].dtype, sos[i].mem = p.xp_dtype, p.mem
-        out = {}
-        for k in names:
-            arr, ptr = _alloc((ncol,), np.int32 if k in L.SCALAR_I else dt, dev, p)
-            setattr(sos[i], k, ptr)
-            out[k] = arr
+        sos[i], out = c.scalars(names, c.hshape)
         if pos is not None:
-            pos[i].dtype, pos[i].mem, pos[i].nlev_out, pos[i].lev_stride, pos[i].col_stride = p.xp_dtype, p.mem, nlev + 1, ncol, 1
-            arr, ptr = _alloc((ncol,), dt, dev, p)
-            pos[i].lifted_index, pos[i].lifted_index_pressure = ptr, float(lifted_index_at)
-            out['lifted_index'] = arr
+            pos[i], li = c.profile((), c.nlev + 1, c.hshape, lifted_index_at)
+            out.update(li)
         outs.append(out)
-    L.check(lib.xp_cape_cin_multi(C.byref(_view(p, nlev, ncol)), C.byref(_view(t, nlev, ncol)), C.byref(_view(td, nlev, ncol)),
-                                  C.c_int32(n), pcs, C.byref(o), sos, pos, _stream(dev)))
-    return [{k: v.reshape(hshape) for k, v in out.items()} for out in outs]
+    c.run('xp_cape_cin_multi', c.view(p), c.view(t), c.view(td), n, pcs, o, sos, pos)
+    return outs
 
 
 # ---- reference-named functions (one column or a grid) -----------------------------------------
@@ -310,21 +267,11 @@ def parcel_profile_with_lcl(pressure, temperature, dewpoint, parcel_pressure, pa
 
 
 def _select(pressure, temperature, dewpoint, mode, depth):
-    (p, t, td), dt, dev = _common(pressure, temperature, dewpoint)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    pc = L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None)
-    so = L.ScalarsOut()
-    so.dtype, so.mem = p.xp_dtype, p.mem
-    out = {}
-    for k in L.SCALAR_P + ('parcel_index',):
-        arr, ptr = _alloc((ncol,), np.int32 if k == 'parcel_index' else dt, dev, p)
-        setattr(so, k, ptr)
-        out[k] = arr
-    L.check(lib.xp_select_parcel(C.byref(_view(p, nlev, ncol)), C.byref(_view(t, nlev, ncol)),
-                                 C.byref(_view(td, nlev, ncol)), C.byref(pc), C.byref(so), _stream(dev)))
-    return {'pressure': out['parcel_pressure'].reshape(hshape), 'temperature': out['parcel_temperature'].reshape(hshape),
-            'dewpoint': out['parcel_dewpoint'].reshape(hshape), 'index': out['parcel_index'].reshape(hshape)}
+    c = _Call(pressure, temperature, dewpoint)
+    so, out = c.scalars(L.SCALAR_P + ('parcel_index',), c.hshape)
+    c.run('xp_select_parcel', *map(c.view, c.ins), L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None), so)
+    return {'pressure': out['parcel_pressure'], 'temperature': out['parcel_temperature'],
+            'dewpoint': out['parcel_dewpoint'], 'index': out['parcel_index']}
 
 
 def most_unstable_parcel(pressure, temperature, dewpoint, depth=300):
@@ -345,45 +292,29 @@ def mixed_layer(dat, depth=100):
     for k, v in dat.items():
         if k == 'pressure':
             continue
-        (p, x), dt, dev = _common(dat['pressure'], v)
-        nlev, ncol, hshape = _vert_shape(p)
-        lib = L.init(_device_of(p))
-        arr, ptr = _alloc((ncol,), dt, dev, p)
-        L.check(lib.xp_mixed_layer(C.byref(_view(p, nlev, ncol)), C.byref(_view(x, nlev, ncol)), C.c_double(depth),
-                                   C.c_void_p(ptr), _stream(dev)))
-        out[k] = arr.reshape(hshape)
+        c = _Call(dat['pressure'], v)
+        out[k] = c.out(c.hshape)
+        c.run('xp_mixed_layer', *map(c.view, c.ins), float(depth), out[k])
     return out
 
 
 def lcl(parcel_pressure, parcel_temperature, parcel_dewpoint):
     """pf.py:609."""
-    (p, t, td), dt, dev = _common(*(x if _is_torch(x) else np.atleast_1d(np.asarray(x, dtype=np.float64))
-                                    for x in (parcel_pressure, parcel_temperature, parcel_dewpoint)))
-    n = int(np.prod(p.shape))
+    c = _Call(*(x if _is_torch(x) else np.atleast_1d(np.asarray(x, dtype=np.float64))
+                for x in (parcel_pressure, parcel_temperature, parcel_dewpoint)))
+    p, t, td = c.ins
     shape = tuple(p.shape) if np.ndim(parcel_pressure) else ()
-    lib = L.init(_device_of(p))
-    outs = [_alloc((n,), dt, dev, p) for _ in range(3)]
-    st, stp = _alloc((n,), np.int32, dev, p)
-    L.check(lib.xp_lcl(C.c_int64(n), p.xp_dtype, p.mem, C.c_void_p(p.ptr), C.c_void_p(t.ptr), C.c_void_p(td.ptr),
-                       C.c_void_p(outs[0][1]), C.c_void_p(outs[1][1]), C.c_void_p(outs[2][1]), C.c_void_p(stp),
-                       _stream(dev)))
-    return {'lcl_pressure': outs[0][0].reshape(shape), 'lcl_temperature': outs[1][0].reshape(shape),
-            'lcl_virtual_temperature': outs[2][0].reshape(shape)}
+    outs = [c.out(shape) for _ in range(3)]
+    c.run('xp_lcl', int(np.prod(p.shape)), c.xp_dtype, c.mem, p, t, td, *outs, c.out(shape, np.int32))
+    return {'lcl_pressure': outs[0], 'lcl_temperature': outs[1], 'lcl_virtual_temperature': outs[2]}
 
 
 def _lapse(fn_name, pressure, parcel_temperature, parcel_pressure, moist_mode=None):
-    (p,), dt, dev = _common(pressure)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    pt = _per_col(parcel_temperature, ncol, dt, dev, p)
-    pp = _per_col(parcel_pressure, ncol, dt, dev, p) if parcel_pressure is not None else None
-    out, optr = _alloc((nlev, ncol), dt, dev, p)
-    args = [C.byref(_view(p, nlev, ncol)), C.c_void_p(pt.ptr), C.c_void_p(pp.ptr) if pp is not None else None]
-    if moist_mode is not None:
-        args.append(C.c_int32(moist_mode))
-    args += [C.c_void_p(optr), _stream(dev)]
-    L.check(getattr(lib, fn_name)(*args))
-    return out.reshape((nlev,) + hshape)
+    c = _Call(pressure)
+    pp = c.per_col(parcel_pressure) if parcel_pressure is not None else None
+    out = c.out(c.ins[0].shape)
+    c.run(fn_name, c.view(c.ins[0]), c.per_col(parcel_temperature), pp, *(() if moist_mode is None else (moist_mode,)), out)
+    return out
 
 
 def dry_lapse(pressure, parcel_temperature, parcel_pressure=None):
@@ -399,127 +330,86 @@ def moist_lapse(pressure, parcel_temperature, parcel_pressure=None, moist=None):
 
 def parcel_profile(pressure, parcel_pressure, parcel_temperature, parcel_dewpoint, moist=None):
     """pf.py:712."""
-    (p,), dt, dev = _common(pressure)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    pp, pt, ptd = (_per_col(x, ncol, dt, dev, p) for x in (parcel_pressure, parcel_temperature, parcel_dewpoint))
-    t_out, tptr = _alloc((nlev, ncol), dt, dev, p)
-    tv_out, tvptr = _alloc((nlev, ncol), dt, dev, p)
-    ls = [_alloc((ncol,), dt, dev, p) for _ in range(3)]
-    L.check(lib.xp_parcel_profile(C.byref(_view(p, nlev, ncol)), C.c_void_p(pp.ptr), C.c_void_p(pt.ptr),
-                                  C.c_void_p(ptd.ptr), C.c_int32(L.MOIST[moist or _DEFAULT['moist']]),
-                                  C.c_void_p(tptr), C.c_void_p(tvptr), C.c_void_p(ls[0][1]), C.c_void_p(ls[1][1]),
-                                  C.c_void_p(ls[2][1]), _stream(dev)))
-    pres = p.t if dev else p.a
-    return {'pressure': pres, 'temperature': t_out.reshape((nlev,) + hshape),
-            'virtual_temperature': tv_out.reshape((nlev,) + hshape), 'lcl_pressure': ls[0][0].reshape(hshape),
-            'lcl_temperature': ls[1][0].reshape(hshape), 'lcl_virtual_temperature': ls[2][0].reshape(hshape)}
+    c = _Call(pressure)
+    p = c.ins[0]
+    pp, pt, ptd = (c.per_col(x) for x in (parcel_pressure, parcel_temperature, parcel_dewpoint))
+    res = {'pressure': p, 'temperature': c.out(p.shape), 'virtual_temperature': c.out(p.shape),
+           'lcl_pressure': c.out(c.hshape), 'lcl_temperature': c.out(c.hshape), 'lcl_virtual_temperature': c.out(c.hshape)}
+    c.run('xp_parcel_profile', c.view(p), pp, pt, ptd, L.MOIST[moist or _DEFAULT['moist']], *list(res.values())[1:])
+    return res
 
 
 def lfc_el(pressure, parcel_temperature, temperature, lcl_pressure, lcl_temperature):
     """pf.py:1066."""
-    (p, par, env), dt, dev = _common(pressure, parcel_temperature, temperature)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    lp, lt = (_per_col(x, ncol, dt, dev, p) for x in (lcl_pressure, lcl_temperature))
-    so = L.ScalarsOut()
-    so.dtype, so.mem = p.xp_dtype, p.mem
-    out = {}
-    for k in ('lfc_pressure', 'lfc_temperature', 'el_pressure', 'el_temperature', 'lfc_index', 'el_index', 'status'):
-        arr, ptr = _alloc((ncol,), np.int32 if k in L.SCALAR_I else dt, dev, p)
-        setattr(so, k, ptr)
-        out[k] = arr.reshape(hshape)
-    L.check(lib.xp_lfc_el(C.byref(_view(p, nlev, ncol)), C.byref(_view(par, nlev, ncol)),
-                          C.byref(_view(env, nlev, ncol)), C.c_void_p(lp.ptr), C.c_void_p(lt.ptr), C.byref(so),
-                          _stream(dev)))
+    c = _Call(pressure, parcel_temperature, temperature)
+    so, out = c.scalars(('lfc_pressure', 'lfc_temperature', 'el_pressure', 'el_temperature', 'lfc_index', 'el_index',
+                         'status'), c.hshape)
+    c.run('xp_lfc_el', *map(c.view, c.ins), c.per_col(lcl_pressure), c.per_col(lcl_temperature), so)
     return out
 
 
 def cape_cin_base(pressure, temperature, lfc_pressure, el_pressure, parcel_temperature, pos_cape_neg_cin=True,
                   post_zero_cin=False, **_ignored):
     """pf.py:1291."""
-    (p, env, par), dt, dev = _common(pressure, temperature, parcel_temperature)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    lf, el = (_per_col(x, ncol, dt, dev, p) for x in (lfc_pressure, el_pressure))
+    c = _Call(pressure, temperature, parcel_temperature)
     o = _opts(pos_cape_neg_cin=pos_cape_neg_cin, post_zero_cin=post_zero_cin)
-    cape, cptr = _alloc((ncol,), dt, dev, p)
-    cin, nptr = _alloc((ncol,), dt, dev, p)
-    L.check(lib.xp_cape_cin_base(C.byref(_view(p, nlev, ncol)), C.byref(_view(env, nlev, ncol)),
-                                 C.byref(_view(par, nlev, ncol)), C.c_void_p(lf.ptr), C.c_void_p(el.ptr), C.byref(o),
-                                 C.c_void_p(cptr), C.c_void_p(nptr), _stream(dev)))
-    return {'cape': cape.reshape(hshape), 'cin': cin.reshape(hshape)}
+    res = {'cape': c.out(c.hshape), 'cin': c.out(c.hshape)}
+    c.run('xp_cape_cin_base', *map(c.view, c.ins), c.per_col(lfc_pressure), c.per_col(el_pressure), o, res['cape'], res['cin'])
+    return res
 
 
 # ---- SURVEY 8(f) items that reuse the hot-path device code -------------------------------------------------
 def wet_bulb_temperature(pressure, temperature, dewpoint, moist=None):
     """pf.py:389: Normand's rule, every element independently."""
-    (p, t, td), dt, dev = _common(pressure, temperature, dewpoint)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    out, optr = _alloc((nlev, ncol), dt, dev, p)
-    L.check(lib.xp_wet_bulb_temperature(C.byref(_view(p, nlev, ncol)), C.byref(_view(t, nlev, ncol)),
-                                        C.byref(_view(td, nlev, ncol)), C.c_int32(L.MOIST[moist or _DEFAULT['moist']]),
-                                        C.c_void_p(optr), _stream(dev)))
-    return out.reshape((nlev,) + hshape)
+    c = _Call(pressure, temperature, dewpoint)
+    out = c.out(c.ins[0].shape)
+    c.run('xp_wet_bulb_temperature', *map(c.view, c.ins), L.MOIST[moist or _DEFAULT['moist']], out)
+    return out
 
 
 def interp_level(coords, variable, at, log=False):
     """pf.py:1758 linear_interp (log=False) / pf.py:1813 log_interp (log=True) of one variable."""
-    (cds, x), dt, dev = _common(coords, variable)
-    nlev, ncol, hshape = _vert_shape(cds)
-    lib = L.init(_device_of(cds))
+    c = _Call(coords, variable)
     scalar = np.ndim(at) == 0 and not _is_torch(at)
-    ah = _Arr(torch.as_tensor(np.asarray([at], dtype=dt)).to(cds.t.device) if dev else np.asarray([at], dtype=dt),
-              dtype=dt) if scalar else _per_col(at, ncol, dt, dev, cds)
-    out, optr = _alloc((ncol,), dt, dev, cds)
-    L.check(lib.xp_interp_level(C.byref(_view(cds, nlev, ncol)), C.byref(_view(x, nlev, ncol)), C.c_void_p(ah.ptr),
-                                C.c_int32(int(scalar)), C.c_int32(int(log)), C.c_void_p(optr), _stream(dev)))
-    return out.reshape(hshape)
+    out = c.out(c.hshape)
+    c.run('xp_interp_level', *map(c.view, c.ins), c.array([at]) if scalar else c.per_col(at), int(scalar), int(log), out)
+    return out
 
 
 def interp_levels(coords, variables, ats, log=False):
     """interp_level() for up to four variables at up to four scalar coordinates in one pass over the column
     (xp_interp_levels): returns [[variable v at ats[j] for j] for v]."""
-    arrs, dt, dev = _common(coords, *variables)
-    cds, xs = arrs[0], arrs[1:]
+    c = _Call(coords, *variables)
+    cds, xs = c.ins[0], c.ins[1:]
     assert 1 <= len(xs) <= 4 and 1 <= len(ats) <= 4, 'one to four variables, one to four coordinates'
     assert all(x.shape == cds.shape for x in xs), 'coords and variables must share a shape'
-    nlev, ncol, hshape = _vert_shape(cds)
-    lib = L.init(_device_of(cds))
-    views = [_view(x, nlev, ncol) for x in xs]
-    vptrs = (C.POINTER(L.View) * len(xs))(*[C.pointer(v) for v in views])
-    outs = [[_alloc((ncol,), dt, dev, cds) for _ in ats] for _ in xs]
-    optrs = (C.c_void_p * (len(xs) * len(ats)))(*[o[1] for row in outs for o in row])
+    vptrs = (C.POINTER(L.View) * len(xs))(*[C.pointer(c.view(x)) for x in xs])
+    outs = [[c.out(c.hshape) for _ in ats] for _ in xs]
+    optrs = (C.c_void_p * (len(xs) * len(ats)))(*[_ptr(o) for row in outs for o in row])
     at = (C.c_double * len(ats))(*[float(a) for a in ats])
-    L.check(lib.xp_interp_levels(C.byref(_view(cds, nlev, ncol)), C.c_int32(len(xs)), vptrs, C.c_int32(len(ats)), at,
-                                 C.c_int32(int(log)), optrs, _stream(dev)))
-    return [[o[0].reshape(hshape) for o in row] for row in outs]
+    c.run('xp_interp_levels', c.view(cds), len(xs), vptrs, len(ats), at, int(log), optrs)
+    return outs
 
 
 def dewpoint_from_specific_humidity(pressure, temperature, specific_humidity):
     """metpy.calc.dewpoint_from_specific_humidity, MetPy 1.4.1 chain (parcel_test.py:262-266, pf.py:1889), K."""
-    (p, t, q), dt, dev = _common(pressure, temperature, specific_humidity)
+    c = _Call(pressure, temperature, specific_humidity)
+    p, t, q = c.ins
     assert p.shape == t.shape == q.shape, 'pressure, temperature, specific_humidity must share a shape'
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    out, optr = _alloc((nlev, ncol), dt, dev, p)
-    L.check(lib.xp_dewpoint_from_specific_humidity(C.byref(_view(p, nlev, ncol)), C.byref(_view(t, nlev, ncol)),
-                                                   C.byref(_view(q, nlev, ncol)), C.c_void_p(optr), _stream(dev)))
-    return out.reshape((nlev,) + hshape)
+    out = c.out(p.shape)
+    c.run('xp_dewpoint_from_specific_humidity', *map(c.view, c.ins), out)
+    return out
 
 
 def mixing_ratio(temperature, dewpoint, pressure):
     """pf.py:684: RH(T, Td) x saturation mixing ratio at (p, T) [kg/kg]."""
-    (t, td, p), dt, dev = _common(temperature, dewpoint, pressure)
+    c = _Call(temperature, dewpoint, pressure)
+    t, td, p = c.ins
     assert t.shape == td.shape == p.shape, 'temperature, dewpoint, pressure must share a shape'
-    shape = t.shape
-    n = int(np.prod(shape)) if shape else 1
-    lib = L.init(_device_of(t))
-    out, optr = _alloc((n,), dt, dev, t)
-    L.check(lib.xp_mixing_ratio(C.byref(_view(t, 1, n)), C.byref(_view(td, 1, n)), C.byref(_view(p, 1, n)),
-                                C.c_void_p(optr), _stream(dev)))
-    return out.reshape(shape)
+    n = int(np.prod(t.shape))
+    out = c.out(t.shape)
+    c.run('xp_mixing_ratio', *[c.view(a, 1, n) for a in c.ins], out)
+    return out
 
 
 def virtual_temperature(temperature, mixing_ratio, epsilon=0.608):
@@ -530,15 +420,11 @@ def virtual_temperature(temperature, mixing_ratio, epsilon=0.608):
 def crossing_level(x, a, value):
     """Smallest x over all intersections of the profile a(x) with the constant `value` (find_intersections
     pf.py:992 + the min of pf.py:2153): freezing_level_height is crossing_level(height, temperature, 273.15)."""
-    (xh, ah), dt, dev = _common(x, a)
-    assert xh.shape == ah.shape
-    nlev, ncol, hshape = _vert_shape(xh)
-    lib = L.init(_device_of(xh))
-    out, optr = _alloc((ncol,), dt, dev, xh)
-    L.check(lib.xp_crossing_level(C.byref(_view(xh, nlev, ncol)), C.byref(_view(ah, nlev, ncol)), C.c_double(float(value)),
-                                  C.c_void_p(optr), _stream(dev)))
-    return out.reshape(hshape)
-
+    c = _Call(x, a)
+    assert c.ins[0].shape == c.ins[1].shape
+    out = c.out(c.hshape)
+    c.run('xp_crossing_level', *map(c.view, c.ins), float(value), out)
+    return out
 
 
 # -- the reference's array primitives (pf.py:63-100, 164-227, 858-1064, 1200-1289, 1517-1555, 1604-1649, 1699-1720) --------
@@ -549,15 +435,12 @@ def insert_level(d, level, coords='pressure', fill_value=-999):
     the keys of `level` define the output (pf.py:983)."""
     out = {}
     for k in level.keys():
-        (cds, v), dt, dev = _common(d[coords], d[k])
+        c = _Call(d[coords], d[k])
+        cds, v = c.ins
         assert cds.shape == v.shape, 'variables of a dataset must share a shape'
-        nlev, ncol, hshape = _vert_shape(cds)
-        lib = L.init(_device_of(cds))
-        lc, lv = _per_col(level[coords], ncol, dt, dev, cds), _per_col(level[k], ncol, dt, dev, cds)
-        arr, ptr = _alloc((nlev + 1, ncol), dt, dev, cds)
-        L.check(lib.xp_insert_level(C.byref(_view(cds, nlev, ncol)), C.byref(_view(v, nlev, ncol)), C.c_void_p(lc.ptr),
-                                    C.c_void_p(lv.ptr), C.c_double(float(fill_value)), C.c_void_p(ptr), _stream(dev)))
-        out[k] = arr.reshape((nlev + 1,) + hshape)
+        out[k] = c.out((c.nlev + 1,) + c.hshape)
+        c.run('xp_insert_level', c.view(cds), c.view(v), c.per_col(level[coords]), c.per_col(level[k]), float(fill_value),
+              out[k])
     return out
 
 
@@ -566,32 +449,12 @@ INTERSECTION_KEYS = ('all_intersect_x', 'all_intersect_y', 'increasing_x', 'incr
 
 def find_intersections(x, a, b=None, log_x=False):
     """pf.py:992: dict of six (nlev - 1, ...) arrays; entry i belongs to the interval between levels i and i + 1."""
-    ins = (x, a) if b is None else (x, a, b)
-    hs, dt, dev = _common(*ins)
-    xh = hs[0]
-    assert all(h.shape == xh.shape for h in hs), 'x, a, b must share a shape'
-    nlev, ncol, hshape = _vert_shape(xh)
-    lib = L.init(_device_of(xh))
-    outs = [_alloc((nlev - 1, ncol), dt, dev, xh) for _ in INTERSECTION_KEYS]
-    optrs = (C.c_void_p * 6)(*[o[1] for o in outs])
-    bview = C.byref(_view(hs[2], nlev, ncol)) if b is not None else None
-    L.check(lib.xp_find_intersections(C.byref(_view(xh, nlev, ncol)), C.byref(_view(hs[1], nlev, ncol)), bview,
-                                      C.c_int32(int(bool(log_x))), optrs, _stream(dev)))
-    return {k: o[0].reshape((nlev - 1,) + hshape) for k, o in zip(INTERSECTION_KEYS, outs)}
-
-
-def _mask_handle(mask, shape, dev, like):
-    """bool / integer mask -> dense uint8 of `shape` in the memory space of the call."""
-    if _is_torch(mask):
-        if dev:
-            m = (mask != 0).to(torch.uint8).reshape(shape).contiguous().to(like.t.device)
-            return m, m.data_ptr()
-        mask = mask.cpu().numpy()
-    m = np.ascontiguousarray((np.asarray(mask) != 0).reshape(shape), dtype=np.uint8)
-    if dev:
-        m = torch.as_tensor(m).to(like.t.device)
-        return m, m.data_ptr()
-    return m, m.ctypes.data
+    c = _Call(*((x, a) if b is None else (x, a, b)))
+    assert all(h.shape == c.ins[0].shape for h in c.ins), 'x, a, b must share a shape'
+    out = {k: c.out((c.nlev - 1,) + c.hshape) for k in INTERSECTION_KEYS}
+    c.run('xp_find_intersections', c.view(c.ins[0]), c.view(c.ins[1]), c.view(c.ins[2]) if b is not None else None,
+          int(bool(log_x)), (C.c_void_p * 6)(*map(_ptr, out.values())))
+    return out
 
 
 def trapz(dat, x, mask=None, only_positive=False, only_negative=False):
@@ -599,16 +462,13 @@ def trapz(dat, x, mask=None, only_positive=False, only_negative=False):
     assert not (only_positive and only_negative), 'Only negative OR positive regions can be included in trapz.'   # pf.py:200
     if isinstance(dat, dict):
         return {k: trapz(v, x, mask=mask, only_positive=only_positive, only_negative=only_negative) for k, v in dat.items()}
-    (d, xh), dt, dev = _common(dat, x)
+    c = _Call(dat, x)
+    d, xh = c.ins
     assert d.shape == xh.shape, 'dat and x must share a shape'
-    nlev, ncol, hshape = _vert_shape(d)
-    lib = L.init(_device_of(d))
-    keep, mptr = (None, None) if mask is None else _mask_handle(mask, (max(nlev - 1, 0), ncol), dev, d)
-    out, optr = _alloc((ncol,), dt, dev, d)
-    L.check(lib.xp_trapz(C.byref(_view(d, nlev, ncol)), C.byref(_view(xh, nlev, ncol)), C.c_void_p(mptr),
-                         C.c_int32(int(bool(only_positive))), C.c_int32(int(bool(only_negative))), C.c_void_p(optr), _stream(dev)))
-    del keep
-    return out.reshape(hshape)
+    out = c.out(c.hshape)
+    c.run('xp_trapz', c.view(d), c.view(xh), None if mask is None else c.mask(mask, (max(c.nlev - 1, 0), c.ncol)),
+          int(bool(only_positive)), int(bool(only_negative)), out)
+    return out
 
 
 AREA_KEYS = ('area', 'dx', 'x', 'x_from', 'x_to')
@@ -619,28 +479,22 @@ def trap_around_zeros(x, y, log_x=True, start=0):
     arrays, the areas before the zeros of y (rows 0 .. nlev-1) followed by the areas after them; mask: (nlev, ...) bool,
     True where no area was taken out of an interval."""
     assert start == 0, 'only start=0 is implemented (the reference never passes anything else)'
-    (xh, yh), dt, dev = _common(x, y)
+    c = _Call(x, y)
+    xh, yh = c.ins
     assert xh.shape == yh.shape, 'x and y must share a shape'
-    nlev, ncol, hshape = _vert_shape(xh)
-    lib = L.init(_device_of(xh))
-    outs = [_alloc((2 * nlev - 1, ncol), dt, dev, xh) for _ in AREA_KEYS]
-    optrs = (C.c_void_p * 5)(*[o[1] for o in outs])
-    mask, mptr = _alloc((nlev, ncol), np.uint8, dev, xh)
-    L.check(lib.xp_trap_around_zeros(C.byref(_view(xh, nlev, ncol)), C.byref(_view(yh, nlev, ncol)), C.c_int32(int(bool(log_x))),
-                                     optrs, C.c_void_p(mptr), _stream(dev)))
-    areas = {k: o[0].reshape((2 * nlev - 1,) + hshape) for k, o in zip(AREA_KEYS, outs)}
-    return areas, (mask != 0).reshape((nlev,) + hshape)
+    areas = {k: c.out((2 * c.nlev - 1,) + c.hshape) for k in AREA_KEYS}
+    mask = c.out(xh.shape, np.uint8)
+    c.run('xp_trap_around_zeros', c.view(xh), c.view(yh), int(bool(log_x)), (C.c_void_p * 5)(*map(_ptr, areas.values())),
+          mask)
+    return areas, mask != 0
 
 
 def bound_pressure(pressure, bound):
     """pf.py:208: the pressure of each column closest to `bound` (scalar or one per column)."""
-    (p,), dt, dev = _common(pressure)
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    b = _per_col(bound, ncol, dt, dev, p)
-    out, optr = _alloc((ncol,), dt, dev, p)
-    L.check(lib.xp_bound_pressure(C.byref(_view(p, nlev, ncol)), C.c_void_p(b.ptr), C.c_void_p(optr), _stream(dev)))
-    return out.reshape(hshape)
+    c = _Call(pressure)
+    out = c.out(c.hshape)
+    c.run('xp_bound_pressure', c.view(c.ins[0]), c.per_col(bound), out)
+    return out
 
 
 def get_layer(dat, depth=100, interpolate=True):
@@ -648,15 +502,11 @@ def get_layer(dat, depth=100, interpolate=True):
     is inserted as a level (nlev + 1 rows)."""
     out = {}
     for k, v in dat.items():
-        (p, x), dt, dev = _common(dat['pressure'], v)
+        c = _Call(dat['pressure'], v)
+        p, x = c.ins
         assert p.shape == x.shape, 'variables of a dataset must share a shape'
-        nlev, ncol, hshape = _vert_shape(p)
-        lib = L.init(_device_of(p))
-        rows = nlev + (1 if interpolate else 0)
-        arr, ptr = _alloc((rows, ncol), dt, dev, p)
-        L.check(lib.xp_get_layer(C.byref(_view(p, nlev, ncol)), C.byref(_view(x, nlev, ncol)), C.c_double(float(depth)),
-                                 C.c_int32(int(bool(interpolate))), C.c_int32(int(k == 'pressure')), C.c_void_p(ptr), _stream(dev)))
-        out[k] = arr.reshape((rows,) + hshape)
+        out[k] = c.out((c.nlev + (1 if interpolate else 0),) + c.hshape)
+        c.run('xp_get_layer', c.view(p), c.view(x), float(depth), int(bool(interpolate)), int(k == 'pressure'), out[k])
     return out
 
 
@@ -665,41 +515,28 @@ def shift_out_nans(x, name):
     x[name] in that column."""
     out = {}
     for k, v in x.items():
-        (nh, vh), dt, dev = _common(x[name], v)
+        c = _Call(x[name], v)
+        nh, vh = c.ins
         assert nh.shape == vh.shape, 'variables of a dataset must share a shape'
-        nlev, ncol, hshape = _vert_shape(nh)
-        lib = L.init(_device_of(nh))
-        arr, ptr = _alloc((nlev, ncol), dt, dev, nh)
-        L.check(lib.xp_shift_out_nans(C.byref(_view(nh, nlev, ncol)), C.byref(_view(vh, nlev, ncol)), C.c_void_p(ptr), _stream(dev)))
-        out[k] = arr.reshape((nlev,) + hshape)
+        out[k] = c.out(nh.shape)
+        c.run('xp_shift_out_nans', c.view(nh), c.view(vh), out[k])
     return out
 
 
 def _rebase(pressure, temperature, dewpoint, mode, depth):
-    (p, t, td), dt, dev = _common(pressure, temperature, dewpoint)
+    c = _Call(pressure, temperature, dewpoint)
+    p, t, td = c.ins
     assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-    nlev, ncol, hshape = _vert_shape(p)
-    lib = L.init(_device_of(p))
-    pc = L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None)
-    so = L.ScalarsOut()
-    so.dtype, so.mem = p.xp_dtype, p.mem
-    par = {}
-    for k in L.SCALAR_P + ('parcel_index',):
-        arr, ptr = _alloc((ncol,), np.int32 if k == 'parcel_index' else dt, dev, p)
-        setattr(so, k, ptr)
-        par[k] = arr
-    rows = nlev + (1 if mode == 'mixed_layer' else 0)
-    outs = [_alloc((rows, ncol), dt, dev, p) for _ in range(3)]
-    kept = np.zeros(nlev, dtype=np.int32)
+    so, par = c.scalars(L.SCALAR_P + ('parcel_index',), c.hshape)
+    outs = [c.out((c.nlev + (1 if mode == 'mixed_layer' else 0),) + c.hshape) for _ in range(3)]
+    kept = np.zeros(c.nlev, dtype=np.int32)
     nout = C.c_int64(0)
-    L.check(lib.xp_rebase_profile(C.byref(_view(p, nlev, ncol)), C.byref(_view(t, nlev, ncol)), C.byref(_view(td, nlev, ncol)),
-                                  C.byref(pc), C.c_void_p(outs[0][1]), C.c_void_p(outs[1][1]), C.c_void_p(outs[2][1]), C.byref(so),
-                                  kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nout), _stream(dev)))
-    n = int(nout.value)
-    arrs = [o[0].reshape((rows,) + hshape)[:n] for o in outs]
-    parcel = {'pressure': par['parcel_pressure'].reshape(hshape), 'temperature': par['parcel_temperature'].reshape(hshape),
-              'dewpoint': par['parcel_dewpoint'].reshape(hshape), 'index': par['parcel_index'].reshape(hshape)}
-    return arrs[0], arrs[1], arrs[2], parcel, kept.astype(bool)
+    c.run('xp_rebase_profile', c.view(p), c.view(t), c.view(td), L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None),
+          *outs, so, kept, C.byref(nout))
+    n = nout.value
+    parcel = {'pressure': par['parcel_pressure'], 'temperature': par['parcel_temperature'],
+              'dewpoint': par['parcel_dewpoint'], 'index': par['parcel_index']}
+    return outs[0][:n], outs[1][:n], outs[2][:n], parcel, kept.astype(bool)
 
 
 def from_most_unstable_parcel(pressure, temperature, dewpoint, depth=300):
@@ -719,26 +556,19 @@ def mix_layer(pressure, temperature, dewpoint, depth=100):
 def interp1d(at, xp, fp):
     """pf.py:23 interp1d_numba = numpy.interp along the vertical: at (m, ...), xp / fp (n, ...) or (n,) shared by all
     columns; xp increasing along the vertical."""
-    (ah,), dt, dev = _common(at)
-    m, ncol, hshape = _vert_shape(ah)
+    c = _Call(at)
+    ah = c.ins[0]
 
     def pts(v):
-        if _is_torch(v):
-            h = _Arr(v.to(ah.t.device) if dev else v.cpu().numpy(), dtype=dt)
-        else:
-            v = np.asarray(v, dtype=dt)
-            h = _Arr(torch.as_tensor(v).to(ah.t.device) if dev else v, dtype=dt)
-        n = h.shape[0]
-        cols = int(np.prod(h.shape[1:])) if len(h.shape) > 1 else 1
-        assert cols in (1, ncol), 'xp / fp must have one column or one per column of `at`'
-        return h, n, cols
+        a = c.array(v)
+        cols = int(np.prod(a.shape[1:]))
+        assert cols in (1, c.ncol), 'xp / fp must have one column or one per column of `at`'
+        return a, a.shape[0], cols
     (xh, n, xc), (fh, n2, fc) = pts(xp), pts(fp)
     assert n == n2, 'xp and fp must have the same number of points'
-    lib = L.init(_device_of(ah))
-    out, optr = _alloc((m, ncol), dt, dev, ah)
-    L.check(lib.xp_interp1d(C.byref(_view(ah, m, ncol)), C.byref(_view(xh, n, xc)), C.byref(_view(fh, n, fc)),
-                            C.c_void_p(optr), _stream(dev)))
-    return out.reshape((m,) + hshape)
+    out = c.out(ah.shape)
+    c.run('xp_interp1d', c.view(ah), c.view(xh, n, xc), c.view(fh, n, fc), out)
+    return out
 
 
 def add_lcl_to_profile(profile, environment=None, interpolator='log'):
@@ -839,35 +669,25 @@ def _flat(hs):
     return n
 
 
-def _as_bool(x):
-    return (x != 0)
-
-
 def wind_shear(surface_wind_u, surface_wind_v, wind_u, wind_v, height, shear_height=6000):
     """pf.py:2216: wind at `shear_height` (linear interpolation in height) minus the surface wind (xp_wind_shear)."""
-    (wu, wv, hh), dt, dev = _common(wind_u, wind_v, height)
+    c = _Call(wind_u, wind_v, height)
+    wu, wv, hh = c.ins
     assert wu.shape == wv.shape == hh.shape, 'wind_u, wind_v, height must share a shape'
-    nw, ncol, hshape = _vert_shape(wu)
-    lib = L.init(_device_of(wu))
-    su, sv = _per_col(surface_wind_u, ncol, dt, dev, wu), _per_col(surface_wind_v, ncol, dt, dev, wu)
-    outs = [_alloc((ncol,), dt, dev, wu) for _ in range(3)]
-    pos, pptr = _alloc((ncol,), np.int32, dev, wu)
-    L.check(lib.xp_wind_shear(C.byref(_view(wu, nw, ncol)), C.byref(_view(wv, nw, ncol)), C.byref(_view(hh, nw, ncol)),
-                              C.c_void_p(su.ptr), C.c_void_p(sv.ptr), C.c_double(float(shear_height)), C.c_void_p(outs[0][1]),
-                              C.c_void_p(outs[1][1]), C.c_void_p(outs[2][1]), C.c_void_p(pptr), _stream(dev)))
-    return {'shear_u': outs[0][0].reshape(hshape), 'shear_v': outs[1][0].reshape(hshape),
-            'shear_magnitude': outs[2][0].reshape(hshape), 'positive_shear': _as_bool(pos).reshape(hshape)}
+    res = {k: c.out(c.hshape) for k in ('shear_u', 'shear_v', 'shear_magnitude')}
+    pos = c.out(c.hshape, np.int32)
+    c.run('xp_wind_shear', *map(c.view, c.ins), c.per_col(surface_wind_u), c.per_col(surface_wind_v), float(shear_height),
+          *res.values(), pos)
+    res['positive_shear'] = pos != 0
+    return res
 
 
 def significant_hail_parameter(mucape, mixing_ratio, lapse, temp_500, shear, flh):
     """pf.py:2261 (SPC SHIP) with the reference's validity windows (xp_significant_hail_parameter)."""
-    hs, dt, dev = _common(mucape, mixing_ratio, lapse, temp_500, shear, flh)
-    n = _flat(hs)
-    lib = L.init(_device_of(hs[0]))
-    out, optr = _alloc((n,), dt, dev, hs[0])
-    L.check(lib.xp_significant_hail_parameter(C.c_int64(n), C.c_int32(hs[0].xp_dtype), C.c_int32(hs[0].mem),
-                                              *[C.c_void_p(h.ptr) for h in hs], C.c_void_p(optr), _stream(dev)))
-    return out.reshape(hs[0].shape)
+    c = _Call(mucape, mixing_ratio, lapse, temp_500, shear, flh)
+    out = c.out(c.ins[0].shape)
+    c.run('xp_significant_hail_parameter', _flat(c.ins), c.xp_dtype, c.mem, *c.ins, out)
+    return out
 
 
 def conv_properties(dat, ignore_nans=False, moist=None):
@@ -879,37 +699,40 @@ def conv_properties(dat, ignore_nans=False, moist=None):
     (...): NumPy arrays (staged through the library) or torch CUDA tensors (in place).  Returns a dict of per-column
     arrays with the reference's variable names (positive_shear: bool)."""
     order = L.CONV_IN_VIEWS + ('surface_wind_u', 'surface_wind_v')
-    hs, dt, dev = _common(*[dat[k] for k in order])
-    h = dict(zip(order, hs))
+    c = _Call(*[dat[k] for k in order])
+    h = dict(zip(order, c.ins))
     p = h['pressure']
     assert all(h[k].shape == p.shape for k in ('temperature', 'specific_humidity', 'height_asl')), 'pressure, temperature, specific_humidity, height_asl must share a shape'
-    nlev, ncol, hshape = _vert_shape(p)
     wu = h['wind_u']
-    assert wu.shape == h['wind_v'].shape == h['wind_height_above_surface'].shape and tuple(wu.shape[1:]) == hshape, 'wind arrays must be (nwind, ...) over the same points'
-    nwind = wu.shape[0]
-    lib = L.init(_device_of(p))
-    views = {k: _view(h[k], nlev if k in L.CONV_IN_VIEWS[:4] else nwind, ncol) for k in L.CONV_IN_VIEWS}
-    ci = L.ConvIn(*[C.pointer(views[k]) for k in L.CONV_IN_VIEWS], h['surface_wind_u'].ptr, h['surface_wind_v'].ptr)
-    assert int(np.prod(h['surface_wind_u'].shape)) == ncol and int(np.prod(h['surface_wind_v'].shape)) == ncol
-    co, out = L.ConvOut(), {}
-    for k in L.CONV_OUT:
-        arr, ptr = _alloc((ncol,), np.int32 if k == 'positive_shear' else dt, dev, p)
-        setattr(co, k, ptr)
-        out[k] = arr
-    o = _opts(moist=moist or _DEFAULT['moist'])
-    L.check(lib.xp_conv_properties(C.byref(ci), C.byref(o), C.c_int32(int(bool(ignore_nans))), C.byref(co), _stream(dev)))
-    res = {k: v.reshape(hshape) for k, v in out.items()}
+    assert wu.shape == h['wind_v'].shape == h['wind_height_above_surface'].shape and tuple(wu.shape[1:]) == c.hshape, 'wind arrays must be (nwind, ...) over the same points'
+    views = [C.pointer(c.view(h[k])) for k in L.CONV_IN_VIEWS]
+    assert int(np.prod(h['surface_wind_u'].shape)) == c.ncol and int(np.prod(h['surface_wind_v'].shape)) == c.ncol
+    ci = L.ConvIn(*views, _ptr(h['surface_wind_u']), _ptr(h['surface_wind_v']))
+    co, res = L.ConvOut(), {k: c.out(c.hshape, np.int32 if k == 'positive_shear' else None) for k in L.CONV_OUT}
+    for k, a in res.items():
+        setattr(co, k, _ptr(a))
+    c.run('xp_conv_properties', ci, _opts(moist=moist or _DEFAULT['moist']), int(bool(ignore_nans)), co)
     res['positive_shear'] = res['positive_shear'] != 0
     return res
 
 
+def _on_device_once(bundle):
+    """A bundle of ~25 launches given host arrays uploads them once, works on device-resident data and brings its results
+    back as NumPy arrays."""
+    @functools.wraps(bundle)
+    def call(dat, *args, **kwargs):
+        host_in = not any(_is_torch(v) and v.is_cuda for v in dat.values())
+        if host_in and torch is not None and torch.cuda.is_available():
+            dat = {k: torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.float64))).cuda() for k, v in dat.items()}
+        out = bundle(dat, *args, **kwargs)
+        return {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in out.items()} if host_in else out
+    return call
+
+
+@_on_device_once
 def conv_properties_composed(dat, ignore_nans=False, moist=None):
     """The same bundle as a composition of the stand-alone calls plus array arithmetic (what conv_properties() was before
     xp_conv_properties existed): kept as the cross-check of the fused call (tests/test_gpu_indices.py)."""
-    host_in = not any(_is_torch(v) for v in dat.values())
-    if host_in and torch is not None and torch.cuda.is_available():
-        # one upload; the ~25 kernel launches of the bundle then work on device-resident data
-        dat = {k: torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.float64))).cuda() for k, v in dat.items()}
     p, t, q = dat['pressure'], dat['temperature'], dat['specific_humidity']
     td = dewpoint_from_specific_humidity(p, t, q)
     xp = _ns(td)
@@ -946,18 +769,14 @@ def conv_properties_composed(dat, ignore_nans=False, moist=None):
                 out[k] = _where(valid, out[k], float('nan'))
             else:
                 out[k] = out[k] & valid          # xarray's where() turns a masked boolean into NaN; here: False
-    if host_in:
-        out = {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in out.items()}
     return out
 
 
+@_on_device_once
 def min_conv_properties(dat, moist=None):
     """pf.py:1873: the minimal bundle -- 100 hPa mixed-layer CAPE / CIN and lifted index, 700-500 hPa lapse rate, 500 hPa
     temperature, freezing and melting level, 0-6 km shear.  Same input mapping as conv_properties(); no NaN blanking
     (the reference has none here)."""
-    host_in = not any(_is_torch(v) for v in dat.values())
-    if host_in and torch is not None and torch.cuda.is_available():
-        dat = {k: torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.float64))).cuda() for k, v in dat.items()}
     p, t, z = dat['pressure'], dat['temperature'], dat['height_asl']
     td = dewpoint_from_specific_humidity(p, t, dat['specific_humidity'])
     ml = cape_cin_columns(p, t, td, parcel='mixed_layer', depth=100, lifted_index_at=500.0, moist=moist)
@@ -967,38 +786,23 @@ def min_conv_properties(dat, moist=None):
            'freezing_level': freezing_level_height(t, z), 'melting_level': melting_level_height(p, t, td, z)[0]}
     out.update(wind_shear(dat['surface_wind_u'], dat['surface_wind_v'], dat['wind_u'], dat['wind_v'],
                           dat['wind_height_above_surface']))
-    if host_in:
-        out = {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in out.items()}
     return out
 
 
 def storm_proxies(dat):
     """pf.py:2323: hail / storm proxies (booleans) and SHIP from the output of conv_properties(), one per-point kernel
     (xp_storm_proxies)."""
-    hs, dt, dev = _common(*[dat[k] for k in L.PROXIES_IN])
-    n = _flat(hs)
-    shape = hs[0].shape
-    lib = L.init(_device_of(hs[0]))
-    ps = dat['positive_shear']
-    if _is_torch(ps):
-        ps = ps.to(torch.int32)
-        ps = ps.to(hs[0].t.device) if dev else ps.cpu().numpy()
-    else:
-        ps = np.asarray(ps).astype(np.int32)
-        if dev:
-            ps = torch.as_tensor(ps).to(hs[0].t.device)
-    ps = ps.reshape(-1).contiguous() if _is_torch(ps) else np.ascontiguousarray(ps.reshape(-1))
+    c = _Call(*[dat[k] for k in L.PROXIES_IN])
+    n, shape = _flat(c.ins), c.ins[0].shape
+    ps = c.array(dat['positive_shear'], np.int32).reshape(-1)
     assert int(np.prod(ps.shape)) == n, 'positive_shear does not match the other arrays'
-    pin = L.ProxiesIn(*[h.ptr for h in hs], ps.data_ptr() if _is_torch(ps) else ps.ctypes.data)
-    flags = [_alloc((n,), np.int32, dev, hs[0]) for _ in L.PROXIES_OUT]
-    ship, sptr = _alloc((n,), dt, dev, hs[0])
-    pout = L.ProxiesOut(*[f[1] for f in flags], sptr)
-    L.check(lib.xp_storm_proxies(C.c_int64(n), C.c_int32(hs[0].xp_dtype), C.c_int32(hs[0].mem), C.byref(pin), C.byref(pout),
-                                 _stream(dev)))
-    out = {k: _as_bool(f[0]).reshape(shape) for k, f in zip(L.PROXIES_OUT, flags)}
-    out['ship'] = ship.reshape(shape)
+    flags = {k: c.out(shape, np.int32) for k in L.PROXIES_OUT}
+    ship = c.out(shape)
+    c.run('xp_storm_proxies', n, c.xp_dtype, c.mem, L.ProxiesIn(*map(_ptr, c.ins), _ptr(ps)),
+          L.ProxiesOut(*map(_ptr, flags.values()), _ptr(ship)))
+    out = {k: f != 0 for k, f in flags.items()}
     # the reference's order of variables (pf.py:2395-2405): proxies, SHIP, the SHIP proxy
-    return {**{k: out[k] for k in L.PROXIES_OUT[:8]}, 'ship': out['ship'], 'proxy_SHIP_0.1': out['proxy_SHIP_0.1']}
+    return {**{k: out[k] for k in L.PROXIES_OUT[:8]}, 'ship': ship, 'proxy_SHIP_0.1': out['proxy_SHIP_0.1']}
 
 
 def family_table():
@@ -1008,7 +812,7 @@ def family_table():
     n1, n2 = C.c_int64(), C.c_int64()
     L.check(lib.xp_family_table(None, C.byref(n1), C.byref(n2)))
     out = np.empty((n1.value, n2.value), dtype=np.float64)
-    L.check(lib.xp_family_table(out.ctypes.data_as(C.c_void_p), None, None))
+    L.check(lib.xp_family_table(out.ctypes.data, None, None))
     return out
 
 
@@ -1016,4 +820,4 @@ def set_family_table(table):
     """Replace the adiabat-family table (xp_set_family_table)."""
     t = np.ascontiguousarray(table, dtype=np.float64)
     t = t.reshape(-1, t.shape[-1])
-    L.check(L.init().xp_set_family_table(t.ctypes.data_as(C.c_void_p), C.c_int64(t.shape[0]), C.c_int64(t.shape[1])))
+    L.check(L.init().xp_set_family_table(t.ctypes.data, *t.shape))
