@@ -122,3 +122,12 @@ def test_call_decision_host_inputs():
         assert (v.mem, v.nlev, v.ncol, v.lev_stride, v.col_stride) == (L.XP_MEM_HOST, 4, 6, 6, 1)
     with pytest.raises(AssertionError, match='per-column argument does not match the grid'):
         xa._Call(a32).per_col(np.ones(5))
+
+
+def test_error_codes_follow_header():
+    """_lib's XP_OK / XP_E_* constants are the header's error-code enum, name for name and value for value."""
+    body = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
+    enum = re.search(r'enum\s*\{([^{}]*\bXP_E_ARG\b[^{}]*)\}', body).group(1)
+    declared = {k: int(v) for k, v in re.findall(r'(XP_(?:OK|E_\w+))\s*=\s*(-?\d+)', enum)}
+    ours = {k: getattr(L, k) for k in dir(L) if k == 'XP_OK' or k.startswith('XP_E_')}
+    assert declared == ours and len(ours) == 7, (declared, ours)

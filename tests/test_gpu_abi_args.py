@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 
 from xarray_parcel_amd import _lib as L
+from xarray_parcel_amd._lib import XP_E_ARG, XP_E_INTERP, XP_E_NO_TABLES, XP_E_NOT_INIT
 from xarray_parcel_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-XP_E_ARG, XP_E_NOT_INIT, XP_E_NO_TABLES, XP_E_INTERP = -1, -2, -3, -4
 NLEV, NCOL = 12, 40
 
 

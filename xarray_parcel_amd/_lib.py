@@ -148,6 +148,10 @@ ARGTYPES = {
 }
 
 
+# return codes of the entry points (the error-code enum of include/xparcel.h)
+XP_OK, XP_E_ARG, XP_E_NOT_INIT, XP_E_NO_TABLES, XP_E_INTERP, XP_E_HIP, XP_E_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6
+
+
 class XParcelError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libxparcel error {code}: {msg}')
