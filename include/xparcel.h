@@ -95,11 +95,12 @@ enum {
     XP_ST_BAD_PRESSURE = 8,     /* a pressure higher than the level below it: outside the input contract (README.md:9,
                                    pf.py:2319-2320); the column's other outputs are unspecified.  (A pressure <= 0 has no
                                    logarithm: it is not tested for as such, but in practice trips this test too.) */
-    XP_ST_NAN_PRESSURE = 4      /* a NaN pressure below the LCL.  The level is treated as MISSING -- exactly as if its
+    XP_ST_NAN_PRESSURE = 4,     /* a NaN pressure below the LCL.  The level is treated as MISSING -- exactly as if its
                                    temperature and dewpoint were NaN too: the two intervals that touch it drop out of
                                    every sum and the LCL bracket skips it -- not as the reference's insert_level does
                                    (pf.py:962-966 puts a copy of the LCL into the NaN slot and integrates over the
                                    out-of-order profile).  Contract: tests/test_gpu_parity.py::test_nan_pressure_levels */
+    XP_ST_NO_LAYER = 16         /* xp_downdraft_cape: the column does not span the layer (MetPy raises); every output NaN */
 };
 
 typedef struct {
@@ -256,6 +257,28 @@ int xp_mixed_layer(const xp_view *pressure, const xp_view *variable, double dept
    the moist adiabat to the element's own pressure (pf.py:525).  out has the layout of `pressure`. */
 int xp_wet_bulb_temperature(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint,
                             int32_t moist_mode, void *out, void *stream);
+
+/* metpy.calc.downdraft_cape (MetPy 1.4; the reference has no counterpart): downdraft CAPE of every column.  Levels where
+   p, T or Td is NaN are dropped.  The layer runs from layer_bottom (b, MetPy: 700 hPa) up layer_depth (MetPy: 200 hPa) to
+   u = b - layer_depth: every level with u <= p <= b (np.isclose counting as equal), plus b and u themselves where no layer
+   level is close to them, with T and Td interpolated linearly in ln p.  The start point p0 is the first layer point, in
+   order of decreasing pressure, with the smallest Bolton theta_e; its wet-bulb temperature wb0 (xp_wet_bulb_temperature's
+   chain) starts a moist descent (xp_moist_lapse from (p0, wb0)) through every level with p >= p0, and
+       DCAPE = -Rd * trapz(Tv_env - Tv_parcel, ln p)  [J/kg]  over those levels,
+   Tv in MetPy's form T (w + eps) / (eps (1 + w)) -- not the T (1 + 0.608 w) of the CAPE path -- with w the saturation
+   mixing ratio at Td (environment) or at the parcel temperature (the parcel is saturated).  Moist modes as in
+   xp_wet_bulb_temperature (XP_MOIST_FAMILY runs the RK4 descent).  Every output may be NULL; the outputs share the views'
+   dtype and mem.  Strided device views are read in place. */
+typedef struct {
+    void *dcape;              /* J/kg, ncol */
+    void *start_pressure;     /* hPa: p0 (a level's pressure or an added bound) */
+    void *start_temperature;  /* K: wb0 */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_LCL_NOT_CONVERGED (the start point's LCL) */
+    void *parcel_temperature; /* dense C-order (nlev, ncol): Tp on the down levels, NaN elsewhere */
+    int32_t dtype, mem;
+} xp_dcape_out;
+int xp_downdraft_cape(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint,
+                      double layer_bottom, double layer_depth, int32_t moist_mode, xp_dcape_out *out, void *stream);
 
 /* pf.py:1758-1811 linear_interp / pf.py:1813-1828 log_interp: value of `variable` at coordinate `at` (one value per
    column, or a single value for all when at_is_scalar) between the bracketing levels of `coords`; duplicates of a

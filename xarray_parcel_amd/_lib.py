@@ -22,7 +22,8 @@ ST_TOP_NAN, ST_LCL_NOT_CONVERGED, ST_NAN_PRESSURE, ST_BAD_PRESSURE = 1, 2, 4, 8
 # every symbol include/xparcel.h declares
 SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_family_table', 'xp_set_family_table', 'xp_cape_cin', 'xp_cape_cin_multi', 'xp_lcl', 'xp_dry_lapse',
            'xp_moist_lapse', 'xp_parcel_profile', 'xp_lfc_el', 'xp_cape_cin_base', 'xp_select_parcel',
-           'xp_mixed_layer', 'xp_wet_bulb_temperature', 'xp_interp_level', 'xp_interp_levels', 'xp_dewpoint_from_specific_humidity',
+           'xp_mixed_layer', 'xp_wet_bulb_temperature', 'xp_downdraft_cape', 'xp_interp_level', 'xp_interp_levels',
+           'xp_dewpoint_from_specific_humidity',
            'xp_crossing_level', 'xp_mixing_ratio', 'xp_conv_properties', 'xp_insert_level', 'xp_find_intersections', 'xp_trapz',
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies',
@@ -95,6 +96,15 @@ class ProxiesOut(C.Structure):
     _fields_ = [('f%d' % i, C.c_void_p) for i in range(9)] + [('ship', C.c_void_p)]
 
 
+# xp_downdraft_cape: its outputs, and the status bit of a column that does not span the layer
+XP_ST_NO_LAYER = 16
+DCAPE_OUT = ('dcape', 'start_pressure', 'start_temperature', 'status', 'parcel_temperature')
+
+
+class DcapeOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in DCAPE_OUT] + [('dtype', C.c_int32), ('mem', C.c_int32)]
+
+
 class Tables(C.Structure):
     _fields_ = [('n_pressure', C.c_int64), ('n_temperature', C.c_int64), ('n_adiabat', C.c_int64),
                 ('p_max', C.c_double), ('p_step', C.c_double), ('t_min', C.c_double), ('t_step', C.c_double),
@@ -126,6 +136,7 @@ ARGTYPES = {
     'xp_select_parcel': (_V, _V, _V, _P, _S, _ptr),
     'xp_mixed_layer': (_V, _V, _f64, _ptr, _ptr),
     'xp_wet_bulb_temperature': (_V, _V, _V, _i32, _ptr, _ptr),
+    'xp_downdraft_cape': (_V, _V, _V, _f64, _f64, _i32, C.POINTER(DcapeOut), _ptr),
     'xp_interp_level': (_V, _V, _ptr, _i32, _i32, _ptr, _ptr),
     'xp_interp_levels': (_V, _i32, C.POINTER(_V), _i32, _ptr, _i32, C.POINTER(_ptr), _ptr),
     'xp_dewpoint_from_specific_humidity': (_V, _V, _V, _ptr, _ptr),

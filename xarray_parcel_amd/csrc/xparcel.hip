@@ -15,6 +15,7 @@
 #include "xp_kernels.hpp"
 #include "xp_multi.hpp"
 #include "xp_bundle.hpp"
+#include "xp_dcape.hpp"
 
 namespace {
 
@@ -952,6 +953,39 @@ int xp_wet_bulb_temperature(const xp_view *p, const xp_view *t, const xp_view *t
     by_dtype(p->dtype, [&](auto z) {
         launch(xp::k_wet_bulb<decltype(z)>, p->nlev * p->ncol, st, pv, tv, tdv, p->nlev, p->ncol, tm, ts.tb, ts.es, out_like(od, p));
     });
+    return st.finish();
+}
+
+int xp_downdraft_cape(const xp_view *p, const xp_view *t, const xp_view *td, double layer_bottom, double layer_depth,
+                      int32_t moist_mode, xp_dcape_out *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}}))) return rc;
+    if (!out) return fail(XP_E_ARG, "xp_downdraft_cape: out: null");
+    if (out->dtype != p->dtype || out->mem != p->mem) return fail(XP_E_ARG, "xp_downdraft_cape: out: dtype / mem differ from the views'");
+    if (!(std::isfinite(layer_bottom) && layer_bottom > 0.0))
+        return fail(XP_E_ARG, "xp_downdraft_cape: layer_bottom must be finite and positive");
+    if (!(layer_depth > 0.0 && layer_depth < layer_bottom))
+        return fail(XP_E_ARG, "xp_downdraft_cape: layer_depth must lie in (0, layer_bottom)");
+    if (moist_mode != XP_MOIST_EXACT && moist_mode != XP_MOIST_TABLE && moist_mode != XP_MOIST_FAMILY)
+        return fail(XP_E_ARG, "xp_downdraft_cape: moist_mode: unknown mode %d", (int)moist_mode);
+    const int tm = moist_mode == XP_MOIST_TABLE;
+    const size_t cb = rows_bytes(p, 1);
+    TableSet ts;
+    xp::DcapeArgs a;
+    memset(&a, 0, sizeof(a));
+    void *status;
+    if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) ||
+        (rc = stage_view(st, td, &a.td)) || (rc = st.out(out->dcape, cb, out->mem, &a.dcape)) ||
+        (rc = st.out(out->start_pressure, cb, out->mem, &a.p0)) || (rc = st.out(out->start_temperature, cb, out->mem, &a.t0)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &status)) ||
+        (rc = st.out(out->parcel_temperature, rows_bytes(p, p->nlev), out->mem, &a.prof))) return rc;
+    a.status = (int32_t *)status;
+    a.nlev = p->nlev; a.ncol = p->ncol;
+    a.bottom = layer_bottom; a.top = layer_bottom - layer_depth;
+    a.table_mode = tm; a.tb = ts.tb; a.es_tab = ts.es;
+    by_dtype(p->dtype, [&](auto z) { launch(xp::k_downdraft_cape<decltype(z)>, p->ncol, st, a); });
     return st.finish();
 }
 

@@ -367,6 +367,26 @@ def wet_bulb_temperature(pressure, temperature, dewpoint, moist=None):
     return out
 
 
+def downdraft_cape(pressure, temperature, dewpoint, bottom=700.0, depth=200.0, moist=None, want_profile=False):
+    """metpy.calc.downdraft_cape for every column (xp_downdraft_cape; the layer from `bottom` up `depth` hPa, MetPy's
+    700 and 200).  Returns a dict of per-column 'dcape' [J/kg], 'start_pressure' (p0), 'start_temperature' (its wet bulb)
+    and 'status' (ST_LCL_NOT_CONVERGED, XP_ST_NO_LAYER: the column does not span the layer, everything NaN); with
+    want_profile also 'parcel_temperature', the descending parcel on the levels with p >= p0 (NaN elsewhere), shaped like
+    the input."""
+    c = _Call(pressure, temperature, dewpoint)
+    p, t, td = c.ins
+    assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
+    res = {k: c.out(c.hshape, np.int32 if k == 'status' else None) for k in L.DCAPE_OUT[:4]}
+    if want_profile:
+        res['parcel_temperature'] = c.out(p.shape)
+    out = L.DcapeOut(dtype=c.xp_dtype, mem=c.mem)
+    for k, a in res.items():
+        setattr(out, k, _ptr(a))
+    c.run('xp_downdraft_cape', c.view(p), c.view(t), c.view(td), float(bottom), float(depth),
+          L.MOIST[moist or _DEFAULT['moist']], out)
+    return res
+
+
 def interp_level(coords, variable, at, log=False):
     """pf.py:1758 linear_interp (log=False) / pf.py:1813 log_interp (log=True) of one variable."""
     c = _Call(coords, variable)
