@@ -100,7 +100,11 @@ enum {
                                    every sum and the LCL bracket skips it -- not as the reference's insert_level does
                                    (pf.py:962-966 puts a copy of the LCL into the NaN slot and integrates over the
                                    out-of-order profile).  Contract: tests/test_gpu_parity.py::test_nan_pressure_levels */
-    XP_ST_NO_LAYER = 16         /* xp_downdraft_cape: the column does not span the layer (MetPy raises); every output NaN */
+    XP_ST_NO_LAYER = 16,        /* xp_downdraft_cape, xp_bunkers_storm_motion: the column does not span the layer (MetPy
+                                   raises), every output NaN; xp_storm_relative_helicity: some depth is not spanned, that
+                                   depth's outputs NaN */
+    XP_ST_BAD_HEIGHT = 32       /* xp_bunkers_storm_motion, xp_storm_relative_helicity: a height not above the valid level
+                                   below it (heights must increase strictly); every output NaN */
 };
 
 typedef struct {
@@ -359,6 +363,62 @@ typedef struct {
     void *ship;
 } xp_proxies_out;
 int xp_storm_proxies(int64_t n, int32_t dtype, int32_t mem, const xp_proxies_in *in, xp_proxies_out *out, void *stream);
+
+/* ---- Kinematics: storm motion, helicity and the composites built on them (MetPy 1.4; the reference has none) ----------
+   Column entry points: (nlev, ncol) views of one shape, dtype and mem, level 0 at the surface.  A level where any input is
+   NaN is dropped.  Ordering is checked on the levels read -- up to and including the first level beyond the deepest top:
+   a height not above the valid level below it gives XP_ST_BAD_HEIGHT, a pressure not below it XP_ST_BAD_PRESSURE, and
+   the column's outputs are NaN.  "close" is np.isclose with its defaults, |x - y| <= 1e-8 + 1e-5 |y|.  Arithmetic is
+   fp64.  Every output may be NULL; the outputs share the views' dtype and mem; per-column inputs are ncol elements in
+   that dtype and mem.  Strided device views are read in place. */
+
+/* metpy.calc.bunkers_storm_motion: right mover, left mover and 0-6 km mean wind of every column, from pressure, u, v and
+   height on one vertical (the caller supplies the pressure on the wind levels).  With z0, p0 the lowest valid level,
+   M(zb, d) is the layer mean of MetPy's weighted_continuous_average / get_layer:
+     pb = np.interp(zb, z, p), pt = np.interp(zb + d, z, p) (linear in height, exact at a level); the points are the levels
+     with pt <= p <= pb (close counting as inside), plus pb and pt where no point is close to them, u and v there linear
+     in ln p between the levels on either side; M = trapz(u, p) / (p_last - p_first) in order of decreasing pressure.
+   mean = M(z0, 6000 m), low = M(z0, 500 m), high = M(z0 + 5500 m, 500 m), shear = high - low,
+   rdev = (shear_v, -shear_u) * 7.5 / hypot(shear), right = mean + rdev, left = mean - rdev [m/s].
+   A column with z0 + 6000 > max z (plain comparison: MetPy raises) gets XP_ST_NO_LAYER and NaN.  Zero shear gives NaN
+   movers (0/0).  One pass: a level below the one that brackets z0 + 5500 m is not looked back at, which matters only
+   for levels closer than 1e-5 (relative) in pressure. */
+typedef struct {
+    void *right_u, *right_v, *left_u, *left_v, *mean_u, *mean_v;   /* m/s, ncol each */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_HEIGHT | XP_ST_BAD_PRESSURE */
+    int32_t dtype, mem;
+} xp_storm_motion_out;
+int xp_bunkers_storm_motion(const xp_view *pressure, const xp_view *u, const xp_view *v, const xp_view *height,
+                            xp_storm_motion_out *out, void *stream);
+
+/* metpy.calc.storm_relative_helicity (get_layer_heights with_agl) for 1 ... 4 depths in one pass.  Heights are made
+   relative to the lowest valid level, h = z - z_first; with surface_u / surface_v (both or neither; dropped where NaN)
+   the point (0 m, su, sv) comes first and heights are used as given (wind_height_above_surface).  For depth d, top =
+   bottom + d: the points are the levels with bottom <= h <= top (close counting as inside), plus bottom and top where no
+   such level EQUALS them (MetPy tests with `in`, not isclose), u and v there linear in height.  With the storm motion
+   (storm_u, storm_v; NULL = 0, MetPy's default) term_i = (u[i+1]-cu)(v[i]-cv) - (u[i]-cu)(v[i+1]-cv); positive = sum of
+   the terms > 0, negative = sum of the terms < 0, total = positive + negative [m^2/s^2].  A depth with top > max h or
+   bottom < min h (plain comparison; MetPy returns a partial sum) is not spanned: its outputs are NaN and the column's
+   status gets XP_ST_NO_LAYER.  A NaN storm motion gives NaN.  bottom >= 0 and every depth > 0, finite. */
+typedef struct {
+    void *positive[4], *negative[4], *total[4];   /* m^2/s^2, ncol each, per depth (entries past ndepth unused) */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_HEIGHT */
+    int32_t dtype, mem;
+} xp_srh_out;
+int xp_storm_relative_helicity(const xp_view *height, const xp_view *u, const xp_view *v, const void *surface_u,
+                               const void *surface_v, const void *storm_u, const void *storm_v, double bottom,
+                               int32_t ndepth, const double *depth, xp_srh_out *out, void *stream);
+
+/* metpy.calc.significant_tornado, per point in MetPy's operation order (NaN propagates):
+   lcl_term = (2000 - clip(lcl_height, 1000, 2000)) / 1000; shr = (shear < 12.5 ? 0 : min(shear, 30)) / 20;
+   stp = (sbcape * lcl_term * srh * shr) / (1500 * 150).  n elements of dtype in mem each; no argument may be NULL. */
+int xp_significant_tornado(int64_t n, int32_t dtype, int32_t mem, const void *sbcape, const void *lcl_height,
+                           const void *srh, const void *shear, void *out, void *stream);
+
+/* metpy.calc.supercell_composite, per point (NaN propagates): shr = (shear < 10 ? 0 : min(shear, 20)) / 20;
+   scp = (mucape / 1000) * (srh / 50) * shr.  As xp_significant_tornado. */
+int xp_supercell_composite(int64_t n, int32_t dtype, int32_t mem, const void *mucape, const void *srh, const void *shear,
+                           void *out, void *stream);
 
 /* ---- Array primitives of the reference's implementation -------------------------------------------------------------
    The CAPE / CIN kernels stream a column once and never build the arrays these functions return, but the reference

@@ -26,7 +26,8 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_dewpoint_from_specific_humidity',
            'xp_crossing_level', 'xp_mixing_ratio', 'xp_conv_properties', 'xp_insert_level', 'xp_find_intersections', 'xp_trapz',
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
-           'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies',
+           'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
+           'xp_storm_relative_helicity', 'xp_significant_tornado', 'xp_supercell_composite',
            'xp_last_error')
 
 
@@ -105,6 +106,23 @@ class DcapeOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in DCAPE_OUT] + [('dtype', C.c_int32), ('mem', C.c_int32)]
 
 
+# xp_bunkers_storm_motion / xp_storm_relative_helicity: their outputs (SRH: per depth, up to SRH_MAX_DEPTHS), and the
+# status bit of a column whose heights do not increase
+ST_BAD_HEIGHT = 32
+SRH_MAX_DEPTHS = 4
+STORM_MOTION_OUT = ('right_u', 'right_v', 'left_u', 'left_v', 'mean_u', 'mean_v', 'status')
+SRH_OUT = ('positive', 'negative', 'total')
+
+
+class StormMotionOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in STORM_MOTION_OUT] + [('dtype', C.c_int32), ('mem', C.c_int32)]
+
+
+class SrhOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p * SRH_MAX_DEPTHS) for k in SRH_OUT] +
+                [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
+
+
 class Tables(C.Structure):
     _fields_ = [('n_pressure', C.c_int64), ('n_temperature', C.c_int64), ('n_adiabat', C.c_int64),
                 ('p_max', C.c_double), ('p_step', C.c_double), ('t_min', C.c_double), ('t_step', C.c_double),
@@ -155,6 +173,10 @@ ARGTYPES = {
     'xp_wind_shear': (_V, _V, _V, _ptr, _ptr, _f64) + (_ptr,) * 5,
     'xp_significant_hail_parameter': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_storm_proxies': (_i64, _i32, _i32, C.POINTER(ProxiesIn), C.POINTER(ProxiesOut), _ptr),
+    'xp_bunkers_storm_motion': (_V, _V, _V, _V, C.POINTER(StormMotionOut), _ptr),
+    'xp_storm_relative_helicity': (_V, _V, _V, _ptr, _ptr, _ptr, _ptr, _f64, _i32, _ptr, C.POINTER(SrhOut), _ptr),
+    'xp_significant_tornado': (_i64, _i32, _i32) + (_ptr,) * 6,
+    'xp_supercell_composite': (_i64, _i32, _i32) + (_ptr,) * 5,
     'xp_last_error': (),
 }
 

@@ -1,0 +1,267 @@
+// xp_kinematics.hpp -- storm motion, helicity and the composites built on them (MetPy 1.4; the reference has none):
+//   k_bunkers_storm_motion     metpy.calc.bunkers_storm_motion, one thread per column;
+//   k_storm_relative_helicity  metpy.calc.storm_relative_helicity for up to four depths, one thread per column;
+//   k_significant_tornado, k_supercell_composite   per point, in MetPy's operation order.
+// The rules are stated in include/xparcel.h and restated in NumPy in tests/kinematics_restatement.py.  Each column kernel
+// makes one upward pass with level-major loads (coalesced when col_stride == 1): the layer points of MetPy's get_layer /
+// get_layer_heights are emitted in order as the walk passes them -- the levels themselves, and the added bound points
+// interpolated between the level below and the level above -- into running sums (trapezoids for the Bunkers layer means,
+// the helicity terms for SRH).  A lane is done at the first level beyond its highest top; the loop ends with a
+// wave-uniform ballot once every lane is done, so levels above 6 km (Bunkers) or the deepest SRH top are never read.
+#pragma once
+#include "xp_kernels.hpp"
+#include "xp_dcape.hpp"   // ST_NO_LAYER, isclose_
+
+namespace xp {
+
+constexpr int ST_BAD_PRESSURE = 8;    // XP_ST_BAD_PRESSURE
+constexpr int ST_BAD_HEIGHT = 32;     // XP_ST_BAD_HEIGHT
+
+// ---- Bunkers storm motion ----------------------------------------------------------------------------------------------
+struct StormMotionArgs {
+    View p, u, v, z;
+    int64_t nlev, ncol;
+    void *right_u, *right_v, *left_u, *left_v, *mean_u, *mean_v;   // per column, in the inputs' dtype (each may be null)
+    int32_t *status;
+};
+
+// One layer mean M(zb, d) of MetPy's weighted_continuous_average, streamed.  The kernel finds the bound pressures (np.interp,
+// linear in height) when the walk reaches the first level at or above each bound height -- one value per bound height,
+// shared by the layers that end or begin there -- and the layer emits its points in order of decreasing pressure into
+// trapz(u, p) and trapz(v, p).  The sums are taken of the wind relative to the layer's first point, (u0, v0), and
+// M = u0 + trapz(u - u0, p) / (p_last - p_first): the same mean, exact for a constant wind (so that zero shear is exactly
+// zero and gives MetPy's NaN movers).
+struct LayerMean {
+    double su, sv, u0, v0, pf, pl, ul, vl;   // trapz sums, first point's wind, first and last point (pressure), last point's
+    bool started, top_close, fin;            // wind relative to the first
+    XP_DEV void init() { su = sv = 0.0; u0 = v0 = pf = pl = ul = vl = qnan(); started = top_close = fin = false; }
+    XP_DEV void emit(double p, double u, double v) {
+        if (started) { u -= u0; v -= v0; su += (p - pl) * (u + ul) * 0.5; sv += (p - pl) * (v + vl) * 0.5; }
+        else { started = true; pf = p; u0 = u; v0 = v; u = v = 0.0; }
+        pl = p; ul = u; vl = v;
+    }
+    // an added bound point at pressure pe between the previous level (pp: higher pressure) and this one: u, v linear in ln p
+    XP_DEV void emit_between(double pe, double pp, double up, double vp, double p, double u, double v) {
+        const double xe = flog(pe), xp_ = flog(pp), x = flog(p);
+        const double f = (xe - x) / (xp_ - x);
+        emit(pe, u + f * (up - u), v + f * (vp - v));
+    }
+    // one valid level (p, u, v), the previous valid level (pp, up, vp) below it if has_prev; pb, pt: the bound pressures
+    // once known (NaN before), b_now / t_now: they became known at this level
+    XP_DEV void level(double p, double u, double v, double pp, double up, double vp, bool has_prev, double pb, bool b_now,
+                      double pt, bool t_now) {
+        if (fin || isnan_(pb)) return;                   // finished, or not begun
+        if (b_now) {
+            if (has_prev && isclose_(pp, pb)) emit(pp, up, vp);          // the level below, close to pb, is the first point
+            else if (!isclose_(p, pb)) emit_between(pb, pp, up, vp, p, u, v);   // pb itself (strictly between the levels)
+        }
+        if (t_now) top_close = started && isclose_(pl, pt);             // the top appears: was the last point close to it?
+        if (isnan_(pt) || p >= pt || isclose_(p, pt)) {
+            emit(p, u, v);
+            top_close = top_close || (!isnan_(pt) && isclose_(p, pt));
+        } else {                                         // the first level beyond the top: pt closes the layer
+            // (pt appeared at this level: had it appeared earlier, that level was in the layer and close to it)
+            if (!top_close && t_now) emit_between(pt, pp, up, vp, p, u, v);
+            fin = true;
+        }
+    }
+    XP_DEV double mean_u() const { return u0 + su / (pl - pf); }
+    XP_DEV double mean_v() const { return v0 + sv / (pl - pf); }
+};
+
+// np.interp(zc, z, p) at the first level (z, p) with z >= zc, the previous valid level (zp, pp) below it; NaN before that
+XP_DEV void bound_p(double &pc, bool &now, double zc, double zp, double pp, double z, double p, bool has_prev) {
+#pragma clang fp contract(off)
+    now = isnan_(pc) && z >= zc;
+    if (now) pc = (z == zc || !has_prev) ? p : (p - pp) / (z - zp) * (zc - zp) + pp;
+}
+
+template <typename T> __global__ __launch_bounds__(256)
+void k_bunkers_storm_motion(StormMotionArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.ncol) return;
+    constexpr int f64 = sizeof(T) == 8;
+    LayerMean mean, low, high;                           // z0 ... z0 + 6000, z0 ... z0 + 500, z0 + 5500 ... z0 + 6000
+    mean.init(); low.init(); high.init();
+    double z0 = qnan(), p0 = qnan(), p500 = qnan(), p5500 = qnan(), p6000 = qnan();   // the bound pressures
+    double zp = qnan(), pp = qnan(), up = qnan(), vp = qnan();
+    bool has_prev = false, done = false;
+    int bad = 0;
+    for (int64_t k = 0; k < a.nlev; ++k) {
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+        if (done) continue;
+        const double p = ld<T>(a.p, k, c), u = ld<T>(a.u, k, c), v = ld<T>(a.v, k, c), z = ld<T>(a.z, k, c);
+        if (isnan_(p) || isnan_(u) || isnan_(v) || isnan_(z)) continue;      // missing level: dropped
+        if (has_prev) {
+            bad = (z > zp ? 0 : ST_BAD_HEIGHT) | (p < pp ? 0 : ST_BAD_PRESSURE);
+            if (bad) { done = true; continue; }
+        } else {
+            z0 = z; p0 = p;
+        }
+        bool n500, n5500, n6000;
+        bound_p(p500, n500, z0 + 500.0, zp, pp, z, p, has_prev);
+        bound_p(p5500, n5500, z0 + 5500.0, zp, pp, z, p, has_prev);
+        bound_p(p6000, n6000, z0 + 6000.0, zp, pp, z, p, has_prev);
+        mean.level(p, u, v, pp, up, vp, has_prev, p0, !has_prev, p6000, n6000);
+        low.level(p, u, v, pp, up, vp, has_prev, p0, !has_prev, p500, n500);
+        high.level(p, u, v, pp, up, vp, has_prev, p5500, n5500, p6000, n6000);
+        done = mean.fin && low.fin && high.fin;
+        zp = z; pp = p; up = u; vp = v; has_prev = true;
+    }
+    // spanned: some level reached z0 + 6000 (then the 500 m layers are complete too)
+    const bool ok = !bad && has_prev && !isnan_(p6000);
+    double mu = qnan(), mv = qnan(), ru = qnan(), rv = qnan(), lu = qnan(), lv = qnan();
+    if (ok) {
+        mu = mean.mean_u(); mv = mean.mean_v();
+        const double shu = high.mean_u() - low.mean_u(), shv = high.mean_v() - low.mean_v();
+        const double s = 7.5 / hypot(shu, shv);
+        const double du = shv * s, dv = -shu * s;
+        ru = mu + du; rv = mv + dv; lu = mu - du; lv = mv - dv;
+    }
+    st(a.right_u, f64, c, ru); st(a.right_v, f64, c, rv);
+    st(a.left_u, f64, c, lu); st(a.left_v, f64, c, lv);
+    st(a.mean_u, f64, c, mu); st(a.mean_v, f64, c, mv);
+    sti(a.status, c, bad ? bad : (ok ? 0 : ST_NO_LAYER));
+}
+
+// ---- storm-relative helicity -------------------------------------------------------------------------------------------
+constexpr int SRH_MAX_DEPTHS = 4;
+
+struct SrhArgs {
+    View z, u, v;
+    int64_t nlev, ncol;
+    const void *sfc_u, *sfc_v, *storm_u, *storm_v;   // per column, in the inputs' dtype (each may be null)
+    double bottom;
+    double top[SRH_MAX_DEPTHS];                       // bottom + depth
+    int ndepth;
+    void *pos[SRH_MAX_DEPTHS], *neg[SRH_MAX_DEPTHS], *tot[SRH_MAX_DEPTHS];
+    int32_t *status;
+};
+
+// the running helicity of one depth: the storm-relative wind of the last point and the two sums
+struct SrhSum {
+    double ul, vl, pos, neg;
+    bool started, top_hit, spanned, fin;
+    XP_DEV void init() { ul = vl = qnan(); pos = neg = 0.0; started = top_hit = spanned = fin = false; }
+    XP_DEV void emit(double u, double v) {          // storm-relative wind of the next point
+#pragma clang fp contract(off)
+        if (started) {
+            const double t = u * vl - ul * v;
+            if (t > 0.0) pos += t;
+            if (t < 0.0) neg += t;
+        }
+        started = true; ul = u; vl = v;
+    }
+};
+
+template <typename T> __global__ __launch_bounds__(256)
+void k_storm_relative_helicity(SrhArgs a) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.ncol) return;
+    constexpr int f64 = sizeof(T) == 8;
+    const double cu = a.storm_u ? ld1<T>(a.storm_u, c) : 0.0, cv = a.storm_v ? ld1<T>(a.storm_v, c) : 0.0;
+    const double b = a.bottom;
+    SrhSum s[SRH_MAX_DEPTHS];
+#pragma unroll
+    for (int i = 0; i < SRH_MAX_DEPTHS; ++i) { s[i].init(); s[i].fin = i >= a.ndepth; }
+    // the walk: the surface point (k = -1) if given, then the levels; h relative to the first valid point without it
+    const bool sfc = a.sfc_u != nullptr;
+    double hp = qnan(), up = qnan(), vp = qnan(), h0 = sfc ? 0.0 : qnan();
+    bool has_prev = false, bottom_ok = false, bottom_hit = false, bottom_done = false, done = false;
+    int bad = 0;
+    for (int64_t k = sfc ? -1 : 0; k < a.nlev; ++k) {
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+        if (done) continue;
+        double h, u, v;
+        if (k < 0) { h = 0.0; u = ld1<T>(a.sfc_u, c); v = ld1<T>(a.sfc_v, c); }
+        else { h = ld<T>(a.z, k, c); u = ld<T>(a.u, k, c); v = ld<T>(a.v, k, c); }
+        if (isnan_(h) || isnan_(u) || isnan_(v)) continue;                  // missing level: dropped
+        if (isnan_(h0)) h0 = h;
+        h = h - h0;
+        if (has_prev && !(h > hp)) { bad = ST_BAD_HEIGHT; done = true; continue; }
+        if (!has_prev) bottom_ok = b >= h;                                  // the bottom lies on or above the lowest point
+        u = u - cu; v = v - cv;
+        const bool above_b = h >= b || isclose_(h, b);
+        // the bottom point, where no level equals it: between the level below and this one, in order
+        bool add_b = false;
+        double ub = qnan(), vb = qnan();
+        if (!bottom_done && h >= b) {
+            bottom_done = true;
+            bottom_hit = h == b;
+            if (!bottom_hit && has_prev) {
+                add_b = true;
+                const double f = (b - hp) / (h - hp);
+                ub = up + f * (u - up); vb = vp + f * (v - vp);
+            }
+        }
+        bool all_fin = true;
+#pragma unroll
+        for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
+            SrhSum &r = s[i];
+            if (r.fin) continue;
+            const double t = a.top[i];
+            if (add_b) r.emit(ub, vb);
+            const bool below_t = h <= t || isclose_(h, t);
+            if (h >= t) r.spanned = true;
+            // the top point, where no level equals it: before the first level above it
+            if (h > t && !r.top_hit) {
+                r.top_hit = true;
+                if (has_prev) {
+                    const double f = (t - hp) / (h - hp);
+                    r.emit(up + f * (u - up), vp + f * (v - vp));
+                }
+            }
+            if (above_b && below_t) {
+                r.emit(u, v);
+                r.top_hit = r.top_hit || h == t;
+            }
+            if (!below_t) r.fin = true;
+            all_fin = all_fin && r.fin;
+        }
+        done = all_fin;
+        hp = h; up = u; vp = v; has_prev = true;
+    }
+    int status = bad;
+#pragma unroll
+    for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
+        if (i >= a.ndepth) continue;
+        const bool ok = !bad && bottom_ok && s[i].spanned && !isnan_(cu) && !isnan_(cv);
+        if (!bad && !(bottom_ok && s[i].spanned)) status |= ST_NO_LAYER;
+        const double pos = ok ? s[i].pos : qnan(), neg = ok ? s[i].neg : qnan();
+        st(a.pos[i], f64, c, pos); st(a.neg[i], f64, c, neg); st(a.tot[i], f64, c, pos + neg);
+    }
+    sti(a.status, c, status);
+}
+
+// ---- composites ---------------------------------------------------------------------------------------------------------
+// metpy.calc.significant_tornado; comparisons with NaN are false, so NaN propagates through the clips
+XP_DEV double stp_value(double sbcape, double lcl_height, double srh, double shear) {
+#pragma clang fp contract(off)
+    double lcl = lcl_height < 1000.0 ? 1000.0 : (lcl_height > 2000.0 ? 2000.0 : lcl_height);
+    lcl = (2000.0 - lcl) / 1000.0;
+    double shr = shear < 12.5 ? 0.0 : (shear > 30.0 ? 30.0 : shear);
+    shr = shr / 20.0;
+    return (sbcape * lcl * srh * shr) / (1500.0 * 150.0);
+}
+// metpy.calc.supercell_composite
+XP_DEV double scp_value(double mucape, double srh, double shear) {
+#pragma clang fp contract(off)
+    double shr = shear < 10.0 ? 0.0 : (shear > 20.0 ? 20.0 : shear);
+    shr = shr / 20.0;
+    return (mucape / 1000.0) * (srh / 50.0) * shr;
+}
+template <typename T> __global__ __launch_bounds__(256)
+void k_significant_tornado(int64_t n, const void *sbcape, const void *lcl_height, const void *srh, const void *shear, void *out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    st(out, sizeof(T) == 8, c, stp_value(ld1<T>(sbcape, c), ld1<T>(lcl_height, c), ld1<T>(srh, c), ld1<T>(shear, c)));
+}
+template <typename T> __global__ __launch_bounds__(256)
+void k_supercell_composite(int64_t n, const void *mucape, const void *srh, const void *shear, void *out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    st(out, sizeof(T) == 8, c, scp_value(ld1<T>(mucape, c), ld1<T>(srh, c), ld1<T>(shear, c)));
+}
+
+}  // namespace xp

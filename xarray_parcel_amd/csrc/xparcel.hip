@@ -16,6 +16,7 @@
 #include "xp_multi.hpp"
 #include "xp_bundle.hpp"
 #include "xp_dcape.hpp"
+#include "xp_kinematics.hpp"
 
 namespace {
 
@@ -986,6 +987,97 @@ int xp_downdraft_cape(const xp_view *p, const xp_view *t, const xp_view *td, dou
     a.bottom = layer_bottom; a.top = layer_bottom - layer_depth;
     a.table_mode = tm; a.tb = ts.tb; a.es_tab = ts.es;
     by_dtype(p->dtype, [&](auto z) { launch(xp::k_downdraft_cape<decltype(z)>, p->ncol, st, a); });
+    return st.finish();
+}
+
+int xp_bunkers_storm_motion(const xp_view *p, const xp_view *u, const xp_view *v, const xp_view *z, xp_storm_motion_out *out,
+                            void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {u, "u"}, {v, "v"}, {z, "height"}}))) return rc;
+    if (!out) return fail(XP_E_ARG, "xp_bunkers_storm_motion: out: null");
+    if (out->dtype != p->dtype || out->mem != p->mem) return fail(XP_E_ARG, "xp_bunkers_storm_motion: out: dtype / mem differ from the views'");
+    const size_t cb = rows_bytes(p, 1);
+    xp::StormMotionArgs a;
+    memset(&a, 0, sizeof(a));
+    void *status;
+    if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
+        (rc = stage_view(st, z, &a.z)) || (rc = st.out(out->right_u, cb, out->mem, &a.right_u)) ||
+        (rc = st.out(out->right_v, cb, out->mem, &a.right_v)) || (rc = st.out(out->left_u, cb, out->mem, &a.left_u)) ||
+        (rc = st.out(out->left_v, cb, out->mem, &a.left_v)) || (rc = st.out(out->mean_u, cb, out->mem, &a.mean_u)) ||
+        (rc = st.out(out->mean_v, cb, out->mem, &a.mean_v)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &status))) return rc;
+    a.status = (int32_t *)status;
+    a.nlev = p->nlev; a.ncol = p->ncol;
+    by_dtype(p->dtype, [&](auto t) { launch(xp::k_bunkers_storm_motion<decltype(t)>, p->ncol, st, a); });
+    return st.finish();
+}
+
+int xp_storm_relative_helicity(const xp_view *z, const xp_view *u, const xp_view *v, const void *surface_u,
+                               const void *surface_v, const void *storm_u, const void *storm_v, double bottom,
+                               int32_t ndepth, const double *depth, xp_srh_out *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{z, "height"}, {u, "u"}, {v, "v"}}))) return rc;
+    if (!out) return fail(XP_E_ARG, "xp_storm_relative_helicity: out: null");
+    if (out->dtype != z->dtype || out->mem != z->mem) return fail(XP_E_ARG, "xp_storm_relative_helicity: out: dtype / mem differ from the views'");
+    if (ndepth < 1 || ndepth > xp::SRH_MAX_DEPTHS) return fail(XP_E_ARG, "xp_storm_relative_helicity: ndepth must lie in 1 ... 4, got %d", (int)ndepth);
+    if (!depth) return fail(XP_E_ARG, "xp_storm_relative_helicity: depth: null");
+    for (int i = 0; i < ndepth; ++i)
+        if (!(std::isfinite(depth[i]) && depth[i] > 0.0))
+            return fail(XP_E_ARG, "xp_storm_relative_helicity: depth[%d] must be finite and positive", i);
+    if (!(std::isfinite(bottom) && bottom >= 0.0)) return fail(XP_E_ARG, "xp_storm_relative_helicity: bottom must be finite and >= 0");
+    if (!surface_u != !surface_v) return fail(XP_E_ARG, "xp_storm_relative_helicity: surface wind: give both components or neither");
+    const size_t cb = rows_bytes(z, 1);
+    xp::SrhArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = stage_view(st, z, &a.z)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
+        (rc = st.in(surface_u, cb, z->mem, &a.sfc_u)) || (rc = st.in(surface_v, cb, z->mem, &a.sfc_v)) ||
+        (rc = st.in(storm_u, cb, z->mem, &a.storm_u)) || (rc = st.in(storm_v, cb, z->mem, &a.storm_v))) return rc;
+    for (int i = 0; i < ndepth; ++i) {
+        a.top[i] = bottom + depth[i];
+        if ((rc = st.out(out->positive[i], cb, out->mem, &a.pos[i])) || (rc = st.out(out->negative[i], cb, out->mem, &a.neg[i])) ||
+            (rc = st.out(out->total[i], cb, out->mem, &a.tot[i]))) return rc;
+    }
+    void *status;
+    if ((rc = st.out(out->status, (size_t)z->ncol * 4, out->mem, &status))) return rc;
+    a.status = (int32_t *)status;
+    a.nlev = z->nlev; a.ncol = z->ncol; a.bottom = bottom; a.ndepth = ndepth;
+    by_dtype(z->dtype, [&](auto t) { launch(xp::k_storm_relative_helicity<decltype(t)>, z->ncol, st, a); });
+    return st.finish();
+}
+
+int xp_significant_tornado(int64_t n, int32_t dtype, int32_t mem, const void *sbcape, const void *lcl_height, const void *srh,
+                           const void *shear, void *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_significant_tornado: bad n / dtype");
+    if (!sbcape || !lcl_height || !srh || !shear || !out) return fail(XP_E_ARG, "xp_significant_tornado: null argument");
+    const size_t b = (size_t)n * esize(dtype);
+    const void *src[4] = {sbcape, lcl_height, srh, shear}, *in[4];
+    void *od;
+    int rc;
+    for (int i = 0; i < 4; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
+    if ((rc = st.out(out, b, mem, &od))) return rc;
+    by_dtype(dtype, [&](auto z) { launch(xp::k_significant_tornado<decltype(z)>, n, st, n, in[0], in[1], in[2], in[3], od); });
+    return st.finish();
+}
+
+int xp_supercell_composite(int64_t n, int32_t dtype, int32_t mem, const void *mucape, const void *srh, const void *shear,
+                           void *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_supercell_composite: bad n / dtype");
+    if (!mucape || !srh || !shear || !out) return fail(XP_E_ARG, "xp_supercell_composite: null argument");
+    const size_t b = (size_t)n * esize(dtype);
+    const void *src[3] = {mucape, srh, shear}, *in[3];
+    void *od;
+    int rc;
+    for (int i = 0; i < 3; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
+    if ((rc = st.out(out, b, mem, &od))) return rc;
+    by_dtype(dtype, [&](auto z) { launch(xp::k_supercell_composite<decltype(z)>, n, st, n, in[0], in[1], in[2], od); });
     return st.finish();
 }
 

@@ -1,0 +1,76 @@
+"""
+Storm motion, helicity and the composites on DataArrays: metpy.calc.bunkers_storm_motion, storm_relative_helicity,
+significant_tornado and supercell_composite for every column (or point) of a grid, through libxparcel
+(numpy_api.bunkers_storm_motion, ...).  The reference has no counterparts, so this lives next to the mirror
+(parcel_functions.py) rather than in it, and is built from the mirror's plumbing: a _Grid splits the inputs and wraps
+the results, _device turns library errors into the mirror's.
+"""
+import numpy as np
+
+from . import numpy_api as _api
+from ._xr import DataArray, Dataset
+from .parcel_functions import VERT, _Grid, _device, _host
+
+_WIND = 'm s$^{-1}$'
+_SRH = 'm$^{2}$ s$^{-2}$'
+_ATTRS = {
+    'bunkers_right_u': {'long_name': 'Bunkers right-mover storm motion, u component', 'units': _WIND},
+    'bunkers_right_v': {'long_name': 'Bunkers right-mover storm motion, v component', 'units': _WIND},
+    'bunkers_left_u': {'long_name': 'Bunkers left-mover storm motion, u component', 'units': _WIND},
+    'bunkers_left_v': {'long_name': 'Bunkers left-mover storm motion, v component', 'units': _WIND},
+    'mean_wind_u': {'long_name': 'Pressure-weighted 0-6 km mean wind, u component', 'units': _WIND},
+    'mean_wind_v': {'long_name': 'Pressure-weighted 0-6 km mean wind, v component', 'units': _WIND},
+    'positive_srh': {'long_name': 'Positive storm-relative helicity', 'units': _SRH},
+    'negative_srh': {'long_name': 'Negative storm-relative helicity', 'units': _SRH},
+    'total_srh': {'long_name': 'Storm-relative helicity', 'units': _SRH},
+    'significant_tornado': {'long_name': 'Significant tornado parameter', 'units': '1'},
+    'supercell_composite': {'long_name': 'Supercell composite parameter', 'units': '1'},
+}
+_BUNKERS = {'right_u': 'bunkers_right_u', 'right_v': 'bunkers_right_v', 'left_u': 'bunkers_left_u',
+            'left_v': 'bunkers_left_v', 'mean_u': 'mean_wind_u', 'mean_v': 'mean_wind_v'}
+_SRH_NAMES = {'positive': 'positive_srh', 'negative': 'negative_srh', 'total': 'total_srh'}
+
+
+def _per_col(g, x):
+    return x if x is None or np.ndim(x) == 0 else g.values(x)
+
+
+def bunkers_storm_motion(pressure, u, v, height, vert_dim=VERT):
+    """Bunkers right- and left-mover storm motion and the 0-6 km pressure-weighted mean wind of every column, from
+    pressure [hPa], u, v [m/s] and height [m] on one vertical (pressure on the wind levels).  Returns a Dataset on the
+    horizontal dims; columns that do not reach 6 km above their lowest level (MetPy raises) are NaN."""
+    g = _Grid(pressure, vert_dim)
+    res = _device(_api.bunkers_storm_motion, g.values(pressure), g.values(u), g.values(v), g.values(height))
+    return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _BUNKERS.items()})
+
+
+def storm_relative_helicity(height, u, v, depth, vert_dim=VERT, bottom=0.0, storm_u=0.0, storm_v=0.0, surface_u=None,
+                            surface_v=None):
+    """Positive, negative and total storm-relative helicity [m^2/s^2] of every column from `bottom` up `depth` metres
+    above the lowest level (or, with surface_u / surface_v, above the surface, height being the height above it).
+    storm_u / storm_v: scalars or DataArrays on the horizontal dims (e.g. bunkers_storm_motion's bunkers_right_u).  A
+    sequence of up to four depths, computed in one pass, adds the leading dim 'srh_depth'.  Depths that the column does
+    not span are NaN."""
+    g = _Grid(height, vert_dim)
+    res = _device(_api.storm_relative_helicity, g.values(height), g.values(u), g.values(v), depth, bottom=bottom,
+                  storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), surface_u=_per_col(g, surface_u),
+                  surface_v=_per_col(g, surface_v))
+    if np.ndim(depth) == 0:
+        return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _SRH_NAMES.items()})
+    coords = dict(g.coords, srh_depth=np.asarray(depth, dtype=np.float64))
+    return Dataset({name: DataArray(_host(res[k]), dims=('srh_depth',) + g.dims, coords=coords, attrs=dict(_ATTRS[name]),
+                                    name=name) for k, name in _SRH_NAMES.items()})
+
+
+def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):
+    """Significant tornado parameter per point: sbcape [J/kg], LCL height [m], 0-1 km SRH [m^2/s^2], 0-6 km shear [m/s]."""
+    g = _Grid(sbcape, None)
+    out = _device(_api.significant_tornado, *(g.values(x) for x in (sbcape, lcl_height, storm_helicity_1km, shear_6km)))
+    return g.horiz(out, 'significant_tornado', _ATTRS['significant_tornado'])
+
+
+def supercell_composite(mucape, effective_storm_helicity, effective_shear):
+    """Supercell composite parameter per point: mucape [J/kg], SRH [m^2/s^2], shear [m/s]."""
+    g = _Grid(mucape, None)
+    out = _device(_api.supercell_composite, *(g.values(x) for x in (mucape, effective_storm_helicity, effective_shear)))
+    return g.horiz(out, 'supercell_composite', _ATTRS['supercell_composite'])

@@ -710,6 +710,69 @@ def significant_hail_parameter(mucape, mixing_ratio, lapse, temp_500, shear, flh
     return out
 
 
+def bunkers_storm_motion(pressure, u, v, height):
+    """metpy.calc.bunkers_storm_motion for every column (xp_bunkers_storm_motion): pressure [hPa], u, v [m/s] and height
+    [m] on one vertical, (nlev, ...).  Returns a dict of per-column 'right_u', 'right_v', 'left_u', 'left_v', 'mean_u',
+    'mean_v' [m/s] and 'status' (XP_ST_NO_LAYER: the column does not reach 6 km above its lowest level; ST_BAD_HEIGHT /
+    ST_BAD_PRESSURE: the levels are out of order; everything NaN)."""
+    c = _Call(pressure, u, v, height)
+    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, u, v, height must share a shape'
+    res = {k: c.out(c.hshape, np.int32 if k == 'status' else None) for k in L.STORM_MOTION_OUT}
+    out = L.StormMotionOut(dtype=c.xp_dtype, mem=c.mem)
+    for k, a in res.items():
+        setattr(out, k, _ptr(a))
+    c.run('xp_bunkers_storm_motion', *map(c.view, c.ins), out)
+    return res
+
+
+def storm_relative_helicity(height, u, v, depth, bottom=0.0, storm_u=0.0, storm_v=0.0, surface_u=None, surface_v=None):
+    """metpy.calc.storm_relative_helicity for every column (xp_storm_relative_helicity): height [m], u, v [m/s] (nlev, ...);
+    heights are taken relative to the lowest valid level, or, with surface_u / surface_v, as heights above the surface
+    with the surface wind as the point at 0 m.  `depth` [m]: a scalar, or a sequence of up to four depths computed in one
+    pass (the outputs then gain a leading axis, one entry per depth); the layer runs from `bottom` to bottom + depth.
+    storm_u, storm_v, surface_u, surface_v: scalars or one value per column.  With CUDA-tensor inputs the outputs of
+    bunkers_storm_motion can be passed straight back as the storm motion (e.g. storm_u=bm['right_u']).  Returns a dict of
+    'positive', 'negative', 'total' [m^2/s^2] and 'status' (XP_ST_NO_LAYER: some depth is not spanned, its values NaN;
+    ST_BAD_HEIGHT: heights out of order, everything NaN)."""
+    many = np.ndim(depth) > 0
+    depths = [float(d) for d in np.atleast_1d(depth)]
+    assert 1 <= len(depths) <= L.SRH_MAX_DEPTHS, 'depth: one to four depths'
+    assert (surface_u is None) == (surface_v is None), 'surface_u, surface_v: give both or neither'
+    per = [x for x in (storm_u, storm_v, surface_u, surface_v) if _is_torch(x)]     # (CUDA tensors decide the device)
+    c = _Call(height, u, v, *per)
+    z, wu, wv = c.ins[:3]
+    assert z.shape == wu.shape == wv.shape, 'height, u, v must share a shape'
+    sfc = [None, None] if surface_u is None else [c.per_col(surface_u), c.per_col(surface_v)]
+    shape = ((len(depths),) if many else ()) + c.hshape
+    res = {k: c.out(shape) for k in L.SRH_OUT}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = L.SrhOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in L.SRH_OUT:
+        arr = getattr(out, k)
+        for i in range(len(depths)):
+            arr[i] = _ptr(res[k][i] if many else res[k])
+    c.run('xp_storm_relative_helicity', c.view(z), c.view(wu), c.view(wv), *sfc, c.per_col(storm_u), c.per_col(storm_v),
+          float(bottom), len(depths), (C.c_double * len(depths))(*depths), out)
+    return res
+
+
+def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):
+    """metpy.calc.significant_tornado per point (xp_significant_tornado): sbcape [J/kg], LCL height [m], 0-1 km SRH
+    [m^2/s^2], 0-6 km bulk shear [m/s]."""
+    c = _Call(sbcape, lcl_height, storm_helicity_1km, shear_6km)
+    out = c.out(c.ins[0].shape)
+    c.run('xp_significant_tornado', _flat(c.ins), c.xp_dtype, c.mem, *c.ins, out)
+    return out
+
+
+def supercell_composite(mucape, effective_storm_helicity, effective_shear):
+    """metpy.calc.supercell_composite per point (xp_supercell_composite): mucape [J/kg], SRH [m^2/s^2], shear [m/s]."""
+    c = _Call(mucape, effective_storm_helicity, effective_shear)
+    out = c.out(c.ins[0].shape)
+    c.run('xp_supercell_composite', _flat(c.ins), c.xp_dtype, c.mem, *c.ins, out)
+    return out
+
+
 def conv_properties(dat, ignore_nans=False, moist=None):
     """pf.py:1951: the reference's convective-property bundle for a grid, ONE library call (xp_conv_properties): the
     q -> dewpoint step, the NaN mask, the fixed-level interpolations and the freezing / melting levels are one pass over
