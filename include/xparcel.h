@@ -103,8 +103,10 @@ enum {
     XP_ST_NO_LAYER = 16,        /* xp_downdraft_cape, xp_bunkers_storm_motion: the column does not span the layer (MetPy
                                    raises), every output NaN; xp_storm_relative_helicity: some depth is not spanned, that
                                    depth's outputs NaN */
-    XP_ST_BAD_HEIGHT = 32       /* xp_bunkers_storm_motion, xp_storm_relative_helicity: a height not above the valid level
+    XP_ST_BAD_HEIGHT = 32,      /* xp_bunkers_storm_motion, xp_storm_relative_helicity: a height not above the valid level
                                    below it (heights must increase strictly); every output NaN */
+    XP_ST_LAYER_OPEN = 64       /* xp_effective_inflow_layer: the last candidate of the search window passes, i.e.
+                                   search_depth (or the column top) cut the layer, which might extend further */
 };
 
 typedef struct {
@@ -284,6 +286,39 @@ typedef struct {
 int xp_downdraft_cape(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint,
                       double layer_bottom, double layer_depth, int32_t moist_mode, xp_dcape_out *out, void *stream);
 
+/* The effective inflow layer of Thompson et al. (2007; the reference and MetPy 1.4 have no counterpart): the lowest
+   contiguous run of levels whose lifted parcels have CAPE >= cape_min (100 J/kg) and CIN >= cin_min (-250 J/kg; CIN is
+   <= 0 in this library).  `height` (same shape, dtype and mem as the other views) may be NULL.
+   A level is VALID when p, T and Td are all non-NaN.  With p0 the pressure of the lowest valid level, the CANDIDATES are
+   the valid levels with p >= p0 - search_depth (plain comparison; 300 hPa is the library's most-unstable default), in
+   level order.  Invalid levels are skipped: they neither start, extend nor close the layer.
+   Candidate k is lifted exactly as xp_cape_cin lifts the surface parcel of the column cut off below k:
+       CAPE_k, CIN_k = xp_cape_cin(XP_PARCEL_SURFACE) on the views p[k:], T[k:], Td[k:] with the same options,
+   NaN handling above k included, and passes when CAPE_k >= cape_min && CIN_k >= cin_min.  A candidate without a level
+   above it is lifted like any other (a one-level view: CAPE 0).
+   base = the first passing candidate; top = the last passing candidate before the first failing candidate above base, or
+   the last candidate if none fails.  Candidates above the first failure after base are not lifted.
+   base_height / top_height: the height of that level MINUS the height of the lowest valid level (a surface-based layer has
+   base_height == 0.0 exactly; NaN without `height`) -- the height convention of xp_storm_relative_helicity_layers.
+   base_index / top_index: level indices, -1 = none.  candidate_cape / candidate_cin: dense C-order (nlev, ncol), what was
+   computed for every level that was lifted -- bit for bit what xp_cape_cin writes for that view -- and NaN elsewhere.
+   status: XP_ST_NO_LAYER when no candidate passes (floats NaN, indices -1); XP_ST_LAYER_OPEN when the last candidate of the
+   window passes; XP_ST_LCL_NOT_CONVERGED ORed over the candidates lifted; XP_ST_BAD_PRESSURE as in xp_cape_cin (ORed likewise).
+   opts: the four CAPE / CIN options and moist_mode (XP_MOIST_EXACT, XP_MOIST_TABLE; XP_MOIST_FAMILY is treated as exact);
+   humidity must be XP_HUM_DEWPOINT.  Non-finite thresholds, search_depth <= 0 or not finite, mismatched views and
+   XP_HUM_SPECIFIC return XP_E_ARG.  Every output may be NULL; the outputs share the views' dtype and mem.  Strided device
+   views are read in place. */
+typedef struct {
+    void *base_pressure, *top_pressure;   /* hPa, ncol: the pressures of the levels base_index / top_index */
+    void *base_height, *top_height;       /* m above the lowest valid level, ncol */
+    int32_t *base_index, *top_index, *status;
+    void *candidate_cape, *candidate_cin; /* J/kg, dense C-order (nlev, ncol), NaN where the level was not lifted */
+    int32_t dtype, mem;
+} xp_effective_layer_out;
+int xp_effective_inflow_layer(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint,
+                              const xp_view *height, double cape_min, double cin_min, double search_depth,
+                              const xp_opts *opts, xp_effective_layer_out *out, void *stream);
+
 /* pf.py:1758-1811 linear_interp / pf.py:1813-1828 log_interp: value of `variable` at coordinate `at` (one value per
    column, or a single value for all when at_is_scalar) between the bracketing levels of `coords`; duplicates of a
    bracketing coordinate are averaged, no extrapolation (NaN).  log_coords != 0 interpolates in ln(coords), ln(at).
@@ -408,6 +443,27 @@ typedef struct {
 int xp_storm_relative_helicity(const xp_view *height, const xp_view *u, const xp_view *v, const void *surface_u,
                                const void *surface_v, const void *storm_u, const void *storm_v, double bottom,
                                int32_t ndepth, const double *depth, xp_srh_out *out, void *stream);
+
+/* Helicity and bulk wind difference between PER-COLUMN bounds: 1 ... 4 layers that share a bottom, one upward pass.  Views,
+   surface wind and storm motion as in xp_storm_relative_helicity; bottom and top[i] are ncol values each (the views' dtype
+   and mem) in that function's own height convention -- above the lowest valid level, or as given when surface winds are
+   passed: what xp_effective_inflow_layer writes to base_height / top_height.  Point selection, the linear-in-height
+   interpolation, the `in`-not-isclose rule for added bound points, the term and the sign-filtered sums are those of
+   xp_storm_relative_helicity with bottom[c], top[i][c] in place of bottom, bottom + depth[i]: with constant arrays the
+   helicity outputs are bit-identical to it.  shear_u[i] / shear_v[i] = the ground-relative wind at top[i][c] minus the wind
+   at bottom[c], each linear in HEIGHT between the levels on either side (a level exactly on the bound gives its own wind):
+   the rule of xp_wind_shear, NOT MetPy's bulk_shear, which interpolates in ln p.  A NaN bound, top <= bottom, bottom < 0 or
+   a layer the column does not span gives NaN for that layer and XP_ST_NO_LAYER; XP_ST_BAD_HEIGHT as above.  A NaN storm
+   motion gives NaN helicity (the shear does not depend on it). */
+typedef struct {
+    void *positive[4], *negative[4], *total[4];   /* m^2/s^2, ncol each, per layer (entries past nlayer unused) */
+    void *shear_u[4], *shear_v[4];                /* m/s, ncol each, per layer */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_HEIGHT */
+    int32_t dtype, mem;
+} xp_srh_layers_out;
+int xp_storm_relative_helicity_layers(const xp_view *height, const xp_view *u, const xp_view *v, const void *surface_u,
+                                      const void *surface_v, const void *storm_u, const void *storm_v, const void *bottom,
+                                      int32_t nlayer, const void *const *top, xp_srh_layers_out *out, void *stream);
 
 /* metpy.calc.significant_tornado, per point in MetPy's operation order (NaN propagates):
    lcl_term = (2000 - clip(lcl_height, 1000, 2000)) / 1000; shr = (shear < 12.5 ? 0 : min(shear, 30)) / 20;

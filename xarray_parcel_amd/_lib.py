@@ -22,12 +22,12 @@ ST_TOP_NAN, ST_LCL_NOT_CONVERGED, ST_NAN_PRESSURE, ST_BAD_PRESSURE = 1, 2, 4, 8
 # every symbol include/xparcel.h declares
 SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_family_table', 'xp_set_family_table', 'xp_cape_cin', 'xp_cape_cin_multi', 'xp_lcl', 'xp_dry_lapse',
            'xp_moist_lapse', 'xp_parcel_profile', 'xp_lfc_el', 'xp_cape_cin_base', 'xp_select_parcel',
-           'xp_mixed_layer', 'xp_wet_bulb_temperature', 'xp_downdraft_cape', 'xp_interp_level', 'xp_interp_levels',
+           'xp_mixed_layer', 'xp_wet_bulb_temperature', 'xp_downdraft_cape', 'xp_effective_inflow_layer', 'xp_interp_level', 'xp_interp_levels',
            'xp_dewpoint_from_specific_humidity',
            'xp_crossing_level', 'xp_mixing_ratio', 'xp_conv_properties', 'xp_insert_level', 'xp_find_intersections', 'xp_trapz',
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
-           'xp_storm_relative_helicity', 'xp_significant_tornado', 'xp_supercell_composite',
+           'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
            'xp_last_error')
 
 
@@ -123,6 +123,28 @@ class SrhOut(C.Structure):
                 [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
 
 
+# xp_effective_inflow_layer: its outputs (per column; the last two dense (nlev, ncol)), and the status bit of a layer that
+# the search window cut
+ST_LAYER_OPEN = 64
+EFFECTIVE_F = ('base_pressure', 'top_pressure', 'base_height', 'top_height')
+EFFECTIVE_I = ('base_index', 'top_index', 'status')
+EFFECTIVE_CANDIDATES = ('candidate_cape', 'candidate_cin')
+
+
+class EffectiveLayerOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in EFFECTIVE_F + EFFECTIVE_I + EFFECTIVE_CANDIDATES] +
+                [('dtype', C.c_int32), ('mem', C.c_int32)])
+
+
+# xp_storm_relative_helicity_layers: per layer (up to SRH_MAX_DEPTHS) the helicity sums and the bulk wind difference
+SRH_LAYERS_OUT = SRH_OUT + ('shear_u', 'shear_v')
+
+
+class SrhLayersOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p * SRH_MAX_DEPTHS) for k in SRH_LAYERS_OUT] +
+                [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
+
+
 class Tables(C.Structure):
     _fields_ = [('n_pressure', C.c_int64), ('n_temperature', C.c_int64), ('n_adiabat', C.c_int64),
                 ('p_max', C.c_double), ('p_step', C.c_double), ('t_min', C.c_double), ('t_step', C.c_double),
@@ -155,6 +177,7 @@ ARGTYPES = {
     'xp_mixed_layer': (_V, _V, _f64, _ptr, _ptr),
     'xp_wet_bulb_temperature': (_V, _V, _V, _i32, _ptr, _ptr),
     'xp_downdraft_cape': (_V, _V, _V, _f64, _f64, _i32, C.POINTER(DcapeOut), _ptr),
+    'xp_effective_inflow_layer': (_V, _V, _V, _V, _f64, _f64, _f64, _O, C.POINTER(EffectiveLayerOut), _ptr),
     'xp_interp_level': (_V, _V, _ptr, _i32, _i32, _ptr, _ptr),
     'xp_interp_levels': (_V, _i32, C.POINTER(_V), _i32, _ptr, _i32, C.POINTER(_ptr), _ptr),
     'xp_dewpoint_from_specific_humidity': (_V, _V, _V, _ptr, _ptr),
@@ -175,6 +198,8 @@ ARGTYPES = {
     'xp_storm_proxies': (_i64, _i32, _i32, C.POINTER(ProxiesIn), C.POINTER(ProxiesOut), _ptr),
     'xp_bunkers_storm_motion': (_V, _V, _V, _V, C.POINTER(StormMotionOut), _ptr),
     'xp_storm_relative_helicity': (_V, _V, _V, _ptr, _ptr, _ptr, _ptr, _f64, _i32, _ptr, C.POINTER(SrhOut), _ptr),
+    'xp_storm_relative_helicity_layers': (_V, _V, _V, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, C.POINTER(_ptr),
+                                          C.POINTER(SrhLayersOut), _ptr),
     'xp_significant_tornado': (_i64, _i32, _i32) + (_ptr,) * 6,
     'xp_supercell_composite': (_i64, _i32, _i32) + (_ptr,) * 5,
     'xp_last_error': (),
@@ -209,7 +234,10 @@ MULTI_FLAGS = {2: ['-DXP_CAPE_THREADS=512', '-DXP_SLOT_FIELDS=12', '-mllvm', '-d
 for _m in list(MULTI_FLAGS):
     if os.environ.get(f'XP_MULTI_FLAGS_{_m}') is not None:
         MULTI_FLAGS[_m] = os.environ[f'XP_MULTI_FLAGS_{_m}'].split()
-UNITS = [('xparcel', 'xparcel.hip', [])] + [
+# The effective-inflow-layer kernel (csrc/xp_effective.hpp): its LCL iteration sits inside the candidate loop, and with
+# machine LICM the fp64 constants of both loops are kept in registers through every ascent (160+ VGPRs instead of 106-112).
+EFFECTIVE_FLAGS = ['-mllvm', '-disable-machine-licm']
+UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS)] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

@@ -403,7 +403,7 @@ struct Lcl { double p, t, tv; int not_converged; };
 // Library-math spelling (IEEE division, device-library exp/log/pow, the oracle's operation order): used for
 // parcels outside the physically sane box, where the fixed point may diverge or leave the domain of log/pow and the
 // outcome (NaN / not converged) has to follow IEEE semantics as on the CPU.  Out of line: rare.
-__device__ __attribute__((noinline)) Lcl lcl_reference(double p_start, double t, double td) {
+XP_DEV Lcl lcl_reference_body(double p_start, double t, double td) {
     Lcl r; r.not_converged = 0;
     double es_td = es_ref(td);
     double w = EPS * es_td / (p_start - es_td);
@@ -428,7 +428,10 @@ __device__ __attribute__((noinline)) Lcl lcl_reference(double p_start, double t,
     r.tv = virt_ref(r.t, r.t, p);
     return r;
 }
-XP_DEV Lcl lcl(double p_start, double t, double td) {
+__device__ __attribute__((noinline)) Lcl lcl_reference(double p_start, double t, double td) { return lcl_reference_body(p_start, t, td); }
+// FLAT: the library-math path inline instead of out of line, for a kernel that must not carry a callee's stack frame
+// (lcl_reference saves a callee-saved VGPR: 8 B of scratch per lane in every kernel that calls it)
+template <bool FLAT = false> XP_DEV Lcl lcl(double p_start, double t, double td) {
     Lcl r;
     r.not_converged = 0;
     if (isnan_(p_start) || isnan_(t) || isnan_(td)) { r.p = r.t = r.tv = qnan(); return r; }   // pf.py:627-634, 680
@@ -456,7 +459,7 @@ XP_DEV Lcl lcl(double p_start, double t, double td) {
     // of T_lcl - T there is rounding noise of exactly those expressions (see the on-LCL handling in k_cape_cin)
     r.tv = virt(r.t, mix_of_e(sat_vapor_pressure(r.t), p));
     bool ref_path = !sane || (p == p_start);
-    if (__builtin_amdgcn_ballot_w64(ref_path) != 0ull && ref_path) r = lcl_reference(p_start, t, td);
+    if (__builtin_amdgcn_ballot_w64(ref_path) != 0ull && ref_path) r = FLAT ? lcl_reference_body(p_start, t, td) : lcl_reference(p_start, t, td);
     return r;
 }
 

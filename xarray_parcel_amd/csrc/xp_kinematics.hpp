@@ -1,6 +1,8 @@
 // xp_kinematics.hpp -- storm motion, helicity and the composites built on them (MetPy 1.4; the reference has none):
 //   k_bunkers_storm_motion     metpy.calc.bunkers_storm_motion, one thread per column;
 //   k_storm_relative_helicity  metpy.calc.storm_relative_helicity for up to four depths, one thread per column;
+//   k_helicity_layers          the same between per-column bounds (up to four tops sharing a bottom), plus the bulk wind
+//                              difference over each layer;
 //   k_significant_tornado, k_supercell_composite   per point, in MetPy's operation order.
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/kinematics_restatement.py.  Each column kernel
 // makes one upward pass with level-major loads (coalesced when col_stride == 1): the layer points of MetPy's get_layer /
@@ -230,6 +232,128 @@ void k_storm_relative_helicity(SrhArgs a) {
         if (!bad && !(bottom_ok && s[i].spanned)) status |= ST_NO_LAYER;
         const double pos = ok ? s[i].pos : qnan(), neg = ok ? s[i].neg : qnan();
         st(a.pos[i], f64, c, pos); st(a.neg[i], f64, c, neg); st(a.tot[i], f64, c, pos + neg);
+    }
+    sti(a.status, c, status);
+}
+
+// ---- helicity and bulk wind difference over per-column layers -----------------------------------------------------------
+// k_storm_relative_helicity's walk with the bounds read per column: bottom[c] and top[i][c] (in the kernel's own height
+// convention) in place of the scalars, and next to the helicity sums the ground-relative wind at top[i][c] minus the wind at
+// bottom[c], both linear in height between the levels on either side (xp_wind_shear's rule, not MetPy's ln p bulk_shear).
+// A NaN bound, top <= bottom or bottom < 0 leaves that layer out (NaN, XP_ST_NO_LAYER).
+struct SrhLayersArgs {
+    View z, u, v;
+    int64_t nlev, ncol;
+    const void *sfc_u, *sfc_v, *storm_u, *storm_v;   // per column, in the inputs' dtype (each may be null)
+    const void *bottom;                               // per column
+    const void *top[SRH_MAX_DEPTHS];                  // per column and layer
+    int nlayer;
+    void *pos[SRH_MAX_DEPTHS], *neg[SRH_MAX_DEPTHS], *tot[SRH_MAX_DEPTHS], *shu[SRH_MAX_DEPTHS], *shv[SRH_MAX_DEPTHS];
+    int32_t *status;
+};
+
+template <typename T> __global__ __launch_bounds__(256, 4)
+void k_helicity_layers(SrhLayersArgs a) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.ncol) return;
+    constexpr int f64 = sizeof(T) == 8;
+    const double cu = a.storm_u ? ld1<T>(a.storm_u, c) : 0.0, cv = a.storm_v ? ld1<T>(a.storm_v, c) : 0.0;
+    const double b = ld1<T>(a.bottom, c);
+    const bool b_valid = b >= 0.0;                                          // NaN: not valid
+    SrhSum s[SRH_MAX_DEPTHS];
+    double top[SRH_MAX_DEPTHS];
+    bool valid[SRH_MAX_DEPTHS];
+#pragma unroll
+    for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
+        s[i].init();
+        top[i] = i < a.nlayer ? ld1<T>(a.top[i], c) : qnan();
+        valid[i] = i < a.nlayer && b_valid && top[i] > b;
+        s[i].fin = !valid[i];
+    }
+    const bool sfc = a.sfc_u != nullptr;
+    double hp = qnan(), h0 = sfc ? 0.0 : qnan();
+    double gup = qnan(), gvp = qnan();                                      // the previous point's ground-relative wind
+    double bu = qnan(), bv = qnan();                                        // the ground-relative wind at the bottom
+    bool has_prev = false, bottom_ok = false, bottom_hit = false, bottom_done = false;
+    bool done = !(valid[0] || valid[1] || valid[2] || valid[3]);
+    int bad = 0;
+    for (int64_t k = sfc ? -1 : 0; k < a.nlev; ++k) {
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+        if (done) continue;
+        double h, u, v;
+        if (k < 0) { h = 0.0; u = ld1<T>(a.sfc_u, c); v = ld1<T>(a.sfc_v, c); }
+        else { h = ld<T>(a.z, k, c); u = ld<T>(a.u, k, c); v = ld<T>(a.v, k, c); }
+        if (isnan_(h) || isnan_(u) || isnan_(v)) continue;                  // missing level: dropped
+        if (isnan_(h0)) h0 = h;
+        h = h - h0;
+        if (has_prev && !(h > hp)) { bad = ST_BAD_HEIGHT; done = true; continue; }
+        if (!has_prev) bottom_ok = b >= h;                                  // the bottom lies on or above the lowest point
+        const double gu = u, gv = v;                                        // ground-relative: the bulk wind difference
+        u = u - cu; v = v - cv;                                             // storm-relative: the helicity
+        const double up = gup - cu, vp = gvp - cv;                          // (the previous point's, as it was formed then)
+        const bool above_b = h >= b || isclose_(h, b);
+        bool add_b = false;
+        double ub = qnan(), vb = qnan();
+        if (!bottom_done && h >= b) {
+            bottom_done = true;
+            bottom_hit = h == b;
+            if (bottom_hit) { bu = gu; bv = gv; }
+            else if (has_prev) {
+                add_b = true;
+                const double f = (b - hp) / (h - hp);
+                ub = up + f * (u - up); vb = vp + f * (v - vp);
+                bu = gup + f * (gu - gup); bv = gvp + f * (gv - gvp);
+            }
+        }
+        bool all_fin = true;
+#pragma unroll
+        for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
+            SrhSum &r = s[i];
+            if (r.fin) continue;
+            const double t = top[i];
+            if (add_b) r.emit(ub, vb);
+            const bool below_t = h <= t || isclose_(h, t);
+            // the first level at or above the top: the wind there minus the wind at the bottom (known by now: bottom < top)
+            // is stored right away, not carried to the end of the walk; a column that turns out bad overwrites it below
+            if (h >= t && !r.spanned) {
+                double tu = gu, tv = gv;
+                if (h != t) {
+                    const double f = (t - hp) / (h - hp);
+                    tu = gup + f * (gu - gup); tv = gvp + f * (gv - gvp);
+                }
+                int64_t cc = c;                                             // (keeps the eight store addresses from being formed ahead
+                asm volatile("" : "+v"(cc));                                // of the loop and carried -- spilled -- through it)
+                st(a.shu[i], f64, cc, tu - bu); st(a.shv[i], f64, cc, tv - bv);
+            }
+            if (h >= t) r.spanned = true;
+            if (h > t && !r.top_hit) {
+                r.top_hit = true;
+                if (has_prev) {
+                    const double f = (t - hp) / (h - hp);
+                    r.emit(up + f * (u - up), vp + f * (v - vp));
+                }
+            }
+            if (above_b && below_t) {
+                r.emit(u, v);
+                r.top_hit = r.top_hit || h == t;
+            }
+            if (!below_t) r.fin = true;
+            all_fin = all_fin && r.fin;
+        }
+        done = all_fin;
+        hp = h; gup = gu; gvp = gv; has_prev = true;
+    }
+    int status = bad;
+#pragma unroll
+    for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
+        if (i >= a.nlayer) continue;
+        const bool span = valid[i] && bottom_ok && s[i].spanned;
+        const bool ok = !bad && span && !isnan_(cu) && !isnan_(cv);
+        if (!bad && !span) status |= ST_NO_LAYER;
+        const double pos = ok ? s[i].pos : qnan(), neg = ok ? s[i].neg : qnan();
+        st(a.pos[i], f64, c, pos); st(a.neg[i], f64, c, neg); st(a.tot[i], f64, c, pos + neg);
+        if (bad || !span) { st(a.shu[i], f64, c, qnan()); st(a.shv[i], f64, c, qnan()); }
     }
     sti(a.status, c, status);
 }

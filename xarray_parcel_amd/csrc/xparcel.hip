@@ -17,6 +17,7 @@
 #include "xp_bundle.hpp"
 #include "xp_dcape.hpp"
 #include "xp_kinematics.hpp"
+#include "xp_effective.hpp"
 
 namespace {
 
@@ -990,6 +991,43 @@ int xp_downdraft_cape(const xp_view *p, const xp_view *t, const xp_view *td, dou
     return st.finish();
 }
 
+int xp_effective_inflow_layer(const xp_view *p, const xp_view *t, const xp_view *td, const xp_view *z, double cape_min,
+                              double cin_min, double search_depth, const xp_opts *o, xp_effective_layer_out *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    const xp_opts opts = o ? *o : default_opts();
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) || (rc = check_opts(opts))) return rc;
+    if (z && (rc = check_views({{p, "pressure"}, {z, "height"}}))) return rc;
+    if (!out) return fail(XP_E_ARG, "xp_effective_inflow_layer: out: null");
+    if (out->dtype != p->dtype || out->mem != p->mem) return fail(XP_E_ARG, "xp_effective_inflow_layer: out: dtype / mem differ from the views'");
+    if (opts.humidity != XP_HUM_DEWPOINT) return fail(XP_E_ARG, "xp_effective_inflow_layer: humidity must be XP_HUM_DEWPOINT");
+    if (!(std::isfinite(cape_min) && std::isfinite(cin_min))) return fail(XP_E_ARG, "xp_effective_inflow_layer: cape_min and cin_min must be finite");
+    if (!(std::isfinite(search_depth) && search_depth > 0.0)) return fail(XP_E_ARG, "xp_effective_inflow_layer: search_depth must be finite and positive");
+    const int tm = opts.moist_mode == XP_MOIST_TABLE;
+    const size_t cb = rows_bytes(p, 1), ib = (size_t)p->ncol * 4;
+    TableSet ts;
+    xp::EffectiveArgs a;
+    memset(&a, 0, sizeof(a));
+    void *bi, *ti, *status;
+    if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) ||
+        (rc = stage_view(st, td, &a.td)) || (z && (rc = stage_view(st, z, &a.z))) ||
+        (rc = st.out(out->base_pressure, cb, out->mem, &a.base_p)) || (rc = st.out(out->top_pressure, cb, out->mem, &a.top_p)) ||
+        (rc = st.out(out->base_height, cb, out->mem, &a.base_z)) || (rc = st.out(out->top_height, cb, out->mem, &a.top_z)) ||
+        (rc = st.out(out->base_index, ib, out->mem, &bi)) || (rc = st.out(out->top_index, ib, out->mem, &ti)) ||
+        (rc = st.out(out->status, ib, out->mem, &status)) ||
+        (rc = st.out(out->candidate_cape, rows_bytes(p, p->nlev), out->mem, &a.cand_cape)) ||
+        (rc = st.out(out->candidate_cin, rows_bytes(p, p->nlev), out->mem, &a.cand_cin))) return rc;
+    a.base_idx = (int32_t *)bi; a.top_idx = (int32_t *)ti; a.status = (int32_t *)status;
+    a.nlev = p->nlev; a.ncol = p->ncol;
+    a.cape_min = cape_min; a.cin_min = cin_min; a.depth = search_depth;
+    a.vtc = opts.virtual_temperature_correction; a.log_interp = opts.lcl_interp == XP_LCL_INTERP_LOG;
+    a.pos_neg = opts.pos_cape_neg_cin; a.post_zero = opts.post_zero_cin;
+    a.tb = ts.tb; a.es_tab = ts.es;
+    xp::launch_effective_inflow(a, p->dtype == XP_F64, tm != 0, st.s);
+    return st.finish();
+}
+
 int xp_bunkers_storm_motion(const xp_view *p, const xp_view *u, const xp_view *v, const xp_view *z, xp_storm_motion_out *out,
                             void *stream) {
     Entry st(stream);
@@ -1046,6 +1084,41 @@ int xp_storm_relative_helicity(const xp_view *z, const xp_view *u, const xp_view
     a.status = (int32_t *)status;
     a.nlev = z->nlev; a.ncol = z->ncol; a.bottom = bottom; a.ndepth = ndepth;
     by_dtype(z->dtype, [&](auto t) { launch(xp::k_storm_relative_helicity<decltype(t)>, z->ncol, st, a); });
+    return st.finish();
+}
+
+int xp_storm_relative_helicity_layers(const xp_view *z, const xp_view *u, const xp_view *v, const void *surface_u,
+                                      const void *surface_v, const void *storm_u, const void *storm_v, const void *bottom,
+                                      int32_t nlayer, const void *const *top, xp_srh_layers_out *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{z, "height"}, {u, "u"}, {v, "v"}}))) return rc;
+    if (!out) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: out: null");
+    if (out->dtype != z->dtype || out->mem != z->mem) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: out: dtype / mem differ from the views'");
+    if (nlayer < 1 || nlayer > xp::SRH_MAX_DEPTHS) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: nlayer must lie in 1 ... 4, got %d", (int)nlayer);
+    if (!bottom || !top) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: bottom / top: null");
+    for (int i = 0; i < nlayer; ++i)
+        if (!top[i]) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: top[%d]: null", i);
+    if (!surface_u != !surface_v) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: surface wind: give both components or neither");
+    const size_t cb = rows_bytes(z, 1);
+    xp::SrhLayersArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = stage_view(st, z, &a.z)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
+        (rc = st.in(surface_u, cb, z->mem, &a.sfc_u)) || (rc = st.in(surface_v, cb, z->mem, &a.sfc_v)) ||
+        (rc = st.in(storm_u, cb, z->mem, &a.storm_u)) || (rc = st.in(storm_v, cb, z->mem, &a.storm_v)) ||
+        (rc = st.in(bottom, cb, z->mem, &a.bottom))) return rc;
+    for (int i = 0; i < nlayer; ++i) {
+        if ((rc = st.in(top[i], cb, z->mem, &a.top[i])) ||
+            (rc = st.out(out->positive[i], cb, out->mem, &a.pos[i])) || (rc = st.out(out->negative[i], cb, out->mem, &a.neg[i])) ||
+            (rc = st.out(out->total[i], cb, out->mem, &a.tot[i])) || (rc = st.out(out->shear_u[i], cb, out->mem, &a.shu[i])) ||
+            (rc = st.out(out->shear_v[i], cb, out->mem, &a.shv[i]))) return rc;
+    }
+    void *status;
+    if ((rc = st.out(out->status, (size_t)z->ncol * 4, out->mem, &status))) return rc;
+    a.status = (int32_t *)status;
+    a.nlev = z->nlev; a.ncol = z->ncol; a.nlayer = nlayer;
+    by_dtype(z->dtype, [&](auto t) { launch(xp::k_helicity_layers<decltype(t)>, z->ncol, st, a); });
     return st.finish();
 }
 

@@ -1,6 +1,7 @@
 """
 Storm motion, helicity and the composites on DataArrays: metpy.calc.bunkers_storm_motion, storm_relative_helicity,
-significant_tornado and supercell_composite for every column (or point) of a grid, through libxparcel
+significant_tornado and supercell_composite for every column (or point) of a grid, and what feeds the composites' effective
+arguments -- the effective inflow layer and helicity / bulk wind difference between per-column bounds -- through libxparcel
 (numpy_api.bunkers_storm_motion, ...).  The reference has no counterparts, so this lives next to the mirror
 (parcel_functions.py) rather than in it, and is built from the mirror's plumbing: a _Grid splits the inputs and wraps
 the results, _device turns library errors into the mirror's.
@@ -23,12 +24,26 @@ _ATTRS = {
     'positive_srh': {'long_name': 'Positive storm-relative helicity', 'units': _SRH},
     'negative_srh': {'long_name': 'Negative storm-relative helicity', 'units': _SRH},
     'total_srh': {'long_name': 'Storm-relative helicity', 'units': _SRH},
+    'shear_u': {'long_name': 'Bulk wind difference over the layer, u component', 'units': _WIND},
+    'shear_v': {'long_name': 'Bulk wind difference over the layer, v component', 'units': _WIND},
+    'shear_magnitude': {'long_name': 'Bulk wind difference over the layer', 'units': _WIND},
+    'base_pressure': {'long_name': 'Effective inflow layer base pressure', 'units': 'hPa'},
+    'top_pressure': {'long_name': 'Effective inflow layer top pressure', 'units': 'hPa'},
+    'base_height': {'long_name': 'Effective inflow layer base height above the lowest level', 'units': 'm'},
+    'top_height': {'long_name': 'Effective inflow layer top height above the lowest level', 'units': 'm'},
+    'base_index': {'long_name': 'Effective inflow layer base level index'},
+    'top_index': {'long_name': 'Effective inflow layer top level index'},
+    'status': {'long_name': 'Status bits'},
+    'candidate_cape': {'long_name': 'CAPE of the parcel lifted from the level', 'units': 'J kg$^{-1}$'},
+    'candidate_cin': {'long_name': 'CIN of the parcel lifted from the level', 'units': 'J kg$^{-1}$'},
     'significant_tornado': {'long_name': 'Significant tornado parameter', 'units': '1'},
     'supercell_composite': {'long_name': 'Supercell composite parameter', 'units': '1'},
 }
 _BUNKERS = {'right_u': 'bunkers_right_u', 'right_v': 'bunkers_right_v', 'left_u': 'bunkers_left_u',
             'left_v': 'bunkers_left_v', 'mean_u': 'mean_wind_u', 'mean_v': 'mean_wind_v'}
 _SRH_NAMES = {'positive': 'positive_srh', 'negative': 'negative_srh', 'total': 'total_srh'}
+_LAYER_NAMES = dict(_SRH_NAMES, shear_u='shear_u', shear_v='shear_v', shear_magnitude='shear_magnitude')
+_EFFECTIVE = ('base_pressure', 'top_pressure', 'base_height', 'top_height', 'base_index', 'top_index', 'status')
 
 
 def _per_col(g, x):
@@ -60,6 +75,44 @@ def storm_relative_helicity(height, u, v, depth, vert_dim=VERT, bottom=0.0, stor
     coords = dict(g.coords, srh_depth=np.asarray(depth, dtype=np.float64))
     return Dataset({name: DataArray(_host(res[k]), dims=('srh_depth',) + g.dims, coords=coords, attrs=dict(_ATTRS[name]),
                                     name=name) for k, name in _SRH_NAMES.items()})
+
+
+def effective_inflow_layer(pressure, temperature, dewpoint, height=None, vert_dim=VERT, cape_min=100.0, cin_min=-250.0,
+                           search_depth=300.0, moist=None, want_candidates=False, **cape_cin_options):
+    """The effective inflow layer (Thompson et al. 2007) of every column: the lowest contiguous run of levels whose lifted
+    parcels have CAPE >= cape_min and CIN >= cin_min, searched over the lowest search_depth hPa.  Returns a Dataset on
+    the horizontal dims: base / top pressure [hPa], height [m above the lowest valid level; NaN without `height`] and
+    level index (-1: none), and the status bits; with want_candidates also candidate_cape / candidate_cin on the
+    vertical (NaN where a level was not lifted).  Columns without a layer are NaN."""
+    g = _Grid(pressure, vert_dim)
+    res = _device(_api.effective_inflow_layer, g.values(pressure), g.values(temperature), g.values(dewpoint),
+                  None if height is None else g.values(height), cape_min=cape_min, cin_min=cin_min,
+                  search_depth=search_depth, moist=moist, want_candidates=want_candidates, **cape_cin_options)
+    out = {name: g.horiz(_host(res[name]), name, _ATTRS[name]) for name in _EFFECTIVE}
+    if want_candidates:
+        out.update({name: g.vert(_host(res[name]), name, _ATTRS[name]) for name in ('candidate_cape', 'candidate_cin')})
+    return Dataset(out)
+
+
+def storm_relative_helicity_layers(height, u, v, bottom, top, vert_dim=VERT, storm_u=0.0, storm_v=0.0, surface_u=None,
+                                   surface_v=None):
+    """Storm-relative helicity [m^2/s^2] and the bulk wind difference [m/s] of every column between its OWN bounds:
+    `bottom`, `top` [m] scalars or DataArrays on the horizontal dims, in storm_relative_helicity's height convention (what
+    effective_inflow_layer returns as base_height / top_height).  A sequence of up to four tops that share the bottom,
+    computed in one pass, adds the leading dim 'srh_layer'.  The wind difference is the wind at top minus the wind at
+    bottom, each linear in height (not MetPy's ln p bulk_shear).  Layers that are not spanned, or whose bounds are NaN or
+    inverted, are NaN."""
+    g = _Grid(height, vert_dim)
+    many = isinstance(top, (list, tuple))
+    tops = [_per_col(g, x) for x in top] if many else _per_col(g, top)
+    res = _device(_api.storm_relative_helicity_layers, g.values(height), g.values(u), g.values(v), _per_col(g, bottom), tops,
+                  storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), surface_u=_per_col(g, surface_u),
+                  surface_v=_per_col(g, surface_v))
+    if not many:
+        return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _LAYER_NAMES.items()})
+    coords = dict(g.coords, srh_layer=np.arange(len(top)))
+    return Dataset({name: DataArray(_host(res[k]), dims=('srh_layer',) + g.dims, coords=coords, attrs=dict(_ATTRS[name]),
+                                    name=name) for k, name in _LAYER_NAMES.items()})
 
 
 def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):

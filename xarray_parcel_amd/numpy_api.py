@@ -387,6 +387,35 @@ def downdraft_cape(pressure, temperature, dewpoint, bottom=700.0, depth=200.0, m
     return res
 
 
+def effective_inflow_layer(pressure, temperature, dewpoint, height=None, cape_min=100.0, cin_min=-250.0, search_depth=300.0,
+                           moist=None, want_candidates=False, **cape_cin_options):
+    """The effective inflow layer of Thompson et al. (2007) for every column (xp_effective_inflow_layer): the lowest
+    contiguous run of levels whose parcels, each lifted as the surface parcel of the column cut off below it, have
+    CAPE >= cape_min [J/kg] and CIN >= cin_min (CIN is <= 0 here).  Levels with a NaN in p, T or Td are skipped; the search
+    covers the levels with p >= p_lowest - search_depth [hPa].  cape_cin_options: the CAPE / CIN options of
+    cape_cin_columns (virtual_temperature_correction, lcl_interp, pos_cape_neg_cin, post_zero_cin); moist: 'exact' or
+    'table' ('family' runs as 'exact').  Returns a dict of per-column 'base_pressure', 'top_pressure' [hPa],
+    'base_height', 'top_height' [m above the lowest valid level: the bounds storm_relative_helicity_layers takes; NaN
+    without `height`], 'base_index', 'top_index' (level indices, -1 = none) and 'status' (XP_ST_NO_LAYER: no level
+    passes; ST_LAYER_OPEN: the window cut the layer; ST_LCL_NOT_CONVERGED, ST_BAD_PRESSURE); with want_candidates also
+    'candidate_cape', 'candidate_cin', shaped like the input: what was computed for every level that was lifted, NaN
+    elsewhere."""
+    assert 'humidity' not in cape_cin_options, 'effective_inflow_layer takes dewpoints'
+    c = _Call(*((pressure, temperature, dewpoint) + (() if height is None else (height,))))
+    p, t, td = c.ins[:3]
+    assert all(a.shape == p.shape for a in c.ins), 'pressure, temperature, dewpoint, height must share a shape'
+    o = _opts(moist=moist or _DEFAULT['moist'], **cape_cin_options)
+    res = {k: c.out(c.hshape, np.int32 if k in L.EFFECTIVE_I else None) for k in L.EFFECTIVE_F + L.EFFECTIVE_I}
+    if want_candidates:
+        res.update({k: c.out(p.shape) for k in L.EFFECTIVE_CANDIDATES})
+    out = L.EffectiveLayerOut(dtype=c.xp_dtype, mem=c.mem)
+    for k, a in res.items():
+        setattr(out, k, _ptr(a))
+    c.run('xp_effective_inflow_layer', c.view(p), c.view(t), c.view(td), None if height is None else c.view(c.ins[3]),
+          float(cape_min), float(cin_min), float(search_depth), o, out)
+    return res
+
+
 def interp_level(coords, variable, at, log=False):
     """pf.py:1758 linear_interp (log=False) / pf.py:1813 log_interp (log=True) of one variable."""
     c = _Call(coords, variable)
@@ -754,6 +783,40 @@ def storm_relative_helicity(height, u, v, depth, bottom=0.0, storm_u=0.0, storm_
     c.run('xp_storm_relative_helicity', c.view(z), c.view(wu), c.view(wv), *sfc, c.per_col(storm_u), c.per_col(storm_v),
           float(bottom), len(depths), (C.c_double * len(depths))(*depths), out)
     return res
+
+
+def storm_relative_helicity_layers(height, u, v, bottom, top, storm_u=0.0, storm_v=0.0, surface_u=None, surface_v=None):
+    """Storm-relative helicity and the bulk wind difference between PER-COLUMN bounds (xp_storm_relative_helicity_layers):
+    `bottom` and `top` [m] one value per column (scalars are broadcast) in storm_relative_helicity's height convention --
+    above the lowest valid level, or above the surface with surface_u / surface_v: what effective_inflow_layer returns
+    as base_height / top_height.  `top`: one array, or a sequence of up to four that share the bottom, computed in one
+    pass (the outputs then gain a leading axis).  Returns a dict of 'positive', 'negative', 'total' [m^2/s^2], 'shear_u',
+    'shear_v' (the wind at top minus the wind at bottom, each linear in height: wind_shear's rule, not MetPy's ln p
+    bulk_shear), 'shear_magnitude' [m/s] and 'status' (XP_ST_NO_LAYER: a NaN or inverted bound, bottom < 0 or a layer the
+    column does not span -- that layer NaN; ST_BAD_HEIGHT)."""
+    many = isinstance(top, (list, tuple))
+    tops = list(top) if many else [top]
+    assert 1 <= len(tops) <= L.SRH_MAX_DEPTHS, 'top: one to four arrays'
+    assert (surface_u is None) == (surface_v is None), 'surface_u, surface_v: give both or neither'
+    per = [x for x in (bottom, *tops, storm_u, storm_v, surface_u, surface_v) if _is_torch(x)]   # (CUDA tensors decide the device)
+    c = _Call(height, u, v, *per)
+    z, wu, wv = c.ins[:3]
+    assert z.shape == wu.shape == wv.shape, 'height, u, v must share a shape'
+    sfc = [None, None] if surface_u is None else [c.per_col(surface_u), c.per_col(surface_v)]
+    tps = [c.per_col(x) for x in tops]
+    shape = ((len(tops),) if many else ()) + c.hshape
+    res = {k: c.out(shape) for k in L.SRH_LAYERS_OUT}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = L.SrhLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in L.SRH_LAYERS_OUT:
+        arr = getattr(out, k)
+        for i in range(len(tops)):
+            arr[i] = _ptr(res[k][i] if many else res[k])
+    c.run('xp_storm_relative_helicity_layers', c.view(z), c.view(wu), c.view(wv), *sfc, c.per_col(storm_u), c.per_col(storm_v),
+          c.per_col(bottom), len(tops), (C.c_void_p * len(tops))(*map(_ptr, tps)), out)
+    hyp = torch.hypot if _is_torch(res['shear_u']) else np.hypot
+    res['shear_magnitude'] = hyp(res['shear_u'], res['shear_v'])
+    return {**{k: res[k] for k in L.SRH_LAYERS_OUT}, 'shear_magnitude': res['shear_magnitude'], 'status': res['status']}
 
 
 def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):
