@@ -3,14 +3,13 @@ declarations, the xarray mirror (xarray_parcel_amd/downdraft.py) around a stubbe
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import thermo as th
 from tests import dcape_restatement as R
+from tests.resource_report import needs_hipcc, resources
 from tests.test_abi_cpu import _KINDS, _prototypes, _struct_fields
 from xarray_parcel_amd import _lib as L
 from xarray_parcel_amd import downdraft
@@ -194,31 +193,11 @@ def test_mirror_without_tables_asserts(monkeypatch):
 
 
 # -- kernel resources ------------------------------------------------------------------------------------------------
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which('hipcc')), reason='hipcc not available')
+@needs_hipcc
 def test_kernel_keeps_four_waves_per_simd_without_spills(tmp_path):
-    src = os.path.join(ROOT, 'xarray_parcel_amd', 'csrc', 'xparcel.hip')
-    cmd = ([HIPCC if os.path.exists(HIPCC) else 'hipcc'] + [f for f in L.HIPCC_FLAGS if f != '-fPIC'] +
-           ['-S', '--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-o', str(tmp_path / 'x.s'), src])
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    asm = open(tmp_path / 'x.s').read()
-    rec, name = {}, None
-    for ln in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', ln)
-        if m:
-            name = m.group(1)
-            rec[name] = {}
-        for key, pat in (('vgprs', r' VGPRs: (\d+)'), ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)')):
-            m = re.search(pat, ln)
-            if m and name:
-                rec[name][key] = int(m.group(1))
+    rec = resources(tmp_path, 'xparcel.hip')
     kernels = [n for n in rec if 'k_downdraft_cape' in n]
     assert sorted(kernels) == ['_ZN2xp16k_downdraft_capeIdEEvNS_9DcapeArgsE', '_ZN2xp16k_downdraft_capeIfEEvNS_9DcapeArgsE']
     for n in kernels:
-        i = asm.find('\n' + n + ':')
-        body = asm[i:asm.find('.Lfunc_end', i)]
-        assert i >= 0 and not re.search(r'scratch_(?:load|store)', body), n
+        assert rec[n]['in_asm'] and not rec[n]['scratch_insts'], n
         assert rec[n]['vgprs'] <= 128 and rec[n]['occupancy'] >= 4, (n, rec[n])

@@ -4,13 +4,12 @@ launch, and the operating point of the two kernels (cross-compiled for gfx950)."
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import effective_layer_restatement as R
+from tests.resource_report import needs_hipcc, resources
 from tests.test_abi_cpu import _KINDS, _prototypes, _struct_fields
 from tests.test_kinematics_cpu import circular_hodograph
 from xarray_parcel_amd import _lib as L
@@ -258,55 +257,29 @@ def test_parcel_functions_gains_nothing():
 
 
 # -- kernel resources -----------------------------------------------------------------------------------------------------
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-
-
-def _resources(tmp_path, src, flags):
-    cmd = ([HIPCC if os.path.exists(HIPCC) else 'hipcc'] + [f for f in L.HIPCC_FLAGS if f != '-fPIC'] + list(flags) +
-           ['-S', '--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-o', str(tmp_path / 'x.s'),
-            os.path.join(ROOT, 'xarray_parcel_amd', 'csrc', src)])
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    asm = open(tmp_path / 'x.s').read()
-    rec, name = {}, None
-    for ln in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', ln)
-        if m:
-            name = m.group(1)
-            rec[name] = {}
-        for key, pat in (('vgprs', r' VGPRs: (\d+)'), ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)'),
-                         ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('lds', r'LDS Size \[bytes/block\]: (\d+)')):
-            m = re.search(pat, ln)
-            if m and name:
-                rec[name][key] = int(m.group(1))
-    return rec, asm
-
-
-def _check(rec, asm, kernels, lds_cap=None):
+def _check(rec, kernels, lds_cap=None):
     for n in kernels:
-        i = asm.find('\n' + n + ':')
-        body = asm[i:asm.find('.Lfunc_end', i)]
         print(n, rec[n])
-        assert i >= 0 and not re.search(r'scratch_(?:load|store)', body), n
+        assert rec[n]['in_asm'] and not rec[n]['scratch_insts'], n
         assert rec[n]['vgprs'] <= 128 and rec[n]['occupancy'] >= 4 and rec[n]['scratch'] == 0, (n, rec[n])
         if lds_cap is not None:
             assert rec[n]['lds'] <= lds_cap, (n, rec[n])
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which('hipcc')), reason='hipcc not available')
+@needs_hipcc
 def test_kernels_keep_four_waves_per_simd_without_spills(tmp_path):
     """Both kernels, f32 and f64: at most 128 VGPRs, four waves per SIMD, no scratch at all (ScratchSize 0, no scratch
     instruction in the body), and the inflow kernel's LDS -- the e_s / ln table plus 13 Scan slots per thread -- within 40 KB,
     i.e. four workgroups per CU.  The layers kernel lives in xparcel.hip; the inflow kernel is compiled as the library
     compiles it, in its own unit with that unit's flags (_lib.UNITS)."""
-    rec, asm = _resources(tmp_path, 'xparcel.hip', [])
+    rec = resources(tmp_path, 'xparcel.hip')
     layers = [n for n in rec if re.search(r'k_helicity_layersI', n)]
     assert len(layers) == 2, sorted(rec)
     assert not [n for n in rec if 'k_effective_inflow' in n]
-    _check(rec, asm, layers)
+    _check(rec, layers)
     unit = [u for u in L.UNITS if u[1] == 'xp_effective_tu.hip']
     assert len(unit) == 1
-    rec, asm = _resources(tmp_path, unit[0][1], unit[0][2])
+    rec = resources(tmp_path, unit[0][1], unit[0][2])
     inflow = [n for n in rec if re.search(r'k_effective_inflowI', n)]
     assert len(inflow) == 4, sorted(rec)                                  # f64 / f32 x RK4 / lookup tables
-    _check(rec, asm, inflow, lds_cap=40 * 1024)
+    _check(rec, inflow, lds_cap=40 * 1024)

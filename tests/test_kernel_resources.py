@@ -9,47 +9,15 @@ resource usage).
   scratch must stay small -- without -disable-machine-licm the compiler hoists ~40 fp64 constants out of the level loop
   and spills them (200+ B / lane, reloaded every level: measured 1.33 ms instead of 0.93 on c2).
 An innocent edit can cost 10-30 % here; this test says so."""
-import os
 import itertools
 import re
-import shutil
-import subprocess
 
-import pytest
-
+from tests.resource_report import needs_hipcc, resources
 from xarray_parcel_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-needs_hipcc = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which('hipcc')), reason='hipcc not available')
 
 
 def _resources(tmp_path, mode):
-    src = os.path.join(ROOT, 'xarray_parcel_amd', 'csrc', 'xp_cape_tu.hip')
-    # device assembly instead of an object: the resource remarks come out the same, and the text shows whether the
-    # kernel itself spills (ScratchSize also counts the frames of the out-of-line slow paths it calls)
-    cmd = ([HIPCC if os.path.exists(HIPCC) else 'hipcc'] + [f for f in _lib.HIPCC_FLAGS if f != '-fPIC'] +
-           ['-S', '--cuda-device-only', '-DXP_TU_T=double', f'-DXP_TU_MODE={mode}'] +
-           _lib.TU_FLAGS[mode] + ['-Rpass-analysis=kernel-resource-usage', '-o', str(tmp_path / 'tu.s'), src])
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    asm = open(tmp_path / 'tu.s').read()
-    rec, name = {}, None
-    for ln in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', ln)
-        if m:
-            name = m.group(1)
-            rec[name] = {}
-        for key, pat in (('vgprs', r' VGPRs: (\d+)'), ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'),
-                         ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)'), ('lds', r'LDS Size \[bytes/block\]: (\d+)')):
-            m = re.search(pat, ln)
-            if m and name:
-                rec[name][key] = int(m.group(1))
-    for name in rec:                                     # spill instructions inside the function's own body
-        i = asm.find('\n' + name + ':')
-        body = asm[i:asm.find('.Lfunc_end', i)] if i >= 0 else ''
-        rec[name]['spills'] = len(re.findall(r'scratch_(?:load|store)|Folded (?:Spill|Reload)', body))
-    return rec
+    return resources(tmp_path, 'xp_cape_tu.hip', ['-DXP_TU_T=double', f'-DXP_TU_MODE={mode}'] + _lib.TU_FLAGS[mode])
 
 
 def _pick(rec, pm, profile, mode, hum, deflt, lean=0, persist=0):
@@ -102,13 +70,6 @@ def test_family_profile_kernels_spill_no_more_than_they_do(tmp_path):
 def test_fused_parcels_kernel_fits_one_workgroup_per_cu(tmp_path):
     """csrc/xp_multi.hpp, two parcels per thread: 512-thread workgroups (two wavefronts per SIMD, up to 256 VGPRs), LDS
     = tables + 2 x 12 slot fields x 512 threads within the CU's 160 KB, no VGPR spill."""
-    src = os.path.join(ROOT, 'xarray_parcel_amd', 'csrc', 'xp_multi_tu.hip')
-    cmd = ([HIPCC if os.path.exists(HIPCC) else 'hipcc'] + [f for f in _lib.HIPCC_FLAGS if f != '-fPIC'] +
-           ['-S', '--cuda-device-only', '-DXP_TU_T=float', '-DXP_MULTI_NP=2'] + _lib.MULTI_FLAGS[2] +
-           ['-Rpass-analysis=kernel-resource-usage', '-o', str(tmp_path / 'mt.s'), src])
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    vg = [int(x) for x in re.findall(r' VGPRs: (\d+)', out.stderr)]
-    lds = [int(x) for x in re.findall(r'LDS Size \[bytes/block\]: (\d+)', out.stderr)]
-    sp = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out.stderr)]
+    rec = resources(tmp_path, 'xp_multi_tu.hip', ['-DXP_TU_T=float', '-DXP_MULTI_NP=2'] + _lib.MULTI_FLAGS[2])
+    vg, lds, sp = ([r[k] for r in rec.values()] for k in ('vgprs', 'lds', 'vgpr_spill'))
     assert len(vg) == 2 and max(vg) <= 256 and max(lds) <= 160 * 1024 and max(sp) == 0, (vg, lds, sp)

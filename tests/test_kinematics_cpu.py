@@ -4,13 +4,12 @@ stubbed launch, and the kernels' resources."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import kinematics_restatement as R
+from tests.resource_report import needs_hipcc, resources
 from tests.test_abi_cpu import _KINDS, _prototypes, _struct_fields
 from xarray_parcel_amd import _lib as L
 from xarray_parcel_amd import kinematics
@@ -284,33 +283,17 @@ def test_parcel_functions_gains_nothing():
 
 
 # -- kernel resources -----------------------------------------------------------------------------------------------------
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which('hipcc')), reason='hipcc not available')
+@needs_hipcc
 def test_kernels_keep_four_waves_per_simd_without_spills(tmp_path):
-    src = os.path.join(ROOT, 'xarray_parcel_amd', 'csrc', 'xparcel.hip')
-    cmd = ([HIPCC if os.path.exists(HIPCC) else 'hipcc'] + [f for f in L.HIPCC_FLAGS if f != '-fPIC'] +
-           ['-S', '--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-o', str(tmp_path / 'x.s'), src])
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    asm = open(tmp_path / 'x.s').read()
-    rec, name = {}, None
-    for ln in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', ln)
-        if m:
-            name = m.group(1)
-            rec[name] = {}
-        for key, pat in (('vgprs', r' VGPRs: (\d+)'), ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)'),
-                         ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)')):
-            m = re.search(pat, ln)
-            if m and name:
-                rec[name][key] = int(m.group(1))
+    rec = resources(tmp_path, 'xparcel.hip')
     kernels = [n for n in rec if re.search(r'k_(bunkers_storm_motion|storm_relative_helicity|significant_tornado|'
                                            r'supercell_composite)I', n)]
     assert len(kernels) == 8, sorted(rec)
     for n in kernels:
-        i = asm.find('\n' + n + ':')
-        body = asm[i:asm.find('.Lfunc_end', i)]
-        assert i >= 0 and not re.search(r'scratch_(?:load|store)', body), n
+        assert rec[n]['in_asm'] and not rec[n]['scratch_insts'], n
         assert rec[n]['vgprs'] <= 128 and rec[n]['occupancy'] >= 4 and rec[n]['scratch'] == 0, (n, rec[n])
+    # the fixed-depth helicity kernel shares its walk with k_helicity_layers (which is held to four waves): it has run at
+    # five waves per SIMD since it was written, and the shared walk must not cost it that
+    for n in kernels:
+        if 'k_storm_relative_helicity' in n:
+            assert rec[n]['occupancy'] >= 5, (n, rec[n])

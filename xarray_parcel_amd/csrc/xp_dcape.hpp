@@ -15,9 +15,6 @@
 
 namespace xp {
 
-constexpr int ST_NO_LAYER = 16;       // XP_ST_NO_LAYER
-constexpr int ST_LCL_NOT_CONVERGED = 2;
-
 struct DcapeArgs {
     View p, t, td;
     int64_t nlev, ncol;
@@ -29,9 +26,6 @@ struct DcapeArgs {
     int32_t *status;
     void *prof;                       // dense (nlev, ncol) parcel temperature, NaN off the down levels (may be null)
 };
-
-// np.isclose(x, y): |x - y| <= 1e-8 + 1e-5 |y|
-XP_DEV bool isclose_(double x, double y) { return fabs(x - y) <= 1e-8 + 1e-5 * fabs(y); }
 
 // value at ln p = x between the levels lo (higher pressure) and hi: MetPy's interpolate_1d on ln p (log_interpolate_1d).
 // Without a level below (lo_x NaN) the result is NaN, as MetPy's fill value outside the data.

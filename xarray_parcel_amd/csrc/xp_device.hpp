@@ -32,6 +32,12 @@ constexpr double LCL_SNAP = 1e-11;    // a level this close (relative) to p_lcl 
 
 XP_DEV double qnan() { return __longlong_as_double(0x7ff8000000000000LL); }
 XP_DEV bool isnan_(double x) { return x != x; }
+// np.isclose(x, y): |x - y| <= 1e-8 + 1e-5 |y|
+XP_DEV bool isclose_(double x, double y) { return fabs(x - y) <= 1e-8 + 1e-5 * fabs(y); }
+
+// the bits of a column's status word: include/xparcel.h's XP_ST_* (xparcel.hip asserts that they agree)
+constexpr int ST_TOP_NAN = 1, ST_LCL_NOT_CONVERGED = 2, ST_NAN_PRESSURE = 4, ST_BAD_PRESSURE = 8, ST_NO_LAYER = 16,
+              ST_BAD_HEIGHT = 32, ST_LAYER_OPEN = 64;
 
 // ---- fp64 math without the special-case handling of the device library -----------------------------
 // fp64 runs at half the fp32 VALU rate on CDNA4 and the library exp/log/pow/division carry ~2x the
@@ -1060,8 +1066,8 @@ struct Scan {
         // EL exists only if the parcel ends colder than the environment and the EL is above the LCL
         bool el_ok = top_le && (el_p < p_lcl);                                  // pf.py:1151-1155
         if (!el_ok) { el_p = qnan(); el_t = qnan(); el_idx = -1; }
-        if (!any_valid && env_any) r.status |= 1;                               // assert of pf.py:1149
-        if (bad_p) r.status |= 8;                                               // XP_ST_BAD_PRESSURE
+        if (!any_valid && env_any) r.status |= ST_TOP_NAN;                      // assert of pf.py:1149
+        if (bad_p) r.status |= ST_BAD_PRESSURE;
         bool lfc_missing = any_inc == 0;
         bool replace = (pos_parcel && lfc_missing) ||
                        (!lfc_missing && isnan_(lfc_p) && (el_p < p_lcl));       // pf.py:1161-1180

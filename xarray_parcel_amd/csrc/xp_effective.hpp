@@ -16,12 +16,8 @@
 // node, including its tie rules (LCL_SNAP, the saturated parcel, a level on the LCL).
 #pragma once
 #include "xp_kernels.hpp"
-#include "xp_dcape.hpp"   // ST_NO_LAYER, ST_LCL_NOT_CONVERGED
 
 namespace xp {
-
-constexpr int ST_LAYER_OPEN = 64;     // XP_ST_LAYER_OPEN
-constexpr int ST_BAD_P = 8;           // XP_ST_BAD_PRESSURE
 
 struct EffectiveArgs {
     View p, t, td, z;                 // z.data may be null (no heights)
@@ -119,7 +115,7 @@ XP_DEV void lift_candidate(const EffectiveArgs &a, const double *es, double *slo
         sP = Pc; sT = Tc; sM = Mc;
     }
     const Scan::Result r = sc.finish(a.post_zero != 0);
-    status |= r.status & ST_BAD_P;
+    status |= r.status & ST_BAD_PRESSURE;
     cape = r.cape; cin = r.cin;
 }
 

@@ -299,7 +299,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     const bool vtc = DEF || (a.vtc != 0), pos_neg = DEF || (a.pos_neg != 0), log_interp = DEF || (a.log_interp != 0);
     const bool need_w = vtc || PROFILE;
     const Lcl l = lcl(pc.p, pc.t, pc.td);
-    int status = l.not_converged ? 2 : 0;
+    int status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
     const ScalarsOut &s = a.s;
 
     if (isnan_(l.p)) {
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
         X = (P == l.p) ? x_lcl : X;
         if (TRACK) cur_k = skew ? kc - 1 : kc;
         const bool cross = !skew && (last || P < l.p);
-        if (!LEAN && isnan_(P) && !skew && !last) status |= 4;             // NaN pressure below the LCL (see xparcel.h)
+        if (!LEAN && isnan_(P) && !skew && !last) status |= ST_NAN_PRESSURE;   // NaN pressure below the LCL (see xparcel.h)
         // only the parcel temperature / mixing ratio is branched, the environment and the scan node are shared
         double tp, tvp;
         if (!skew) {                                                       // dry adiabat (pf.py:313, 767)

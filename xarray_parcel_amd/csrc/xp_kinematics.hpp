@@ -2,7 +2,7 @@
 //   k_bunkers_storm_motion     metpy.calc.bunkers_storm_motion, one thread per column;
 //   k_storm_relative_helicity  metpy.calc.storm_relative_helicity for up to four depths, one thread per column;
 //   k_helicity_layers          the same between per-column bounds (up to four tops sharing a bottom), plus the bulk wind
-//                              difference over each layer;
+//                              difference over each layer -- both are helicity_walk, one with LAYERS and one without;
 //   k_significant_tornado, k_supercell_composite   per point, in MetPy's operation order.
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/kinematics_restatement.py.  Each column kernel
 // makes one upward pass with level-major loads (coalesced when col_stride == 1): the layer points of MetPy's get_layer /
@@ -12,12 +12,8 @@
 // wave-uniform ballot once every lane is done, so levels above 6 km (Bunkers) or the deepest SRH top are never read.
 #pragma once
 #include "xp_kernels.hpp"
-#include "xp_dcape.hpp"   // ST_NO_LAYER, isclose_
 
 namespace xp {
-
-constexpr int ST_BAD_PRESSURE = 8;    // XP_ST_BAD_PRESSURE
-constexpr int ST_BAD_HEIGHT = 32;     // XP_ST_BAD_HEIGHT
 
 // ---- Bunkers storm motion ----------------------------------------------------------------------------------------------
 struct StormMotionArgs {
@@ -126,17 +122,22 @@ void k_bunkers_storm_motion(StormMotionArgs a) {
     sti(a.status, c, bad ? bad : (ok ? 0 : ST_NO_LAYER));
 }
 
-// ---- storm-relative helicity -------------------------------------------------------------------------------------------
+// ---- storm-relative helicity, and the bulk wind difference over per-column layers ------------------------------------------
 constexpr int SRH_MAX_DEPTHS = 4;
 
+// One argument struct for both kernels.  k_storm_relative_helicity reads its bounds from bottom / top[] (the same for every
+// column) and has no shu / shv; k_helicity_layers reads them per column from bottom_col / top_col[] (in the kernel's own
+// height convention).
 struct SrhArgs {
     View z, u, v;
     int64_t nlev, ncol;
     const void *sfc_u, *sfc_v, *storm_u, *storm_v;   // per column, in the inputs' dtype (each may be null)
     double bottom;
     double top[SRH_MAX_DEPTHS];                       // bottom + depth
-    int ndepth;
-    void *pos[SRH_MAX_DEPTHS], *neg[SRH_MAX_DEPTHS], *tot[SRH_MAX_DEPTHS];
+    const void *bottom_col;                           // per column
+    const void *top_col[SRH_MAX_DEPTHS];              // per column and layer
+    int n;                                            // depths / layers
+    void *pos[SRH_MAX_DEPTHS], *neg[SRH_MAX_DEPTHS], *tot[SRH_MAX_DEPTHS], *shu[SRH_MAX_DEPTHS], *shv[SRH_MAX_DEPTHS];
     int32_t *status;
 };
 
@@ -156,127 +157,39 @@ struct SrhSum {
     }
 };
 
-template <typename T> __global__ __launch_bounds__(256)
-void k_storm_relative_helicity(SrhArgs a) {
+// The walk of both kernels.  LAYERS: the bounds are read per column, and next to the helicity sums goes the ground-relative
+// wind at top[i] minus the wind at bottom, both linear in height between the levels on either side (xp_wind_shear's rule,
+// not MetPy's ln p bulk_shear).  A layer takes part when i < n, bottom >= 0 and top > bottom (a NaN bound fails both
+// comparisons); any other is left out (NaN, XP_ST_NO_LAYER).  The fixed-depth entry point only passes bounds that qualify.
+template <typename T, bool LAYERS>
+XP_DEV void helicity_walk(const SrhArgs &a) {
 #pragma clang fp contract(off)
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.ncol) return;
     constexpr int f64 = sizeof(T) == 8;
     const double cu = a.storm_u ? ld1<T>(a.storm_u, c) : 0.0, cv = a.storm_v ? ld1<T>(a.storm_v, c) : 0.0;
-    const double b = a.bottom;
-    SrhSum s[SRH_MAX_DEPTHS];
-#pragma unroll
-    for (int i = 0; i < SRH_MAX_DEPTHS; ++i) { s[i].init(); s[i].fin = i >= a.ndepth; }
-    // the walk: the surface point (k = -1) if given, then the levels; h relative to the first valid point without it
-    const bool sfc = a.sfc_u != nullptr;
-    double hp = qnan(), up = qnan(), vp = qnan(), h0 = sfc ? 0.0 : qnan();
-    bool has_prev = false, bottom_ok = false, bottom_hit = false, bottom_done = false, done = false;
-    int bad = 0;
-    for (int64_t k = sfc ? -1 : 0; k < a.nlev; ++k) {
-        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
-        if (done) continue;
-        double h, u, v;
-        if (k < 0) { h = 0.0; u = ld1<T>(a.sfc_u, c); v = ld1<T>(a.sfc_v, c); }
-        else { h = ld<T>(a.z, k, c); u = ld<T>(a.u, k, c); v = ld<T>(a.v, k, c); }
-        if (isnan_(h) || isnan_(u) || isnan_(v)) continue;                  // missing level: dropped
-        if (isnan_(h0)) h0 = h;
-        h = h - h0;
-        if (has_prev && !(h > hp)) { bad = ST_BAD_HEIGHT; done = true; continue; }
-        if (!has_prev) bottom_ok = b >= h;                                  // the bottom lies on or above the lowest point
-        u = u - cu; v = v - cv;
-        const bool above_b = h >= b || isclose_(h, b);
-        // the bottom point, where no level equals it: between the level below and this one, in order
-        bool add_b = false;
-        double ub = qnan(), vb = qnan();
-        if (!bottom_done && h >= b) {
-            bottom_done = true;
-            bottom_hit = h == b;
-            if (!bottom_hit && has_prev) {
-                add_b = true;
-                const double f = (b - hp) / (h - hp);
-                ub = up + f * (u - up); vb = vp + f * (v - vp);
-            }
-        }
-        bool all_fin = true;
-#pragma unroll
-        for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
-            SrhSum &r = s[i];
-            if (r.fin) continue;
-            const double t = a.top[i];
-            if (add_b) r.emit(ub, vb);
-            const bool below_t = h <= t || isclose_(h, t);
-            if (h >= t) r.spanned = true;
-            // the top point, where no level equals it: before the first level above it
-            if (h > t && !r.top_hit) {
-                r.top_hit = true;
-                if (has_prev) {
-                    const double f = (t - hp) / (h - hp);
-                    r.emit(up + f * (u - up), vp + f * (v - vp));
-                }
-            }
-            if (above_b && below_t) {
-                r.emit(u, v);
-                r.top_hit = r.top_hit || h == t;
-            }
-            if (!below_t) r.fin = true;
-            all_fin = all_fin && r.fin;
-        }
-        done = all_fin;
-        hp = h; up = u; vp = v; has_prev = true;
-    }
-    int status = bad;
-#pragma unroll
-    for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
-        if (i >= a.ndepth) continue;
-        const bool ok = !bad && bottom_ok && s[i].spanned && !isnan_(cu) && !isnan_(cv);
-        if (!bad && !(bottom_ok && s[i].spanned)) status |= ST_NO_LAYER;
-        const double pos = ok ? s[i].pos : qnan(), neg = ok ? s[i].neg : qnan();
-        st(a.pos[i], f64, c, pos); st(a.neg[i], f64, c, neg); st(a.tot[i], f64, c, pos + neg);
-    }
-    sti(a.status, c, status);
-}
-
-// ---- helicity and bulk wind difference over per-column layers -----------------------------------------------------------
-// k_storm_relative_helicity's walk with the bounds read per column: bottom[c] and top[i][c] (in the kernel's own height
-// convention) in place of the scalars, and next to the helicity sums the ground-relative wind at top[i][c] minus the wind at
-// bottom[c], both linear in height between the levels on either side (xp_wind_shear's rule, not MetPy's ln p bulk_shear).
-// A NaN bound, top <= bottom or bottom < 0 leaves that layer out (NaN, XP_ST_NO_LAYER).
-struct SrhLayersArgs {
-    View z, u, v;
-    int64_t nlev, ncol;
-    const void *sfc_u, *sfc_v, *storm_u, *storm_v;   // per column, in the inputs' dtype (each may be null)
-    const void *bottom;                               // per column
-    const void *top[SRH_MAX_DEPTHS];                  // per column and layer
-    int nlayer;
-    void *pos[SRH_MAX_DEPTHS], *neg[SRH_MAX_DEPTHS], *tot[SRH_MAX_DEPTHS], *shu[SRH_MAX_DEPTHS], *shv[SRH_MAX_DEPTHS];
-    int32_t *status;
-};
-
-template <typename T> __global__ __launch_bounds__(256, 4)
-void k_helicity_layers(SrhLayersArgs a) {
-#pragma clang fp contract(off)
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.ncol) return;
-    constexpr int f64 = sizeof(T) == 8;
-    const double cu = a.storm_u ? ld1<T>(a.storm_u, c) : 0.0, cv = a.storm_v ? ld1<T>(a.storm_v, c) : 0.0;
-    const double b = ld1<T>(a.bottom, c);
-    const bool b_valid = b >= 0.0;                                          // NaN: not valid
+    const double b = LAYERS ? ld1<T>(a.bottom_col, c) : a.bottom;
     SrhSum s[SRH_MAX_DEPTHS];
     double top[SRH_MAX_DEPTHS];
+    // (valid[] apart from s[i].fin, and below the fixed-depth tops read from the arguments again, not from top[]: with either
+    // written the shorter way the compiler gives k_storm_relative_helicity a 36-byte scratch frame it never touches)
     bool valid[SRH_MAX_DEPTHS];
 #pragma unroll
     for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
         s[i].init();
-        top[i] = i < a.nlayer ? ld1<T>(a.top[i], c) : qnan();
-        valid[i] = i < a.nlayer && b_valid && top[i] > b;
+        top[i] = LAYERS && i < a.n ? ld1<T>(a.top_col[i], c) : a.top[i];
+        valid[i] = i < a.n && b >= 0.0 && top[i] > b;
         s[i].fin = !valid[i];
     }
+    bool done = !(valid[0] || valid[1] || valid[2] || valid[3]);
+    // the walk: the surface point (k = -1) if given, then the levels; h relative to the first valid point without it
     const bool sfc = a.sfc_u != nullptr;
     double hp = qnan(), h0 = sfc ? 0.0 : qnan();
-    double gup = qnan(), gvp = qnan();                                      // the previous point's ground-relative wind
-    double bu = qnan(), bv = qnan();                                        // the ground-relative wind at the bottom
+    // the previous point's wind: storm-relative (the helicity), carried as it was formed; LAYERS carries the ground-relative
+    // one (the bulk wind difference) and forms the storm-relative one from it again, the same value in two registers fewer
+    double up = qnan(), vp = qnan(), gup = qnan(), gvp = qnan();
+    double bu = qnan(), bv = qnan();                                        // LAYERS: the ground-relative wind at the bottom
     bool has_prev = false, bottom_ok = false, bottom_hit = false, bottom_done = false;
-    bool done = !(valid[0] || valid[1] || valid[2] || valid[3]);
     int bad = 0;
     for (int64_t k = sfc ? -1 : 0; k < a.nlev; ++k) {
         if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
@@ -289,10 +202,11 @@ void k_helicity_layers(SrhLayersArgs a) {
         h = h - h0;
         if (has_prev && !(h > hp)) { bad = ST_BAD_HEIGHT; done = true; continue; }
         if (!has_prev) bottom_ok = b >= h;                                  // the bottom lies on or above the lowest point
-        const double gu = u, gv = v;                                        // ground-relative: the bulk wind difference
-        u = u - cu; v = v - cv;                                             // storm-relative: the helicity
-        const double up = gup - cu, vp = gvp - cv;                          // (the previous point's, as it was formed then)
+        const double gu = u, gv = v;
+        u = u - cu; v = v - cv;
+        if constexpr (LAYERS) { up = gup - cu; vp = gvp - cv; }
         const bool above_b = h >= b || isclose_(h, b);
+        // the bottom point, where no level equals it: between the level below and this one, in order
         bool add_b = false;
         double ub = qnan(), vb = qnan();
         if (!bottom_done && h >= b) {
@@ -311,12 +225,12 @@ void k_helicity_layers(SrhLayersArgs a) {
         for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
             SrhSum &r = s[i];
             if (r.fin) continue;
-            const double t = top[i];
+            const double t = LAYERS ? top[i] : a.top[i];
             if (add_b) r.emit(ub, vb);
             const bool below_t = h <= t || isclose_(h, t);
             // the first level at or above the top: the wind there minus the wind at the bottom (known by now: bottom < top)
             // is stored right away, not carried to the end of the walk; a column that turns out bad overwrites it below
-            if (h >= t && !r.spanned) {
+            if (LAYERS && h >= t && !r.spanned) {
                 double tu = gu, tv = gv;
                 if (h != t) {
                     const double f = (t - hp) / (h - hp);
@@ -327,6 +241,7 @@ void k_helicity_layers(SrhLayersArgs a) {
                 st(a.shu[i], f64, cc, tu - bu); st(a.shv[i], f64, cc, tv - bv);
             }
             if (h >= t) r.spanned = true;
+            // the top point, where no level equals it: before the first level above it
             if (h > t && !r.top_hit) {
                 r.top_hit = true;
                 if (has_prev) {
@@ -342,21 +257,29 @@ void k_helicity_layers(SrhLayersArgs a) {
             all_fin = all_fin && r.fin;
         }
         done = all_fin;
-        hp = h; gup = gu; gvp = gv; has_prev = true;
+        hp = h; has_prev = true;
+        if constexpr (LAYERS) { gup = gu; gvp = gv; }
+        else { up = u; vp = v; }
     }
     int status = bad;
 #pragma unroll
     for (int i = 0; i < SRH_MAX_DEPTHS; ++i) {
-        if (i >= a.nlayer) continue;
-        const bool span = valid[i] && bottom_ok && s[i].spanned;
+        if (i >= a.n) continue;
+        const bool span = bottom_ok && s[i].spanned;                        // (a layer left out never gets spanned)
         const bool ok = !bad && span && !isnan_(cu) && !isnan_(cv);
         if (!bad && !span) status |= ST_NO_LAYER;
         const double pos = ok ? s[i].pos : qnan(), neg = ok ? s[i].neg : qnan();
         st(a.pos[i], f64, c, pos); st(a.neg[i], f64, c, neg); st(a.tot[i], f64, c, pos + neg);
-        if (bad || !span) { st(a.shu[i], f64, c, qnan()); st(a.shv[i], f64, c, qnan()); }
+        if (LAYERS && (bad || !span)) { st(a.shu[i], f64, c, qnan()); st(a.shv[i], f64, c, qnan()); }
     }
     sti(a.status, c, status);
 }
+
+template <typename T> __global__ __launch_bounds__(256)
+void k_storm_relative_helicity(SrhArgs a) { helicity_walk<T, false>(a); }
+// (256, 4: four workgroups per CU, i.e. the compiler has to stay within 128 VGPRs)
+template <typename T> __global__ __launch_bounds__(256, 4)
+void k_helicity_layers(SrhArgs a) { helicity_walk<T, true>(a); }
 
 // ---- composites ---------------------------------------------------------------------------------------------------------
 // metpy.calc.significant_tornado; comparisons with NaN are false, so NaN propagates through the clips

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
         double X = log_tab<true>(es, P);
         X = (P == h.lp) ? h.xl : X;
         const bool cross = !skew && (last || P < h.lp);
-        if (isnan_(P) && !skew && !last) h.status |= 4;                            // NaN pressure below the LCL (see xparcel.h)
+        if (isnan_(P) && !skew && !last) h.status |= ST_NAN_PRESSURE;            // NaN pressure below the LCL (see xparcel.h)
         double tp, tvp;
         if (!skew) {                                                               // dry adiabat (pf.py:313, 767)
             tp = h.pt * dry_factor(es, KAPPA * (X - h.x0));
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
         const Lcl l = lcl(pc.p, pc.t, pc.td);
         const ScalarsOut &s = a.s[i];
         double *const slot = s_slot + i * (SLOT_FIELDS * SLOT_STRIDE) + threadIdx.x;
-        h.status = l.not_converged ? 2 : 0;
+        h.status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
         h.lp = l.p; h.lt = l.t; h.xl = qnan(); h.pt = pc.t; h.x0 = qnan(); h.vfac = 1.0;
         h.sat = false; h.done = true; h.first = DEAD;
         h.li_p = h.li_e = h.li_q = qnan(); h.li_done = false;

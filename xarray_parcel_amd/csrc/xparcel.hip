@@ -19,6 +19,11 @@
 #include "xp_kinematics.hpp"
 #include "xp_effective.hpp"
 
+static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_ST_LCL_NOT_CONVERGED &&
+              xp::ST_NAN_PRESSURE == XP_ST_NAN_PRESSURE && xp::ST_BAD_PRESSURE == XP_ST_BAD_PRESSURE &&
+              xp::ST_NO_LAYER == XP_ST_NO_LAYER && xp::ST_BAD_HEIGHT == XP_ST_BAD_HEIGHT &&
+              xp::ST_LAYER_OPEN == XP_ST_LAYER_OPEN, "the kernels' status bits are the ABI's");
+
 namespace {
 
 thread_local char g_err[512] = "";
@@ -125,6 +130,12 @@ struct Stager {
         any_host = true;
         *dev = d;
         return 0;
+    }
+    int out(int32_t *p, size_t bytes, int mem, int32_t **dev) {
+        void *d;
+        const int rc = out((void *)p, bytes, mem, &d);
+        *dev = (int32_t *)d;
+        return rc;
     }
     int finish() {
         HIP_TRY(hipGetLastError());
@@ -276,6 +287,12 @@ size_t rows_bytes(const xp_view *v, int64_t rows) { return (size_t)rows * (size_
 // an output laid out like view v (a device output keeps its input's strides), or as dense (rows, ncol)
 xp::OutView out_like(void *d, const xp_view *v) { return {d, v->lev_stride, v->col_stride}; }
 xp::OutView dense_out(void *d, int64_t ncol) { return {d, ncol, 1}; }
+// an output struct with a dtype and a mem of its own: present, and both equal to the views'
+template <typename O> int check_out(const char *entry, const O *out, const xp_view *v) {
+    if (!out) return fail(XP_E_ARG, "%s: out: null", entry);
+    if (out->dtype != v->dtype || out->mem != v->mem) return fail(XP_E_ARG, "%s: out: dtype / mem differ from the views'", entry);
+    return 0;
+}
 
 // every entry point switches to the library's device for its duration and leaves the calling thread's current device
 // as it found it (the caller -- torch, say -- may be working on another one)
@@ -315,7 +332,7 @@ int stage_scalars(Stager &st, xp_scalars_out *s, int64_t ncol, xp::ScalarsOut *o
     size_t fb = (size_t)ncol * esize(s->dtype), ib = (size_t)ncol * 4;
     int rc = 0;
 #define F_(dst, src) if (!rc) rc = st.out(s->src, fb, s->mem, &o->dst)
-#define I_(dst, src) if (!rc) { void *t_; rc = st.out(s->src, ib, s->mem, &t_); o->dst = (int32_t *)t_; }
+#define I_(dst, src) if (!rc) rc = st.out(s->src, ib, s->mem, &o->dst)
     F_(cape, cape); F_(cin, cin); F_(lcl_p, lcl_pressure); F_(lcl_t, lcl_temperature); F_(lcl_tv, lcl_virtual_temperature);
     F_(lfc_p, lfc_pressure); F_(lfc_t, lfc_temperature); F_(el_p, el_pressure); F_(el_t, el_temperature);
     I_(lfc_idx, lfc_index); I_(el_idx, el_index); I_(status, status); I_(parcel_idx, parcel_index);
@@ -522,6 +539,41 @@ int interp_levels(Stager &st, const xp_view *coords, int32_t nvar, const xp_view
         launch_interp_levels_v<decltype(z)>(nvar, ntarget, st, cv, m, coords->nlev, coords->ncol, (int)log_coords);
     });
     return 0;
+}
+
+// The body of xp_storm_relative_helicity and xp_storm_relative_helicity_layers (entry: which of them, for the messages).
+// bounds(a) is the caller's part: it checks its own bounds arguments and puts them into a -- the LAYERS ones as the caller's
+// pointers, staged here.
+template <bool LAYERS, typename O, typename F>
+int helicity(const char *entry, const xp_view *z, const xp_view *u, const xp_view *v, const void *surface_u,
+             const void *surface_v, const void *storm_u, const void *storm_v, int n, O *out, void *stream, F &&bounds) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    xp::SrhArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = check_views({{z, "height"}, {u, "u"}, {v, "v"}})) || (rc = check_out(entry, out, z)) || (rc = bounds(a))) return rc;
+    if (!surface_u != !surface_v) return fail(XP_E_ARG, "%s: surface wind: give both components or neither", entry);
+    const size_t cb = rows_bytes(z, 1);
+    if ((rc = stage_view(st, z, &a.z)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
+        (rc = st.in(surface_u, cb, z->mem, &a.sfc_u)) || (rc = st.in(surface_v, cb, z->mem, &a.sfc_v)) ||
+        (rc = st.in(storm_u, cb, z->mem, &a.storm_u)) || (rc = st.in(storm_v, cb, z->mem, &a.storm_v))) return rc;
+    if constexpr (LAYERS)
+        if ((rc = st.in(a.bottom_col, cb, z->mem, &a.bottom_col))) return rc;
+    for (int i = 0; i < n; ++i) {
+        if ((rc = st.out(out->positive[i], cb, out->mem, &a.pos[i])) || (rc = st.out(out->negative[i], cb, out->mem, &a.neg[i])) ||
+            (rc = st.out(out->total[i], cb, out->mem, &a.tot[i]))) return rc;
+        if constexpr (LAYERS)
+            if ((rc = st.in(a.top_col[i], cb, z->mem, &a.top_col[i])) || (rc = st.out(out->shear_u[i], cb, out->mem, &a.shu[i])) ||
+                (rc = st.out(out->shear_v[i], cb, out->mem, &a.shv[i]))) return rc;
+    }
+    if ((rc = st.out(out->status, (size_t)z->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = z->nlev; a.ncol = z->ncol; a.n = n;
+    by_dtype(z->dtype, [&](auto t) {
+        if constexpr (LAYERS) launch(xp::k_helicity_layers<decltype(t)>, z->ncol, st, a);
+        else launch(xp::k_storm_relative_helicity<decltype(t)>, z->ncol, st, a);
+    });
+    return st.finish();
 }
 
 bool multi_fused_ok(int32_t np, const xp_parcel *parcels, const xp_opts &o, const xp_profile_out *profiles) {
@@ -833,12 +885,13 @@ int xp_lcl(int64_t n, int32_t dtype, int32_t mem, const void *pp, const void *pt
     if (dtype != XP_F32 && dtype != XP_F64) return fail(XP_E_ARG, "xp_lcl: bad dtype");
     size_t b = (size_t)n * esize(dtype);
     const void *dp, *dt, *dtd;
-    void *op, *ot, *otv, *os;
+    void *op, *ot, *otv;
+    int32_t *os;
     int rc;
     if ((rc = st.in(pp, b, mem, &dp)) || (rc = st.in(pt, b, mem, &dt)) || (rc = st.in(ptd, b, mem, &dtd)) ||
         (rc = st.out(lp, b, mem, &op)) || (rc = st.out(lt, b, mem, &ot)) || (rc = st.out(ltv, b, mem, &otv)) ||
         (rc = st.out(status, (size_t)n * 4, mem, &os))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_lcl<decltype(z)>, n, st, n, dp, dt, dtd, op, ot, otv, (int32_t *)os); });
+    by_dtype(dtype, [&](auto z) { launch(xp::k_lcl<decltype(z)>, n, st, n, dp, dt, dtd, op, ot, otv, os); });
     return st.finish();
 }
 
@@ -964,8 +1017,7 @@ int xp_downdraft_cape(const xp_view *p, const xp_view *t, const xp_view *td, dou
     if (st.rc) return st.rc;
     int rc;
     if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}}))) return rc;
-    if (!out) return fail(XP_E_ARG, "xp_downdraft_cape: out: null");
-    if (out->dtype != p->dtype || out->mem != p->mem) return fail(XP_E_ARG, "xp_downdraft_cape: out: dtype / mem differ from the views'");
+    if ((rc = check_out("xp_downdraft_cape", out, p))) return rc;
     if (!(std::isfinite(layer_bottom) && layer_bottom > 0.0))
         return fail(XP_E_ARG, "xp_downdraft_cape: layer_bottom must be finite and positive");
     if (!(layer_depth > 0.0 && layer_depth < layer_bottom))
@@ -977,13 +1029,11 @@ int xp_downdraft_cape(const xp_view *p, const xp_view *t, const xp_view *td, dou
     TableSet ts;
     xp::DcapeArgs a;
     memset(&a, 0, sizeof(a));
-    void *status;
     if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) ||
         (rc = stage_view(st, td, &a.td)) || (rc = st.out(out->dcape, cb, out->mem, &a.dcape)) ||
         (rc = st.out(out->start_pressure, cb, out->mem, &a.p0)) || (rc = st.out(out->start_temperature, cb, out->mem, &a.t0)) ||
-        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &status)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status)) ||
         (rc = st.out(out->parcel_temperature, rows_bytes(p, p->nlev), out->mem, &a.prof))) return rc;
-    a.status = (int32_t *)status;
     a.nlev = p->nlev; a.ncol = p->ncol;
     a.bottom = layer_bottom; a.top = layer_bottom - layer_depth;
     a.table_mode = tm; a.tb = ts.tb; a.es_tab = ts.es;
@@ -999,8 +1049,7 @@ int xp_effective_inflow_layer(const xp_view *p, const xp_view *t, const xp_view 
     int rc;
     if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) || (rc = check_opts(opts))) return rc;
     if (z && (rc = check_views({{p, "pressure"}, {z, "height"}}))) return rc;
-    if (!out) return fail(XP_E_ARG, "xp_effective_inflow_layer: out: null");
-    if (out->dtype != p->dtype || out->mem != p->mem) return fail(XP_E_ARG, "xp_effective_inflow_layer: out: dtype / mem differ from the views'");
+    if ((rc = check_out("xp_effective_inflow_layer", out, p))) return rc;
     if (opts.humidity != XP_HUM_DEWPOINT) return fail(XP_E_ARG, "xp_effective_inflow_layer: humidity must be XP_HUM_DEWPOINT");
     if (!(std::isfinite(cape_min) && std::isfinite(cin_min))) return fail(XP_E_ARG, "xp_effective_inflow_layer: cape_min and cin_min must be finite");
     if (!(std::isfinite(search_depth) && search_depth > 0.0)) return fail(XP_E_ARG, "xp_effective_inflow_layer: search_depth must be finite and positive");
@@ -1009,16 +1058,14 @@ int xp_effective_inflow_layer(const xp_view *p, const xp_view *t, const xp_view 
     TableSet ts;
     xp::EffectiveArgs a;
     memset(&a, 0, sizeof(a));
-    void *bi, *ti, *status;
     if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) ||
         (rc = stage_view(st, td, &a.td)) || (z && (rc = stage_view(st, z, &a.z))) ||
         (rc = st.out(out->base_pressure, cb, out->mem, &a.base_p)) || (rc = st.out(out->top_pressure, cb, out->mem, &a.top_p)) ||
         (rc = st.out(out->base_height, cb, out->mem, &a.base_z)) || (rc = st.out(out->top_height, cb, out->mem, &a.top_z)) ||
-        (rc = st.out(out->base_index, ib, out->mem, &bi)) || (rc = st.out(out->top_index, ib, out->mem, &ti)) ||
-        (rc = st.out(out->status, ib, out->mem, &status)) ||
+        (rc = st.out(out->base_index, ib, out->mem, &a.base_idx)) || (rc = st.out(out->top_index, ib, out->mem, &a.top_idx)) ||
+        (rc = st.out(out->status, ib, out->mem, &a.status)) ||
         (rc = st.out(out->candidate_cape, rows_bytes(p, p->nlev), out->mem, &a.cand_cape)) ||
         (rc = st.out(out->candidate_cin, rows_bytes(p, p->nlev), out->mem, &a.cand_cin))) return rc;
-    a.base_idx = (int32_t *)bi; a.top_idx = (int32_t *)ti; a.status = (int32_t *)status;
     a.nlev = p->nlev; a.ncol = p->ncol;
     a.cape_min = cape_min; a.cin_min = cin_min; a.depth = search_depth;
     a.vtc = opts.virtual_temperature_correction; a.log_interp = opts.lcl_interp == XP_LCL_INTERP_LOG;
@@ -1034,19 +1081,16 @@ int xp_bunkers_storm_motion(const xp_view *p, const xp_view *u, const xp_view *v
     if (st.rc) return st.rc;
     int rc;
     if ((rc = check_views({{p, "pressure"}, {u, "u"}, {v, "v"}, {z, "height"}}))) return rc;
-    if (!out) return fail(XP_E_ARG, "xp_bunkers_storm_motion: out: null");
-    if (out->dtype != p->dtype || out->mem != p->mem) return fail(XP_E_ARG, "xp_bunkers_storm_motion: out: dtype / mem differ from the views'");
+    if ((rc = check_out("xp_bunkers_storm_motion", out, p))) return rc;
     const size_t cb = rows_bytes(p, 1);
     xp::StormMotionArgs a;
     memset(&a, 0, sizeof(a));
-    void *status;
     if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
         (rc = stage_view(st, z, &a.z)) || (rc = st.out(out->right_u, cb, out->mem, &a.right_u)) ||
         (rc = st.out(out->right_v, cb, out->mem, &a.right_v)) || (rc = st.out(out->left_u, cb, out->mem, &a.left_u)) ||
         (rc = st.out(out->left_v, cb, out->mem, &a.left_v)) || (rc = st.out(out->mean_u, cb, out->mem, &a.mean_u)) ||
         (rc = st.out(out->mean_v, cb, out->mem, &a.mean_v)) ||
-        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &status))) return rc;
-    a.status = (int32_t *)status;
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
     a.nlev = p->nlev; a.ncol = p->ncol;
     by_dtype(p->dtype, [&](auto t) { launch(xp::k_bunkers_storm_motion<decltype(t)>, p->ncol, st, a); });
     return st.finish();
@@ -1055,71 +1099,32 @@ int xp_bunkers_storm_motion(const xp_view *p, const xp_view *u, const xp_view *v
 int xp_storm_relative_helicity(const xp_view *z, const xp_view *u, const xp_view *v, const void *surface_u,
                                const void *surface_v, const void *storm_u, const void *storm_v, double bottom,
                                int32_t ndepth, const double *depth, xp_srh_out *out, void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    int rc;
-    if ((rc = check_views({{z, "height"}, {u, "u"}, {v, "v"}}))) return rc;
-    if (!out) return fail(XP_E_ARG, "xp_storm_relative_helicity: out: null");
-    if (out->dtype != z->dtype || out->mem != z->mem) return fail(XP_E_ARG, "xp_storm_relative_helicity: out: dtype / mem differ from the views'");
-    if (ndepth < 1 || ndepth > xp::SRH_MAX_DEPTHS) return fail(XP_E_ARG, "xp_storm_relative_helicity: ndepth must lie in 1 ... 4, got %d", (int)ndepth);
-    if (!depth) return fail(XP_E_ARG, "xp_storm_relative_helicity: depth: null");
-    for (int i = 0; i < ndepth; ++i)
-        if (!(std::isfinite(depth[i]) && depth[i] > 0.0))
-            return fail(XP_E_ARG, "xp_storm_relative_helicity: depth[%d] must be finite and positive", i);
-    if (!(std::isfinite(bottom) && bottom >= 0.0)) return fail(XP_E_ARG, "xp_storm_relative_helicity: bottom must be finite and >= 0");
-    if (!surface_u != !surface_v) return fail(XP_E_ARG, "xp_storm_relative_helicity: surface wind: give both components or neither");
-    const size_t cb = rows_bytes(z, 1);
-    xp::SrhArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = stage_view(st, z, &a.z)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
-        (rc = st.in(surface_u, cb, z->mem, &a.sfc_u)) || (rc = st.in(surface_v, cb, z->mem, &a.sfc_v)) ||
-        (rc = st.in(storm_u, cb, z->mem, &a.storm_u)) || (rc = st.in(storm_v, cb, z->mem, &a.storm_v))) return rc;
-    for (int i = 0; i < ndepth; ++i) {
-        a.top[i] = bottom + depth[i];
-        if ((rc = st.out(out->positive[i], cb, out->mem, &a.pos[i])) || (rc = st.out(out->negative[i], cb, out->mem, &a.neg[i])) ||
-            (rc = st.out(out->total[i], cb, out->mem, &a.tot[i]))) return rc;
-    }
-    void *status;
-    if ((rc = st.out(out->status, (size_t)z->ncol * 4, out->mem, &status))) return rc;
-    a.status = (int32_t *)status;
-    a.nlev = z->nlev; a.ncol = z->ncol; a.bottom = bottom; a.ndepth = ndepth;
-    by_dtype(z->dtype, [&](auto t) { launch(xp::k_storm_relative_helicity<decltype(t)>, z->ncol, st, a); });
-    return st.finish();
+    const char *const entry = "xp_storm_relative_helicity";
+    return helicity<false>(entry, z, u, v, surface_u, surface_v, storm_u, storm_v, ndepth, out, stream, [&](xp::SrhArgs &a) {
+        if (ndepth < 1 || ndepth > xp::SRH_MAX_DEPTHS) return fail(XP_E_ARG, "%s: ndepth must lie in 1 ... 4, got %d", entry, (int)ndepth);
+        if (!depth) return fail(XP_E_ARG, "%s: depth: null", entry);
+        for (int i = 0; i < ndepth; ++i)
+            if (!(std::isfinite(depth[i]) && depth[i] > 0.0)) return fail(XP_E_ARG, "%s: depth[%d] must be finite and positive", entry, i);
+        if (!(std::isfinite(bottom) && bottom >= 0.0)) return fail(XP_E_ARG, "%s: bottom must be finite and >= 0", entry);
+        a.bottom = bottom;
+        for (int i = 0; i < ndepth; ++i) a.top[i] = bottom + depth[i];
+        return 0;
+    });
 }
 
 int xp_storm_relative_helicity_layers(const xp_view *z, const xp_view *u, const xp_view *v, const void *surface_u,
                                       const void *surface_v, const void *storm_u, const void *storm_v, const void *bottom,
                                       int32_t nlayer, const void *const *top, xp_srh_layers_out *out, void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    int rc;
-    if ((rc = check_views({{z, "height"}, {u, "u"}, {v, "v"}}))) return rc;
-    if (!out) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: out: null");
-    if (out->dtype != z->dtype || out->mem != z->mem) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: out: dtype / mem differ from the views'");
-    if (nlayer < 1 || nlayer > xp::SRH_MAX_DEPTHS) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: nlayer must lie in 1 ... 4, got %d", (int)nlayer);
-    if (!bottom || !top) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: bottom / top: null");
-    for (int i = 0; i < nlayer; ++i)
-        if (!top[i]) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: top[%d]: null", i);
-    if (!surface_u != !surface_v) return fail(XP_E_ARG, "xp_storm_relative_helicity_layers: surface wind: give both components or neither");
-    const size_t cb = rows_bytes(z, 1);
-    xp::SrhLayersArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = stage_view(st, z, &a.z)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
-        (rc = st.in(surface_u, cb, z->mem, &a.sfc_u)) || (rc = st.in(surface_v, cb, z->mem, &a.sfc_v)) ||
-        (rc = st.in(storm_u, cb, z->mem, &a.storm_u)) || (rc = st.in(storm_v, cb, z->mem, &a.storm_v)) ||
-        (rc = st.in(bottom, cb, z->mem, &a.bottom))) return rc;
-    for (int i = 0; i < nlayer; ++i) {
-        if ((rc = st.in(top[i], cb, z->mem, &a.top[i])) ||
-            (rc = st.out(out->positive[i], cb, out->mem, &a.pos[i])) || (rc = st.out(out->negative[i], cb, out->mem, &a.neg[i])) ||
-            (rc = st.out(out->total[i], cb, out->mem, &a.tot[i])) || (rc = st.out(out->shear_u[i], cb, out->mem, &a.shu[i])) ||
-            (rc = st.out(out->shear_v[i], cb, out->mem, &a.shv[i]))) return rc;
-    }
-    void *status;
-    if ((rc = st.out(out->status, (size_t)z->ncol * 4, out->mem, &status))) return rc;
-    a.status = (int32_t *)status;
-    a.nlev = z->nlev; a.ncol = z->ncol; a.nlayer = nlayer;
-    by_dtype(z->dtype, [&](auto t) { launch(xp::k_helicity_layers<decltype(t)>, z->ncol, st, a); });
-    return st.finish();
+    const char *const entry = "xp_storm_relative_helicity_layers";
+    return helicity<true>(entry, z, u, v, surface_u, surface_v, storm_u, storm_v, nlayer, out, stream, [&](xp::SrhArgs &a) {
+        if (nlayer < 1 || nlayer > xp::SRH_MAX_DEPTHS) return fail(XP_E_ARG, "%s: nlayer must lie in 1 ... 4, got %d", entry, (int)nlayer);
+        if (!bottom || !top) return fail(XP_E_ARG, "%s: bottom / top: null", entry);
+        for (int i = 0; i < nlayer; ++i)
+            if (!top[i]) return fail(XP_E_ARG, "%s: top[%d]: null", entry, i);
+        a.bottom_col = bottom;
+        for (int i = 0; i < nlayer; ++i) a.top_col[i] = top[i];
+        return 0;
+    });
 }
 
 int xp_significant_tornado(int64_t n, int32_t dtype, int32_t mem, const void *sbcape, const void *lcl_height, const void *srh,

@@ -50,6 +50,15 @@ def _per_col(g, x):
     return x if x is None or np.ndim(x) == 0 else g.values(x)
 
 
+def _per_layer(g, res, names, dim, coord):
+    """The helicity results as a Dataset on the horizontal dims, or, with a coordinate, under the leading dim `dim`."""
+    if coord is None:
+        return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in names.items()})
+    coords = dict(g.coords, **{dim: coord})
+    return Dataset({name: DataArray(_host(res[k]), dims=(dim,) + g.dims, coords=coords, attrs=dict(_ATTRS[name]), name=name)
+                    for k, name in names.items()})
+
+
 def bunkers_storm_motion(pressure, u, v, height, vert_dim=VERT):
     """Bunkers right- and left-mover storm motion and the 0-6 km pressure-weighted mean wind of every column, from
     pressure [hPa], u, v [m/s] and height [m] on one vertical (pressure on the wind levels).  Returns a Dataset on the
@@ -70,11 +79,7 @@ def storm_relative_helicity(height, u, v, depth, vert_dim=VERT, bottom=0.0, stor
     res = _device(_api.storm_relative_helicity, g.values(height), g.values(u), g.values(v), depth, bottom=bottom,
                   storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), surface_u=_per_col(g, surface_u),
                   surface_v=_per_col(g, surface_v))
-    if np.ndim(depth) == 0:
-        return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _SRH_NAMES.items()})
-    coords = dict(g.coords, srh_depth=np.asarray(depth, dtype=np.float64))
-    return Dataset({name: DataArray(_host(res[k]), dims=('srh_depth',) + g.dims, coords=coords, attrs=dict(_ATTRS[name]),
-                                    name=name) for k, name in _SRH_NAMES.items()})
+    return _per_layer(g, res, _SRH_NAMES, 'srh_depth', None if np.ndim(depth) == 0 else np.asarray(depth, dtype=np.float64))
 
 
 def effective_inflow_layer(pressure, temperature, dewpoint, height=None, vert_dim=VERT, cape_min=100.0, cin_min=-250.0,
@@ -108,11 +113,7 @@ def storm_relative_helicity_layers(height, u, v, bottom, top, vert_dim=VERT, sto
     res = _device(_api.storm_relative_helicity_layers, g.values(height), g.values(u), g.values(v), _per_col(g, bottom), tops,
                   storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), surface_u=_per_col(g, surface_u),
                   surface_v=_per_col(g, surface_v))
-    if not many:
-        return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _LAYER_NAMES.items()})
-    coords = dict(g.coords, srh_layer=np.arange(len(top)))
-    return Dataset({name: DataArray(_host(res[k]), dims=('srh_layer',) + g.dims, coords=coords, attrs=dict(_ATTRS[name]),
-                                    name=name) for k, name in _LAYER_NAMES.items()})
+    return _per_layer(g, res, _LAYER_NAMES, 'srh_layer', np.arange(len(top)) if many else None)
 
 
 def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):

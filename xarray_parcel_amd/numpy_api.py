@@ -754,6 +754,28 @@ def bunkers_storm_motion(pressure, u, v, height):
     return res
 
 
+def _helicity(entry, height, u, v, per_col, storm, surface, n, many, keys, out_type, bounds):
+    """What the two helicity calls share: the _Call (CUDA tensors among the per-column arguments decide the device), the
+    storm and surface wind per column, one output per key and layer (with a leading axis if `many`) and the status.
+    bounds(cols), cols being per_col as per-column arrays: the entry point's own arguments between the storm motion and the
+    output struct."""
+    assert (surface[0] is None) == (surface[1] is None), 'surface_u, surface_v: give both or neither'
+    c = _Call(height, u, v, *[x for x in (*per_col, *storm, *surface) if _is_torch(x)])
+    z, wu, wv = c.ins[:3]
+    assert z.shape == wu.shape == wv.shape, 'height, u, v must share a shape'
+    sfc = [None, None] if surface[0] is None else [c.per_col(x) for x in surface]
+    res = {k: c.out(((n,) if many else ()) + c.hshape) for k in keys}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = out_type(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in keys:
+        arr = getattr(out, k)
+        for i in range(n):
+            arr[i] = _ptr(res[k][i] if many else res[k])
+    cols = [c.per_col(x) for x in per_col]
+    c.run(entry, c.view(z), c.view(wu), c.view(wv), *sfc, *[c.per_col(x) for x in storm], *bounds(cols), out)
+    return res
+
+
 def storm_relative_helicity(height, u, v, depth, bottom=0.0, storm_u=0.0, storm_v=0.0, surface_u=None, surface_v=None):
     """metpy.calc.storm_relative_helicity for every column (xp_storm_relative_helicity): height [m], u, v [m/s] (nlev, ...);
     heights are taken relative to the lowest valid level, or, with surface_u / surface_v, as heights above the surface
@@ -763,26 +785,11 @@ def storm_relative_helicity(height, u, v, depth, bottom=0.0, storm_u=0.0, storm_
     bunkers_storm_motion can be passed straight back as the storm motion (e.g. storm_u=bm['right_u']).  Returns a dict of
     'positive', 'negative', 'total' [m^2/s^2] and 'status' (XP_ST_NO_LAYER: some depth is not spanned, its values NaN;
     ST_BAD_HEIGHT: heights out of order, everything NaN)."""
-    many = np.ndim(depth) > 0
     depths = [float(d) for d in np.atleast_1d(depth)]
     assert 1 <= len(depths) <= L.SRH_MAX_DEPTHS, 'depth: one to four depths'
-    assert (surface_u is None) == (surface_v is None), 'surface_u, surface_v: give both or neither'
-    per = [x for x in (storm_u, storm_v, surface_u, surface_v) if _is_torch(x)]     # (CUDA tensors decide the device)
-    c = _Call(height, u, v, *per)
-    z, wu, wv = c.ins[:3]
-    assert z.shape == wu.shape == wv.shape, 'height, u, v must share a shape'
-    sfc = [None, None] if surface_u is None else [c.per_col(surface_u), c.per_col(surface_v)]
-    shape = ((len(depths),) if many else ()) + c.hshape
-    res = {k: c.out(shape) for k in L.SRH_OUT}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = L.SrhOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in L.SRH_OUT:
-        arr = getattr(out, k)
-        for i in range(len(depths)):
-            arr[i] = _ptr(res[k][i] if many else res[k])
-    c.run('xp_storm_relative_helicity', c.view(z), c.view(wu), c.view(wv), *sfc, c.per_col(storm_u), c.per_col(storm_v),
-          float(bottom), len(depths), (C.c_double * len(depths))(*depths), out)
-    return res
+    return _helicity('xp_storm_relative_helicity', height, u, v, (), (storm_u, storm_v), (surface_u, surface_v), len(depths),
+                     np.ndim(depth) > 0, L.SRH_OUT, L.SrhOut,
+                     lambda cols: (float(bottom), len(depths), (C.c_double * len(depths))(*depths)))
 
 
 def storm_relative_helicity_layers(height, u, v, bottom, top, storm_u=0.0, storm_v=0.0, surface_u=None, surface_v=None):
@@ -797,26 +804,11 @@ def storm_relative_helicity_layers(height, u, v, bottom, top, storm_u=0.0, storm
     many = isinstance(top, (list, tuple))
     tops = list(top) if many else [top]
     assert 1 <= len(tops) <= L.SRH_MAX_DEPTHS, 'top: one to four arrays'
-    assert (surface_u is None) == (surface_v is None), 'surface_u, surface_v: give both or neither'
-    per = [x for x in (bottom, *tops, storm_u, storm_v, surface_u, surface_v) if _is_torch(x)]   # (CUDA tensors decide the device)
-    c = _Call(height, u, v, *per)
-    z, wu, wv = c.ins[:3]
-    assert z.shape == wu.shape == wv.shape, 'height, u, v must share a shape'
-    sfc = [None, None] if surface_u is None else [c.per_col(surface_u), c.per_col(surface_v)]
-    tps = [c.per_col(x) for x in tops]
-    shape = ((len(tops),) if many else ()) + c.hshape
-    res = {k: c.out(shape) for k in L.SRH_LAYERS_OUT}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = L.SrhLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in L.SRH_LAYERS_OUT:
-        arr = getattr(out, k)
-        for i in range(len(tops)):
-            arr[i] = _ptr(res[k][i] if many else res[k])
-    c.run('xp_storm_relative_helicity_layers', c.view(z), c.view(wu), c.view(wv), *sfc, c.per_col(storm_u), c.per_col(storm_v),
-          c.per_col(bottom), len(tops), (C.c_void_p * len(tops))(*map(_ptr, tps)), out)
+    res = _helicity('xp_storm_relative_helicity_layers', height, u, v, (bottom, *tops), (storm_u, storm_v),
+                    (surface_u, surface_v), len(tops), many, L.SRH_LAYERS_OUT, L.SrhLayersOut,
+                    lambda cols: (cols[0], len(tops), (C.c_void_p * len(tops))(*map(_ptr, cols[1:]))))
     hyp = torch.hypot if _is_torch(res['shear_u']) else np.hypot
-    res['shear_magnitude'] = hyp(res['shear_u'], res['shear_v'])
-    return {**{k: res[k] for k in L.SRH_LAYERS_OUT}, 'shear_magnitude': res['shear_magnitude'], 'status': res['status']}
+    return {**{k: res[k] for k in L.SRH_LAYERS_OUT}, 'shear_magnitude': hyp(res['shear_u'], res['shear_v']), 'status': res['status']}
 
 
 def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):
