@@ -12,8 +12,8 @@
 // sits the candidate out, and a ballot ends the loop when no lane has work left.  Every lane that takes part in a candidate
 // starts at level k, so the level loads stay level-major and coalesced and the inner loop bound is scalar.  The LCL differs
 // per lane; each lane feeds exactly one node per inner iteration -- below its LCL the level just loaded, at the crossing the
-// LCL node instead (the level waits), above it the level that has been waiting -- which is k_cape_cin's phase A, node for
-// node, including its tie rules (LCL_SNAP, the saturated parcel, a level on the LCL).
+// LCL node instead (the level waits), above it the level that has been waiting: xp::below_lcl_node (xp_lcl_node.hpp), the
+// node k_cape_cin and the fused kernel feed there, tie rules included, with the RK4 / table moist adiabat.
 #pragma once
 #include "xp_kernels.hpp"
 
@@ -42,18 +42,27 @@ XP_DEV void lift_candidate(const EffectiveArgs &a, const double *es, double *slo
     status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
     cape = 0.0; cin = 0.0;
     if (isnan_(l.p)) return;                                               // a NaN LCL blanks the profile: CAPE = CIN = 0.0
-    const double vf_parcel = need_w ? virt_factor_tab(es, pc_t, pc_td, pc_p, false) : 1.0;
-    const double x_lcl = log(l.p);
-    const double x0 = (pc_p == l.p) ? x_lcl : log_tab<true>(es, pc_p);
+    BelowLcl n;
+    n.lp = l.p; n.x_lcl = log(l.p); n.t0 = pc_t; n.sat = (l.p == pc_p);
+    n.vfac = need_w ? virt_factor_tab(es, pc_t, pc_td, pc_p, false) : 1.0;
+    n.x0 = n.sat ? n.x_lcl : log_tab<true>(es, pc_p);
 
-    Scan sc; sc.init(l.p, x_lcl, pos_neg, slot);
+    Scan sc; sc.init(l.p, n.x_lcl, pos_neg, slot);
     sc.slot[SL_LCL_T * SLOT_STRIDE] = vtc ? l.tv : l.t;
     Moist m;
-    m.start(es, l.p, x_lcl, l.t, TABLE, a.tb);
-    double *const br = sc.slot;
-    br[SL_BR_P * SLOT_STRIDE] = qnan(); br[SL_BR_X * SLOT_STRIDE] = qnan(); br[SL_BR_T * SLOT_STRIDE] = qnan(); br[SL_BR_TD * SLOT_STRIDE] = qnan();
+    m.start(es, l.p, n.x_lcl, l.t, TABLE, a.tb);
+    clear_bracket(sc.slot);
+    // The moist adiabat by the RK4 stepper or the reference's tables.  A level exactly on the LCL comes before the stepper
+    // has moved, and Moist::at at its own start point returns the start temperature, l.t, as it stands: taken directly (the
+    // stepper inlined a second time cost the RK4 kernels 2-4 VGPRs and 450 instructions); the tables are interpolated there.
+    auto adiabat = [&](bool above, double P, double X, double &tp, double &tvp) __attribute__((always_inline)) {
+        if (!TABLE && !above) { tp = l.t; return; }
+        tp = m.at(P, X, a.tb);
+        tvp = need_w ? virt(tp, mix_of_e(TABLE ? es_tab(es, tp) : m.e, P)) : tp;
+    };
 
     bool lcl_done = false;
+    int unreported = 0;                                                    // (a NaN pressure below the LCL is not reported here)
     double sP = qnan(), sT = qnan(), sM = qnan();                          // the level that waits while the LCL node is fed
     // one-level look-ahead, kept in the input type until it is used (see select_mu_exact)
     T np_ = ldr<T>(a.p, k0, c), nt_ = ldr<T>(a.t, k0, c), ntd_ = ldr<T>(a.td, k0, c);
@@ -61,57 +70,8 @@ XP_DEV void lift_candidate(const EffectiveArgs &a, const double *es, double *slo
         const bool last = k >= nlev;
         const double Pc = last ? qnan() : (double)np_, Tc = last ? qnan() : (double)nt_, Mc = last ? qnan() : (double)ntd_;
         if (k + 1 < nlev) { np_ = ldr<T>(a.p, k + 1, c); nt_ = ldr<T>(a.t, k + 1, c); ntd_ = ldr<T>(a.td, k + 1, c); }
-        // ---- k_cape_cin's `source`, for a dewpoint view without profile output
         const bool skew = lcl_done;
-        double P = skew ? sP : Pc, T_ = skew ? sT : Tc;
-        double Td_ = skew ? sM : Mc;
-        if (fabs(P - l.p) <= LCL_SNAP * l.p) P = l.p;                       // on the LCL (see xp::lcl)
-        double X = log_tab<true>(es, P);
-        X = (P == l.p) ? x_lcl : X;
-        const bool cross = !skew && (last || P < l.p);
-        // the moist adiabat: above the LCL, and at a level exactly on it (there the state does not move: X == x_lcl)
-        const bool on_lcl = need_w && !skew && !cross && (P == l.p);
-        double tm = qnan();
-        if (skew || on_lcl) tm = m.at(P, X, a.tb);
-        double tp, tvp;
-        if (!skew) {                                                       // dry adiabat
-            tp = pc_t * dry_factor(es, KAPPA * (X - x0));
-            tvp = need_w ? tp * vf_parcel : tp;
-        } else {
-            tp = tm;
-            tvp = need_w ? virt(tp, mix_of_e(TABLE ? es_tab(es, tp) : m.e, P)) : tp;
-        }
-        if (cross) {                                                       // this lane's node is its LCL
-            const double at = log_interp ? x_lcl : l.p;
-            const double pb = br[SL_BR_P * SLOT_STRIDE], xb = br[SL_BR_X * SLOT_STRIDE], tb_ = br[SL_BR_T * SLOT_STRIDE], tdb = br[SL_BR_TD * SLOT_STRIDE];
-            lds_wait_all();
-            double cb = log_interp ? xb : pb, ca = log_interp ? X : P;
-            double ta2 = T_, tda2 = Td_;
-            if (pb == l.p) { ca = cb; ta2 = tb_; tda2 = tdb; }             // a level sits exactly on the LCL
-            const double te = interp_rule(tb_, ta2, at, cb, ca), tde = interp_rule(tdb, tda2, at, cb, ca);
-            const double lsel = br[SL_LCL_T * SLOT_STRIDE];
-            P = l.p; X = x_lcl; T_ = te; Td_ = tde;
-            tp = lsel; tvp = lsel;
-        }
-        double tve = T_;
-        if (need_w) {                                                      // one wave-uniform range test for the two e_s
-            if (__builtin_amdgcn_ballot_w64(!all_in_table(umax_(table_dist(T_), table_dist(Td_)))) == 0ull) tve = virt_env_tab(es, T_, Td_, P, true);
-            else { double tq = T_; asm volatile("" : "+v"(tq)); tve = virt_env_tab(es, tq, Td_, P, false); }
-        }
-        // saturated parcel (LCL == parcel level): the reference's own operation order decides the sign at the LCL node
-        const bool tie = need_w && cross && (l.p == pc_p);
-        if (tie) { double q = T_; asm volatile("" : "+v"(q)); tve = virt_ref(q, Td_, l.p); }
-        // a level exactly ON the LCL pairs the dry temperature with the saturation mixing ratio at the moist-adiabat temperature
-        if (on_lcl) {
-            double ta = tm;
-            asm volatile("" : "+v"(ta));
-            const double ea = es_ref(ta);
-            tvp = tp * (1.0 + VT_EPS * (EPS * ea / (P - ea)));
-            tve = virt_ref(T_, Td_, P);
-        }
-        sc.template node<false, false>(P, X, vtc ? tvp : tp, vtc ? tve : T_, cross);
-        if (!isnan_(P) && !skew && !cross) { br[SL_BR_P * SLOT_STRIDE] = P; br[SL_BR_X * SLOT_STRIDE] = X; br[SL_BR_T * SLOT_STRIDE] = T_; br[SL_BR_TD * SLOT_STRIDE] = Td_; }
-        lcl_done = skew || cross;
+        lcl_done = below_lcl_node(es, sc, n, vtc, log_interp, skew ? sP : Pc, skew ? sT : Tc, skew ? sM : Mc, skew, last, unreported, adiabat);
         sP = Pc; sT = Tc; sM = Mc;
     }
     const Scan::Result r = sc.finish(a.post_zero != 0);

@@ -2,31 +2,12 @@
 // x-adjacent columns so every level read is one coalesced 256 B (fp32) / 512 B (fp64) request per
 // array (layout (lev, y, x), col_stride == 1).  No MFMA: the path is an elementwise + per-column scan
 // (SURVEY.md 8d); LDS holds the e_s / ln lookup tables and the per-thread slots of the scan (xp_device.hpp).
+// Views, stores and the node at or below the LCL: xp_lcl_node.hpp.
 #pragma once
-#include "xp_device.hpp"
+#include "xp_lcl_node.hpp"
 
 namespace xp {
 
-struct View { const void *data; int64_t ls, cs; };           // element strides
-struct OutView { void *data; int64_t ls, cs; };
-
-template <typename T> XP_DEV double ld(const View &v, int64_t k, int64_t c) {
-    return (double)((const T *)v.data)[k * v.ls + c * v.cs];
-}
-template <typename T> XP_DEV T ldr(const View &v, int64_t k, int64_t c) { return ((const T *)v.data)[k * v.ls + c * v.cs]; }   // raw: no conversion at the load
-template <typename T> XP_DEV double ld1(const void *p, int64_t c) { return (double)((const T *)p)[c]; }
-XP_DEV void st(void *p, int f64, int64_t i, double v) {
-    if (p == nullptr) return;
-    if (f64) ((double *)p)[i] = v; else ((float *)p)[i] = (float)v;
-}
-XP_DEV void sti(int32_t *p, int64_t i, int v) { if (p) p[i] = v; }
-
-struct ScalarsOut {
-    void *cape, *cin, *lcl_p, *lcl_t, *lcl_tv, *lfc_p, *lfc_t, *el_p, *el_t;
-    int32_t *lfc_idx, *el_idx, *status, *parcel_idx;
-    void *par_p, *par_t, *par_td;
-    int f64;
-};
 struct ProfileOut {
     void *v[6];            // p, t_parcel, tv_parcel, t_env, tv_env, td_env (each may be null)
     int64_t nlev_out, ls, cs;
@@ -61,8 +42,6 @@ enum { PM_SURFACE = 0, PM_MU = 1, PM_ML = 2, PM_EXPLICIT = 3 };
 template <bool HUM> XP_DEV double as_dewpoint(const double *es, double p, double t, double m) {
     return HUM ? dewpoint_from_q_tab(es, p, t, m) : m;
 }
-
-struct Parcel { double p, t, td; int64_t first; int idx; bool prepend; };
 
 // most_unstable_parcel (pf.py:102-135 with get_layer pf.py:63-100 and bound_pressure pf.py:208-227):
 // highest theta-e in the lowest `depth` hPa, first maximum wins; the layer top is the level closest to
@@ -159,10 +138,6 @@ template <typename T, bool HUM> XP_DEV Parcel select_mu(const CapeArgs &a, int64
 template <typename T> XP_DEV void layer_mean_step(double &sum, double p0, double v0, double p1, double v1) {
     double a = fabs(p1 - p0) * ((v0 + v1) * 0.5);
     if (!isnan_(a)) sum += a;
-}
-XP_DEV double interp_rule(double xb, double xa, double at, double cb, double ca) {   // pf.py:1798-1806
-    double res = xb + (xa - xb) * fdiv(at - cb, ca - cb);
-    return (xb == xa) ? xb : res;
 }
 template <typename T, bool HUM> XP_DEV Parcel select_ml(const CapeArgs &a, int64_t c, const double *es, const double depth) {
     Parcel r; r.p = r.t = r.td = qnan(); r.first = a.nlev; r.idx = -1; r.prepend = true;
@@ -309,19 +284,13 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
                 for (int v = 0; v < 6; ++v) st(a.prof.v[v], a.prof.f64, j * a.prof.ls + c * a.prof.cs, qnan());
             st(a.prof.li, a.prof.f64, c, qnan());
         }
-        st(s.cape, s.f64, c, 0.0); st(s.cin, s.f64, c, 0.0);
-        st(s.lcl_p, s.f64, c, l.p); st(s.lcl_t, s.f64, c, l.t); st(s.lcl_tv, s.f64, c, l.tv);
-        st(s.lfc_p, s.f64, c, qnan()); st(s.lfc_t, s.f64, c, qnan()); st(s.el_p, s.f64, c, qnan()); st(s.el_t, s.f64, c, qnan());
-        sti(s.lfc_idx, c, -1); sti(s.el_idx, c, -1); sti(s.status, c, status); sti(s.parcel_idx, c, pc.idx);
-        st(s.par_p, s.f64, c, pc.p); st(s.par_t, s.f64, c, pc.t); st(s.par_td, s.f64, c, pc.td);
+        store_blank_column(s, c, pc, l, status);
         if (FAMILY) a.flags[c] = 0;
         return;
     }
 
     // everything known before the scan is stored now, so that it does not occupy registers through the level loop
-    st(s.lcl_p, s.f64, c, l.p); st(s.lcl_t, s.f64, c, l.t); st(s.lcl_tv, s.f64, c, l.tv);
-    sti(s.parcel_idx, c, pc.idx);
-    st(s.par_p, s.f64, c, pc.p); st(s.par_t, s.f64, c, pc.t); st(s.par_td, s.f64, c, pc.td);
+    store_parcel_and_lcl(s, c, pc, l);
     const double vf_parcel = need_w ? virt_factor_tab(es, pc.t, pc.td, pc.p, false) : 1.0;   // 1 + 0.608 w of the parcel (pf.py:748, 767)
     // ln p bookkeeping.  Levels use the table logarithm; the LCL node uses the library log (its crossing tests
     // "p* < p_lcl" then break ties as on the CPU); a level that sits exactly on the LCL pressure takes the LCL's
@@ -423,21 +392,8 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     };
 
     bool lcl_done = false;
-    // last valid-pressure node at or below the LCL (the lower bracket of the LCL interpolation): LDS slots, written in
-    // phase A only
-    double *const br = sc.slot;
-    br[SL_BR_P * SLOT_STRIDE] = qnan(); br[SL_BR_X * SLOT_STRIDE] = qnan(); br[SL_BR_T * SLOT_STRIDE] = qnan(); br[SL_BR_TD * SLOT_STRIDE] = qnan();
-    // environment at the LCL: bracketing-level interpolation in ln p or p (pf.py:897-906, 1758-1811) between the last
-    // valid level at or below the LCL (the br slots) and the first level above it
-    auto lcl_environment = [&](double pa, double xa, double ta, double tda, double &te, double &tde) __attribute__((always_inline)) {
-        double at = log_interp ? x_lcl : l.p;
-        const double pb = br[SL_BR_P * SLOT_STRIDE], xb = br[SL_BR_X * SLOT_STRIDE], tb_ = br[SL_BR_T * SLOT_STRIDE], tdb = br[SL_BR_TD * SLOT_STRIDE];
-        lds_wait_all();
-        double cb = log_interp ? xb : pb, ca = log_interp ? xa : pa;
-        double ta2 = ta, tda2 = tda;
-        if (pb == l.p) { ca = cb; ta2 = tb_; tda2 = tdb; }                 // a level sits exactly on the LCL
-        te = interp_rule(tb_, ta2, at, cb, ca); tde = interp_rule(tdb, tda2, at, cb, ca);
-    };
+    double *const br = sc.slot;                                            // the bracket slots (xp_lcl_node.hpp), written in phase A only
+    clear_bracket(br);
     // parcel temperature / mixing ratio above the LCL; e_s(T) rides along with the RK4 state in exact mode
     // `Q`: with specific-humidity input and no profile output the environment's mixing ratio is q / (1 - q) itself --
     // the reference's w = RH * w_s(p, T) with RH = e_s(Td) / e_s(T) (pf.py:698-704) undoes exactly the q -> Td chain --
@@ -502,6 +458,9 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     // (some lane of 64 crosses at nearly every level there: 13.4 against 6.2 us per level and Mi-column, measured).
     // One iteration past the top level (`last`, nothing loaded) flushes the waiting level; a column whose LCL lies above
     // the top level feeds its LCL node there, with no upper bracket (NaN environment).
+    // The rules of the node -- snap onto the LCL, bracket slots, environment at the LCL, environment Tv behind one range
+    // test, the two ties -- are the functions of xp_lcl_node.hpp, which the kernels without profile output take composed
+    // (xp::below_lcl_node); `source` composes them itself around PROFILE, LAZY, TRACK, HUM / PREP and the `Q` shortcut.
     double sP = qnan(), sT = qnan(), sM = qnan();
     // specific-humidity input, mixed-layer parcel: the prepended parcel node carries a DEWPOINT; when it is the waiting
     // level (a supersaturated mixed parcel lies above its own LCL) it must not be converted again, and it has to be fed by
@@ -513,9 +472,8 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
         double P = skew ? sP : Pc, T_ = skew ? sT : Tc;
         const double M_ = skew ? sM : Mc;
         double Td_ = (decltype(raw)::value && !(PREP && skew && s_is_td)) ? as_dewpoint<HUM>(es, P, T_, M_) : M_;
-        if (fabs(P - l.p) <= LCL_SNAP * l.p) P = l.p;                       // on the LCL (see xp::lcl)
-        double X = log_tab<true>(es, P);
-        X = (P == l.p) ? x_lcl : X;
+        double X;
+        snap_to_lcl(es, l.p, x_lcl, P, X);
         if (TRACK) cur_k = skew ? kc - 1 : kc;
         const bool cross = !skew && (last || P < l.p);
         if (!LEAN && isnan_(P) && !skew && !last) status |= ST_NAN_PRESSURE;   // NaN pressure below the LCL (see xparcel.h)
@@ -534,34 +492,17 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
         }
         if (cross) {                                                       // (a plain divergent branch: saveexec + execz)          // this lane's node is its LCL
             double te, tde;
-            lcl_environment(P, X, T_, Td_, te, tde);
+            lcl_environment(br, log_interp, l.p, x_lcl, P, X, T_, Td_, te, tde);
             // without profile output the scan only sees the temperature picked by the correction switch, which sits in
             // the SL_LCL_T slot: neither LCL temperature has to stay in registers through the loop
             const double lsel = br[SL_LCL_T * SLOT_STRIDE];
             P = l.p; X = x_lcl; T_ = te; Td_ = tde;
             tp = PROFILE ? l.t : lsel; tvp = PROFILE ? l.tv : lsel;
         }
-        double tve = T_;                                                   // pf.py:839-843, 911-920
-        if (need_w) {                                                      // one wave-uniform range test for the two e_s, as in phase B
-            if (__builtin_amdgcn_ballot_w64(!all_in_table(umax_(table_dist(T_), table_dist(Td_)))) == 0ull) tve = virt_env_tab<LEAN && !PROFILE>(es, T_, Td_, P, true);
-            else { double tq = T_; asm volatile("" : "+v"(tq)); tve = virt_env_tab(es, tq, Td_, P, false); }
-        }
-        // For a saturated parcel (LCL == parcel level) the sign of parcel-minus-environment at the LCL node is rounding
-        // noise of exactly the reference's expressions: those columns evaluate them in its operation order.
-        const bool tie = need_w && cross && (l.p == pc.p);
-        if (tie) { double q = T_; asm volatile("" : "+v"(q)); tve = virt_ref(q, Td_, l.p); }
-        // A level exactly ON the LCL pairs the dry temperature with the saturation mixing ratio at the moist-adiabat
-        // temperature (pf.py:773 uses <=).  For a saturated parcel this is the parcel's own level and the same holds.
-        const bool on_lcl = need_w && !cross && (P == l.p);
-        if (on_lcl) {
-            double ta = FAMILY ? l.t : m.at(P, X, a.tb);
-            asm volatile("" : "+v"(ta));
-            double ea = es_ref(ta);
-            tvp = tp * (1.0 + VT_EPS * (EPS * ea / (P - ea)));
-            tve = virt_ref(T_, Td_, P);
-        }
+        double tve = need_w ? virt_env_ranged<LEAN && !PROFILE>(es, T_, Td_, P) : T_;
+        lcl_ties(need_w, cross, l.p == pc.p, P, l.p, tp, T_, Td_, [&]() __attribute__((always_inline)) { return FAMILY ? l.t : m.at(P, X, a.tb); }, tvp, tve);
         emit(std::false_type{}, P, X, tp, tvp, T_, tve, Td_, cross);
-        if (!isnan_(P) && !skew && !cross) { br[SL_BR_P * SLOT_STRIDE] = P; br[SL_BR_X * SLOT_STRIDE] = X; br[SL_BR_T * SLOT_STRIDE] = T_; br[SL_BR_TD * SLOT_STRIDE] = Td_; }
+        if (!isnan_(P) && !skew && !cross) store_bracket(br, P, X, T_, Td_);
         lcl_done = skew || cross;
         sP = Pc; sT = Tc; sM = Mc;
         if (PREP) s_is_td = !decltype(raw)::value;
@@ -709,32 +650,13 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     typedef const CapeArgs __attribute__((address_space(4))) *KernargPtr;
     KernargPtr late = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(late) : : "memory");
-    const int of64 = late->s.f64;
     Scan::Result r = sc.finish(late->post_zero != 0);
-    status |= r.status;
     if (FAMILY) late->flags[c] = fam.bad ? 1 : 0;
-    st(late->s.cape, of64, c, r.cape); st(late->s.cin, of64, c, r.cin);
-    st(late->s.lfc_p, of64, c, r.lfc_p); st(late->s.lfc_t, of64, c, r.lfc_t);
-    st(late->s.el_p, of64, c, r.el_p); st(late->s.el_t, of64, c, r.el_t);
-    sti(late->s.lfc_idx, c, r.lfc_idx); sti(late->s.el_idx, c, r.el_idx); sti(late->s.status, c, status);
+    store_scan_result(late->s, c, r, status | r.status);
     };   // column
 
-    if (PERSIST) {
-        // Every workgroup owns a contiguous share of the grid's 64-column tiles and its wavefronts take them one by one
-        // from a counter in LDS.  (One device-wide counter in memory was measured first: same-address atomics execute at
-        // the memory side one after the other, ~50 ns each -- 12 000 of them are most of c2's 0.7 ms.)
-        const int64_t ntiles = (a.ncol + 63) >> 6;
-        const int t0 = (int)(ntiles * blockIdx.x / gridDim.x), t1 = (int)(ntiles * (blockIdx.x + 1) / gridDim.x);
-        int tile = t0 + (int)(threadIdx.x >> 6);                            // s_next starts behind these (set before the staging barrier)
-        while (tile < t1) {
-            const int64_t c = ((int64_t)tile << 6) + (threadIdx.x & 63);
-            if (c < a.ncol) column(c);
-            if ((threadIdx.x & 63) == 0) tile = t0 + atomicAdd(&s_next, 1);
-            tile = __builtin_amdgcn_readfirstlane(tile);
-        }
-    } else {
-        column(c0);
-    }
+    if (PERSIST) persistent_tiles(a.ncol, s_next, column);
+    else column(c0);
 }
 
 // parcels only (most_unstable_parcel pf.py:102, mixed_parcel pf.py:229)
@@ -870,8 +792,8 @@ void k_lfc_el(View pv, View parv, View envv, int64_t nlev, int64_t ncol, const v
         sc.node(P, flog(P), ld<T>(parv, k, c), ld<T>(envv, k, c), false);
     }
     Scan::Result r = sc.finish(false);
-    st(s.lfc_p, s.f64, c, r.lfc_p); st(s.lfc_t, s.f64, c, r.lfc_t); st(s.el_p, s.f64, c, r.el_p); st(s.el_t, s.f64, c, r.el_t);
-    sti(s.lfc_idx, c, r.lfc_idx); sti(s.el_idx, c, r.el_idx); sti(s.status, c, r.status);
+    s.cape = s.cin = nullptr;                                              // lfc_el has no CAPE / CIN
+    store_scan_result(s, c, r, r.status);
 }
 
 // cape_cin_base (pf.py:1291-1392) on caller-supplied profiles and LFC/EL: direct form (LFC and EL are
