@@ -1,5 +1,7 @@
 """Several parcels of one grid in one pass (xp_cape_cin_multi, csrc/xp_multi.hpp): the fused kernel against separate
 xp_cape_cin calls -- bit for bit, every output -- and against the oracle."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -58,11 +60,11 @@ def test_fused_truncated_and_ragged_shapes(xa):
     """1 ... 8 levels (LCL above the top, flush iteration), column counts around the wavefront / workgroup sizes, and a
     grid large enough for persistent wavefronts."""
     full = synth.columns(nlev=64, ncol=6000, seed=41, nan_fraction=0.08, dtype=np.float64)
-    for nlev in (1, 2, 3, 5, 8):
-        p, t, td = (np.ascontiguousarray(v[:nlev]) for v in full)
+    for nlev, dtype in itertools.product((1, 2, 3, 5, 8), (np.float64, np.float32)):
+        p, t, td = (np.ascontiguousarray(v[:nlev], dtype=dtype) for v in full)
         got = xa.cape_cin_multi(p, t, td, SETS[0], moist='family', fused=True)
         for (name, depth), g in zip(SETS[0], got):
-            _same(g, xa.cape_cin_columns(p, t, td, parcel=name, depth=depth, moist='family'), (name, nlev))
+            _same(g, xa.cape_cin_columns(p, t, td, parcel=name, depth=depth, moist='family'), (name, nlev, dtype))
     for ncol in (1, 63, 65, 511, 513, 1025):
         p, t, td = synth.columns(nlev=33, ncol=ncol, seed=ncol, nan_fraction=0.1, dtype=np.float32)
         got = xa.cape_cin_multi(p, t, td, SETS[0], moist='family', fused=True)

@@ -38,20 +38,12 @@ XP_DEV void lift_candidate(const EffectiveArgs &a, const double *es, double *slo
                            double pc_p, double pc_t, double pc_td, double &cape, double &cin, int &status) {
     const bool vtc = a.vtc != 0, pos_neg = a.pos_neg != 0, log_interp = a.log_interp != 0;
     const bool need_w = vtc;
-    const Lcl l = lcl<true>(pc_p, pc_t, pc_td);
-    status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
     cape = 0.0; cin = 0.0;
-    if (isnan_(l.p)) return;                                               // a NaN LCL blanks the profile: CAPE = CIN = 0.0
-    BelowLcl n;
-    n.lp = l.p; n.x_lcl = log(l.p); n.t0 = pc_t; n.sat = (l.p == pc_p);
-    n.vfac = need_w ? virt_factor_tab(es, pc_t, pc_td, pc_p, false) : 1.0;
-    n.x0 = n.sat ? n.x_lcl : log_tab<true>(es, pc_p);
-
-    Scan sc; sc.init(l.p, n.x_lcl, pos_neg, slot);
-    sc.slot[SL_LCL_T * SLOT_STRIDE] = vtc ? l.tv : l.t;
+    Parcel pc; pc.p = pc_p; pc.t = pc_t; pc.td = pc_td;
+    Lcl l; BelowLcl n; Scan sc;
+    if (!start_column<true>(es, pc, need_w, vtc, pos_neg, slot, l, n, sc, status)) return;   // a NaN LCL blanks the profile: CAPE = CIN = 0.0
     Moist m;
     m.start(es, l.p, n.x_lcl, l.t, TABLE, a.tb);
-    clear_bracket(sc.slot);
     // The moist adiabat by the RK4 stepper or the reference's tables.  A level exactly on the LCL comes before the stepper
     // has moved, and Moist::at at its own start point returns the start temperature, l.t, as it stands: taken directly (the
     // stepper inlined a second time cost the RK4 kernels 2-4 VGPRs and 450 instructions); the tables are interpolated there.
@@ -64,12 +56,12 @@ XP_DEV void lift_candidate(const EffectiveArgs &a, const double *es, double *slo
     bool lcl_done = false;
     int unreported = 0;                                                    // (a NaN pressure below the LCL is not reported here)
     double sP = qnan(), sT = qnan(), sM = qnan();                          // the level that waits while the LCL node is fed
-    // one-level look-ahead, kept in the input type until it is used (see select_mu_exact)
-    T np_ = ldr<T>(a.p, k0, c), nt_ = ldr<T>(a.t, k0, c), ntd_ = ldr<T>(a.td, k0, c);
+    LookAhead<T> next(a.p, a.t, a.td, c, k0);
     for (int k = k0; k <= nlev; ++k) {
         const bool last = k >= nlev;
-        const double Pc = last ? qnan() : (double)np_, Tc = last ? qnan() : (double)nt_, Mc = last ? qnan() : (double)ntd_;
-        if (k + 1 < nlev) { np_ = ldr<T>(a.p, k + 1, c); nt_ = ldr<T>(a.t, k + 1, c); ntd_ = ldr<T>(a.td, k + 1, c); }
+        double Pc, Tc, Mc;
+        next.take(k + 1, nlev, Pc, Tc, Mc);
+        if (last) Pc = Tc = Mc = qnan();
         const bool skew = lcl_done;
         lcl_done = below_lcl_node(es, sc, n, vtc, log_interp, skew ? sP : Pc, skew ? sT : Tc, skew ? sM : Mc, skew, last, unreported, adiabat);
         sP = Pc; sT = Tc; sM = Mc;

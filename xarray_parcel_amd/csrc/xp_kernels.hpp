@@ -2,20 +2,14 @@
 // x-adjacent columns so every level read is one coalesced 256 B (fp32) / 512 B (fp64) request per
 // array (layout (lev, y, x), col_stride == 1).  No MFMA: the path is an elementwise + per-column scan
 // (SURVEY.md 8d); LDS holds the e_s / ln lookup tables and the per-thread slots of the scan (xp_device.hpp).
-// Views, stores and the node at or below the LCL: xp_lcl_node.hpp.
+// Views, stores, the start of a column and the node at or below the LCL: xp_lcl_node.hpp; the level reader:
+// xp_level_reader.hpp; the profile output: xp_profile_out.hpp.
 #pragma once
-#include "xp_lcl_node.hpp"
+#include "xp_level_reader.hpp"
+#include "xp_profile_out.hpp"
 
 namespace xp {
 
-struct ProfileOut {
-    void *v[6];            // p, t_parcel, tv_parcel, t_env, tv_env, td_env (each may be null)
-    int64_t nlev_out, ls, cs;
-    int f64;
-    int native6;           // all six arrays wanted, in the dtype of the input views: the row is stored without per-array tests
-    void *li;              // lifted index (pf.py:1722): environment minus parcel temperature of this profile at exp(li_x) hPa
-    double li_x;           // ln of that pressure
-};
 struct CapeArgs {
     View p, t, td;
     int64_t nlev, ncol;
@@ -49,13 +43,11 @@ template <bool HUM> XP_DEV double as_dewpoint(const double *es, double p, double
 template <typename T, bool HUM> XP_DEV Parcel select_mu_exact(const CapeArgs &a, int64_t c, const double *es, const double depth) {
     Parcel r; r.p = r.t = r.td = qnan(); r.first = a.nlev; r.idx = -1; r.prepend = false;
     double bottom = qnan(), bound = qnan(), dmin = qnan(), best = qnan();
-    // one-level software prefetch: the loop is otherwise a chain of dependent HBM round trips
-    // (the look-ahead values stay in the INPUT type until they are used: converting an fp32 value at the load makes the
-    // wavefront wait for the load right there, and the prefetch hides nothing)
-    T np_ = ldr<T>(a.p, 0, c), nt_ = ldr<T>(a.t, 0, c), ntd_ = ldr<T>(a.td, 0, c);
+    LookAhead<T> next(a.p, a.t, a.td, c, 0);
     for (int64_t k = 0; k < a.nlev; ++k) {
-        double p = (double)np_, t = (double)nt_, td = as_dewpoint<HUM>(es, p, t, (double)ntd_);
-        if (k + 1 < a.nlev) { np_ = ldr<T>(a.p, k + 1, c); nt_ = ldr<T>(a.t, k + 1, c); ntd_ = ldr<T>(a.td, k + 1, c); }
+        double p, t, td;
+        next.take(k + 1, a.nlev, p, t, td);
+        td = as_dewpoint<HUM>(es, p, t, td);
         if (isnan_(p)) continue;
         if (isnan_(bottom)) { bottom = p; bound = bottom - depth; }
         double d = fabs(p - bound);
@@ -135,7 +127,7 @@ template <typename T, bool HUM> XP_DEV Parcel select_mu(const CapeArgs &a, int64
 
 // mixed_parcel (pf.py:229-289) with mixed_layer (pf.py:137-162) / get_layer(interpolate=True):
 // trapezoid in linear p of theta and w_s(p, Td) over [p_bottom - depth, p_bottom], top interpolated in ln p.
-template <typename T> XP_DEV void layer_mean_step(double &sum, double p0, double v0, double p1, double v1) {
+XP_DEV void layer_mean_step(double &sum, double p0, double v0, double p1, double v1) {
     double a = fabs(p1 - p0) * ((v0 + v1) * 0.5);
     if (!isnan_(a)) sum += a;
 }
@@ -147,10 +139,11 @@ template <typename T, bool HUM> XP_DEV Parcel select_ml(const CapeArgs &a, int64
     double pp = qnan(), thp = qnan(), wp = qnan();        // previous row of the layer
     double pb = qnan(), thb = qnan(), wb = qnan();        // last row with a valid pressure >= top
     bool closed = false;
-    T np_ = ldr<T>(a.p, 0, c), nt_ = ldr<T>(a.t, 0, c), ntd_ = ldr<T>(a.td, 0, c);   // one-level software prefetch, in the input type (see select_mu_exact)
+    LookAhead<T> next(a.p, a.t, a.td, c, 0);
     for (int64_t k = 0; k < a.nlev; ++k) {
-        double p = (double)np_, t = (double)nt_, td = as_dewpoint<HUM>(es, p, t, (double)ntd_);
-        if (k + 1 < a.nlev) { np_ = ldr<T>(a.p, k + 1, c); nt_ = ldr<T>(a.t, k + 1, c); ntd_ = ldr<T>(a.td, k + 1, c); }
+        double p, t, td;
+        next.take(k + 1, a.nlev, p, t, td);
+        td = as_dewpoint<HUM>(es, p, t, td);
         if (isnan_(bottom) && !isnan_(p)) { bottom = p; top = bottom - depth; }
         if (!isnan_(p) && p < top) {
             // insert the interpolated top row, close the integral; the profile continues from this level
@@ -159,21 +152,21 @@ template <typename T, bool HUM> XP_DEV Parcel select_ml(const CapeArgs &a, int64
             double cb2 = cb, ca2 = ca, tha = th_a, wa = w_a;
             if (pb == top) { ca2 = cb; tha = thb; wa = wb; }
             double th_t = interp_rule(thb, tha, lt, cb2, ca2), w_t = interp_rule(wb, wa, lt, cb2, ca2);
-            layer_mean_step<T>(s_th, pp, thp, top, th_t);
-            layer_mean_step<T>(s_w, pp, wp, top, w_t);
+            layer_mean_step(s_th, pp, thp, top, th_t);
+            layer_mean_step(s_w, pp, wp, top, w_t);
             r.first = k; closed = true;
             break;
         }
         double th = t / fpow(p / 1000.0, KAPPA), w = sat_mix(p, td);
-        if (k > 0) { layer_mean_step<T>(s_th, pp, thp, p, th); layer_mean_step<T>(s_w, pp, wp, p, w); }
+        if (k > 0) { layer_mean_step(s_th, pp, thp, p, th); layer_mean_step(s_w, pp, wp, p, w); }
         pp = p; thp = th; wp = w;
         if (!isnan_(p)) { pb = p; thb = th; wb = w; }
     }
     if (!closed) {
         // column never gets above the layer top: the inserted row holds NaN unless a level sits exactly on it
         double th_t = (pb == top) ? thb : qnan(), w_t = (pb == top) ? wb : qnan();
-        layer_mean_step<T>(s_th, pp, thp, top, th_t);
-        layer_mean_step<T>(s_w, pp, wp, top, w_t);
+        layer_mean_step(s_th, pp, thp, top, th_t);
+        layer_mean_step(s_w, pp, wp, top, w_t);
     }
     double dlay = fabs(top - bottom);
     double th_m = (1.0 / dlay) * s_th, w_m = (1.0 / dlay) * s_w;
@@ -181,6 +174,24 @@ template <typename T, bool HUM> XP_DEV Parcel select_ml(const CapeArgs &a, int64
     r.t = th_m * fpow(p_start / 1000.0, KAPPA);                             // pf.py:268-269
     r.td = dewpoint_of_e(vapor_pressure(p_start, w_m));                    // pf.py:275-280
     return r;
+}
+
+// The parcel a column lifts: its surface level, the caller's explicit parcel, or one of the two searches (pmode is a
+// compile-time constant wherever the kernel is instantiated per parcel kind).
+template <typename T, bool HUM> XP_DEV Parcel choose_parcel(const CapeArgs &a, int pmode, int64_t c, const double *es, const double depth) {
+    Parcel pc;
+    if (pmode == PM_SURFACE) {
+        pc.p = ld<T>(a.p, 0, c); pc.t = ld<T>(a.t, 0, c); pc.td = as_dewpoint<HUM>(es, pc.p, pc.t, ld<T>(a.td, 0, c));
+        pc.first = 0; pc.idx = 0; pc.prepend = false;
+    } else if (pmode == PM_EXPLICIT) {
+        pc.p = ld1<T>(a.ex_p, c); pc.t = ld1<T>(a.ex_t, c); pc.td = ld1<T>(a.ex_td, c);
+        pc.first = 0; pc.idx = -1; pc.prepend = false;
+    } else if (pmode == PM_MU) {
+        pc = select_mu<T, HUM>(a, c, es, depth);
+    } else {
+        pc = select_ml<T, HUM>(a, c, es, depth);
+    }
+    return pc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -242,48 +253,36 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     // between workgroups, and whichever wavefront is free takes the next tile, so the chip walks the grid roughly in
     // order (8-Mi-column configs: -3 % surface, -12 % mixed-layer, -15 % most-unstable; c2 has only four tiles per
     // wavefront and is 4 % faster as an ordinary launch).
-    constexpr bool persist = PERSIST;
     int64_t c0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (a.only_flagged) {                                                  // fix-up pass: most blocks have nothing to do
         int need = (c0 < a.ncol) ? a.flags[c0] : 0;
         if (!__syncthreads_or(need)) return;
-        const double *es0 = stage_es_table(a.es_tab, s_es);
-        (void)es0;
+        stage_es_table(a.es_tab, s_es);
         if (!need) return;
     } else {
         stage_es_table(a.es_tab, s_es);
-        if (!persist && c0 >= a.ncol) return;
+        if (!PERSIST && c0 >= a.ncol) return;
     }
     const double *es = s_es;
     double *const s_slot = lds.slot;
 
     auto column = [&](const int64_t c) __attribute__((always_inline)) {
-    Parcel pc;
-    if (PMODE == PM_SURFACE) {
-        pc.p = ld<T>(a.p, 0, c); pc.t = ld<T>(a.t, 0, c); pc.td = as_dewpoint<HUM>(es, pc.p, pc.t, ld<T>(a.td, 0, c));
-        pc.first = 0; pc.idx = 0; pc.prepend = false;
-    } else if (PMODE == PM_EXPLICIT) {
-        pc.p = ld1<T>(a.ex_p, c); pc.t = ld1<T>(a.ex_t, c); pc.td = ld1<T>(a.ex_td, c);
-        pc.first = 0; pc.idx = -1; pc.prepend = false;
-    } else if (PMODE == PM_MU) {
-        pc = select_mu<T, HUM>(a, c, es, a.depth);
-    } else {
-        pc = select_ml<T, HUM>(a, c, es, a.depth);
-    }
+    const Parcel pc = choose_parcel<T, HUM>(a, PMODE, c, es, a.depth);
 
     const bool vtc = DEF || (a.vtc != 0), pos_neg = DEF || (a.pos_neg != 0), log_interp = DEF || (a.log_interp != 0);
     const bool need_w = vtc || PROFILE;
+    // The start of the column is spelled out here; the fused and the inflow kernel take it as xp::start_column
+    // (xp_lcl_node.hpp), the same statements.  Taken from there -- x0, vf_parcel, x_lcl and the saturation test read from its
+    // BelowLcl -- 47 of the 48 family instantiations spilled more (up to +10 VGPRs, +28 spill instructions, +16..32 B of
+    // scratch); the bracket slots cleared where they are now, the stores handed in as a callable so that they keep their
+    // place, and the saturation test kept local did not cure it (43-49 of 48 worse).
     const Lcl l = lcl(pc.p, pc.t, pc.td);
     int status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
     const ScalarsOut &s = a.s;
 
     if (isnan_(l.p)) {
         // NaN parcel / LCL blanks the whole profile (pf.py:965-985): CAPE = CIN = 0.0, everything else NaN
-        if (PROFILE) {
-            for (int64_t j = 0; j < a.prof.nlev_out; ++j)
-                for (int v = 0; v < 6; ++v) st(a.prof.v[v], a.prof.f64, j * a.prof.ls + c * a.prof.cs, qnan());
-            st(a.prof.li, a.prof.f64, c, qnan());
-        }
+        if (PROFILE) ProfileSink<T, LAZY>::blank(a.prof, c);
         store_blank_column(s, c, pc, l, status);
         if (FAMILY) a.flags[c] = 0;
         return;
@@ -292,11 +291,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     // everything known before the scan is stored now, so that it does not occupy registers through the level loop
     store_parcel_and_lcl(s, c, pc, l);
     const double vf_parcel = need_w ? virt_factor_tab(es, pc.t, pc.td, pc.p, false) : 1.0;   // 1 + 0.608 w of the parcel (pf.py:748, 767)
-    // ln p bookkeeping.  Levels use the table logarithm; the LCL node uses the library log (its crossing tests
-    // "p* < p_lcl" then break ties as on the CPU); a level that sits exactly on the LCL pressure takes the LCL's
-    // value so that the interval between the two stays zero-width; and the parcel's own ln p (x0) is whatever its
-    // level gets, so that the surface parcel reproduces its level bit for bit (T0 * exp(0)) -- the reference's lfc_el
-    // branches on that exact equality (pf.py:1117-1120).
+    // (ln p bookkeeping: the rule is stated at xp::start_column)
     const double x_lcl = log(l.p);
     const double x0 = (pc.p == l.p) ? x_lcl : log_tab<true>(es, pc.p);
 
@@ -309,13 +304,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     double fam_off = l.tv - l.t;                                            // family profile kernels: Tv - T of the parcel at the node before (temperature_from)
     double fam_offp = fam_off;                                              // ... and at the node before that (temperature_from2)
 
-    int jout = 0;                                                           // profile row
-    double li_d = qnan();                                                   // PROFILE: environment minus parcel temperature of the node before this one (lifted index)
-    // LAZY: the node before this one as it came -- its parcel temperature where the node had one (dry adiabat, LCL), else
-    // its virtual temperature, to be inverted if the next node turns out to close the bracket
-    double lz_te = qnan(), lz_tq = qnan(), lz_p = qnan();
-    int lz_known = 1;
-    bool li_done = false;
+    ProfileSink<T, LAZY> sink;                                              // PROFILE: the rows and the lifted index (xp_profile_out.hpp)
     // CAPE / CIN-only kernels and the lowest valid pressure of the profile (stands in for a missing EL, pf.py:1329): recovered
     // after the walk (below) -- except for the mixed-layer parcel, whose kernels the register allocator serves better with
     // the per-node bookkeeping (17-27 spilled VGPRs otherwise): the level index of the last valid-pressure node
@@ -323,68 +312,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     int last_k = -1, cur_k = -1;
     // `above` (a std::integral_constant): this node and the one before it lie strictly above the LCL (phase B)
     auto emit = [&](auto above, double P, double X, double tp, double tvp, double te, double tve, double tde, bool is_lcl) __attribute__((always_inline)) {
-        if (PROFILE) {
-            if (!LAZY && jout < a.prof.nlev_out) {
-                int64_t o = jout * a.prof.ls + c * a.prof.cs;
-                bool dead = isnan_(P);                                     // NaN-coordinate rows come out all-NaN (pf.py:963, 988)
-#ifndef XP_NO_NATIVE6
-                if (a.prof.native6) {
-                    // the common request (the drivers, BASELINE config 3): six stores of the input dtype, no null / dtype
-                    // test per array (each was two scalar branches plus, at this register pressure, two v_readlane), the
-                    // NaN-row select done on the converted value
-                    const T vP = (T)P;
-                    ((T *)a.prof.v[0])[o] = vP;
-                    ((T *)a.prof.v[1])[o] = dead ? vP : (T)tp;
-                    ((T *)a.prof.v[2])[o] = dead ? vP : (T)tvp;
-                    ((T *)a.prof.v[3])[o] = dead ? vP : (T)te;
-                    ((T *)a.prof.v[4])[o] = dead ? vP : (T)tve;
-                    ((T *)a.prof.v[5])[o] = dead ? vP : (T)tde;
-                } else
-#endif
-                {
-                st(a.prof.v[0], a.prof.f64, o, P);
-                st(a.prof.v[1], a.prof.f64, o, dead ? P : tp);
-                st(a.prof.v[2], a.prof.f64, o, dead ? P : tvp);
-                st(a.prof.v[3], a.prof.f64, o, dead ? P : te);
-                st(a.prof.v[4], a.prof.f64, o, dead ? P : tve);
-                st(a.prof.v[5], a.prof.f64, o, dead ? P : tde);
-                }
-            }
-            ++jout;
-            // lifted_index (pf.py:1722 = log_interp of the profile's two temperatures at one pressure, pf.py:1813): the
-            // nodes come with decreasing pressure, so the first one at or above the level closes the bracket that the
-            // node before it opened (coords_before / coords_after of pf.py:1774-1775; a NaN-pressure row is no
-            // coordinate; value rule of pf.py:1802-1806)
-            // -- both temperatures take the same weight, so their difference is interpolated: one value of state.
-            // The state lives in an LDS slot where the workgroup has one to spare (not the 1024-thread family build).
-            if constexpr (LAZY) {
-                // (a node without a parcel temperature of its own hands in NaN for it; a NaN parcel inverts to NaN)
-                const bool known = !isnan_(tp);
-                if (!li_done && X <= a.prof.li_x + 1e-12) {
-                    const bool on = X >= a.prof.li_x - 1e-12;
-                    double off0 = 0.0, off1 = 0.0;
-                    const double tc = known ? tp : Family::temperature_from(es, P, tvp, off0);
-                    const double tb4 = lz_known ? lz_tq : Family::temperature_from(es, lz_p, lz_tq, off1);
-                    const double d_ = te - tc, dp = lz_te - tb4;
-                    const double wgt = (a.prof.li_x - sc.Xp) / (X - sc.Xp);
-                    st(a.prof.li, a.prof.f64, c, (on || dp == d_) ? d_ : dp + (d_ - dp) * wgt);
-                    li_done = true;
-                }
-                if (!isnan_(P)) { lz_te = te; lz_tq = known ? tp : tvp; lz_p = P; lz_known = known ? 1 : 0; }
-            } else if (a.prof.li) {
-                constexpr bool LI_SLOT = SLOT_FIELDS > SL_LI;
-                const double d_ = te - tp;
-                if (!li_done && X <= a.prof.li_x + 1e-12) {
-                    // a node ON the level (the table logarithm and the host's differ in the last bits) is its own bracket
-                    const bool on = X >= a.prof.li_x - 1e-12;
-                    const double dp = LI_SLOT ? sc.slot[(LI_SLOT ? SL_LI : 0) * SLOT_STRIDE] : li_d;
-                    const double wgt = (a.prof.li_x - sc.Xp) / (X - sc.Xp);
-                    st(a.prof.li, a.prof.f64, c, (on || dp == d_) ? d_ : dp + (d_ - dp) * wgt);
-                    li_done = true;
-                }
-                if (!isnan_(P)) { if (LI_SLOT) sc.slot[(LI_SLOT ? SL_LI : 0) * SLOT_STRIDE] = d_; else li_d = d_; }
-            }
-        }
+        if (PROFILE) sink.node(a.prof, c, es, sc, P, X, tp, tvp, te, tve, tde);
         if (TRACK) {
             if (!isnan_(P)) { last_k = (is_lcl || cur_k < 0) ? -1 : cur_k; if (is_lcl || cur_k < 0) sc.slot[SL_MIN_P * SLOT_STRIDE] = P; }
         }
@@ -511,47 +439,20 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     if (pc.prepend) source(std::false_type{}, pc.p, pc.t, pc.td, false, -1);  // ML: the parcel is the new level 0 (pf.py:1641-1644)
     constexpr bool SEARCH = PMODE == PM_MU || PMODE == PM_ML;
     int k = (int)pc.first;      // per lane for MU / ML parcels through phase A; phase B re-aligns the wavefront (below)
-    // software-prefetched level loop
-    // Three per-lane row pointers that WALK up the levels: set once (64-bit multiply-add, a quarter-rate instruction),
-    // then advanced by the row stride with two full-rate adds per array and level.
-    const int64_t lane_off = (int64_t)c * a.p.cs * (int64_t)sizeof(T);
-    const int64_t row_step = a.p.ls * (int64_t)sizeof(T);
-    // (address space 1 = global, spelled out: behind the asm barrier below the compiler would otherwise fall back to
-    // flat loads, which also count against the LDS counter and so make every LDS wait a memory wait)
-    typedef const char __attribute__((address_space(1))) *GPtr;
-    GPtr lp = nullptr, lt = nullptr, ld_ = nullptr;
-    // (the look-ahead buffer holds the values as they are in memory: an fp32 level is converted when it is TAKEN -- converting
-    // at the load made every fp32 kernel wait for its loads on the spot, i.e. run without any prefetch)
-    T np_ = (T)qnan(), nt_ = (T)qnan(), ntd_ = (T)qnan();
-    auto seek = [&](int64_t kk) __attribute__((always_inline)) {             // the next load3() reads level kk
-        const int64_t o = kk * row_step + lane_off;
-        lp = (GPtr)a.p.data + o; lt = (GPtr)a.t.data + o; ld_ = (GPtr)a.td.data + o;
-    };
-    auto load3 = [&](T &P_, T &T2_, T &Td2_) __attribute__((always_inline)) {
-        typedef const T __attribute__((address_space(1))) *GT;
-        P_ = *(GT)lp; T2_ = *(GT)lt; Td2_ = *(GT)ld_;
-        lp += row_step; lt += row_step; ld_ += row_step;
-        asm volatile("" : "+v"(lp), "+v"(lt), "+v"(ld_));                  // (keeps the walk: no re-derivation from the level index)
-    };
+    // software-prefetched level loop: three row pointers that walk up the levels and a one-level look-ahead buffer
+    // (xp_level_reader.hpp)
+    LevelReader<T> rd(a.p, a.t, a.td, c);
     const int nlev = (int)a.nlev;                                          // the host checks nlev < 2^31: 32-bit scalar compares in the loops
-    seek(k);
-    if (k < nlev) load3(np_, nt_, ntd_);
-    // Level out of the look-ahead buffer, the next one requested.  The buffer itself holds NaN once the levels are used up
-    // (no select per level), and the wave-uniform loops count DOWN -- `rem` levels not yet taken out of the buffer -- so
-    // that they compare against 0 and 1 and the level count is not live in them (it used to be spilled and read back with
-    // eight v_readlane per level).
-    auto take = [&](bool more, double &P_, double &T2_, double &M_) __attribute__((always_inline)) {
-        // (one wait for the three values: left alone the compiler waits for each one just before its copy)
-        __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0F70); __builtin_amdgcn_sched_barrier(0);
-        M_ = (double)ntd_; T2_ = (double)nt_; P_ = (double)np_;            // (the value requested last first)
-        if (more) load3(np_, nt_, ntd_);
-        else { np_ = (T)qnan(); nt_ = (T)qnan(); ntd_ = (T)qnan(); }
-    };
+    rd.start(k, nlev);
+    // A level is TAKEN out of the look-ahead buffer and the next one requested.  The buffer itself holds NaN once the levels
+    // are used up (no select per level), and the wave-uniform loops count DOWN -- `rem` levels not yet taken out of the
+    // buffer -- so that they compare against 0 and 1 and the level count is not live in them (it used to be spilled and
+    // read back with eight v_readlane per level).
     constexpr bool Q = HUM && !PROFILE;
     for (; k <= nlev; ++k) {                                             // phase A (the searching parcels: per-lane level index)
         if (__ballot(!lcl_done || (PREP && s_is_td)) == 0ull) break;       // wave-uniform: everybody is above its LCL
         double P, T_, M_;
-        take(k + 1 < nlev, P, T_, M_);
+        rd.take(k + 1 < nlev, P, T_, M_);
         source(std::true_type{}, P, T_, M_, k >= nlev, k);
     }
     // (counting phase A down as well costs the surface / explicit-parcel kernels 60-70 spilled VGPRs at the 128 cap: measured)
@@ -563,22 +464,22 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
     // and from then on a level goes from the buffer straight into the node.  Needs (sP, sT, sM) to be a LEVEL (exact in T).
     auto plain_walk = [&](int k_) __attribute__((always_inline)) {
         int rem = __builtin_amdgcn_readfirstlane(nlev - k_);               // levels not yet requested into the buffer ...
-        if (rem > 0) { lp -= row_step; lt -= row_step; ld_ -= row_step; }
+        if (rem > 0) rd.step_back();
         // (the dropped request is waited for HERE, once: left pending on phase A's buffer registers it made the compiler put
         // `s_waitcnt vmcnt` in front of the first reuse of those registers inside the loop -- in the middle of every iteration,
         // where it waited for the loads of THIS level's successor: half the prefetch distance gone)
 #ifndef XP_NO_PREWAIT
-        __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0F70); __builtin_amdgcn_sched_barrier(0);
+        rd.wait();
 #endif
-        np_ = (T)sP; nt_ = (T)sT; ntd_ = (T)sM;
+        rd.put_back(sP, sT, sM);
         rem += 1;                                                          // ... nodes still to feed: levels k - 1 ... nlev - 1
         asm volatile("" : "+s"(rem));
         for (; rem > 0; --rem, ++k_) {
             double P, T_, M_;
-            // (take() without its NaN refill: what the buffer holds after the last level is never looked at here; the value
-            // requested last is copied first, so that the compiler's one wait covers all three)
-            M_ = (double)ntd_; T_ = (double)nt_; P = (double)np_;
-            if (rem > 1) load3(np_, nt_, ntd_);
+            // (take() without its wait and its NaN refill: what the buffer holds after the last level is never looked at
+            // here; the value requested last is copied first, so that the compiler's one wait covers all three)
+            rd.peek(P, T_, M_);
+            if (rem > 1) rd.request();
             if (TRACK) cur_k = k_ - 1;
             moist_node(P, log_tab<true>(es, P), T_, Q ? M_ : as_dewpoint<HUM>(es, P, T_, M_), Q);
         }
@@ -592,16 +493,14 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
         const int resume = k;                                              // the level this lane would load next
         int ku = nlev + 1;
         for (int probe = 0; probe <= nlev; ++probe) if (__ballot(resume <= probe) != 0ull) { ku = probe; break; }
-        seek(ku);
-        np_ = (T)qnan(); nt_ = (T)qnan(); ntd_ = (T)qnan();
-        if (ku < nlev) load3(np_, nt_, ntd_);
+        rd.start(ku, nlev);
         int rem = nlev - ku;
         asm volatile("" : "+s"(rem));
         // (Leaving this gated loop for the plain walk once every lane has joined was measured: mixed-layer +- 0, most-unstable
         // + 3.7 %, and the profile-output kernels spill over a hundred VGPRs with two copies of the node code.)
         for (; rem >= 0; --rem, ++ku) {
             double Pn, Tn, Mn;
-            take(rem > 1, Pn, Tn, Mn);
+            rd.take(rem > 1, Pn, Tn, Mn);
             if (ku >= resume) {
                 if (TRACK) cur_k = ku - 1;
                 moist_node(sP, log_tab<true>(es, sP), sT, Q ? sM : as_dewpoint<HUM>(es, sP, sT, sM), Q);
@@ -624,7 +523,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
             // after the plain walk the look-ahead buffer still holds the top level (the last one taken; nothing was requested
             // behind it): when its pressure is valid -- the normal case -- that is the answer, without a load whose round
             // trip nothing would cover at this point
-            const double q = (double)np_;
+            const double q = rd.peek_p();
             if (!isnan_(q)) { pm = (q < pm) ? q : pm; found = true; }
         }
         for (int kk = nlev - 1; kk >= (int)pc.first; --kk) {
@@ -634,22 +533,10 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
         }
         sc.slot[SL_MIN_P * SLOT_STRIDE] = pm;
     }
-    if (PROFILE) {
-        for (; jout < a.prof.nlev_out; ++jout) {
-            int64_t o = jout * a.prof.ls + c * a.prof.cs;
-            for (int v = 0; v < 6; ++v) st(a.prof.v[v], a.prof.f64, o, qnan());
-        }
-        if (!li_done) st(a.prof.li, a.prof.f64, c, qnan());              // the profile never reaches the level
-    }
+    if (PROFILE) sink.finish(a.prof, c);
 
-    // The output pointers are fetched from the kernel arguments only now, through a pointer the compiler cannot see
-    // through, so that it does not load all of them up front and carry ~26 scalar registers across the level loop
-    // (where they were being spilled into VGPR lanes and read back lane by lane: 840 v_readlane in the family kernel).
-    // `a` is the kernel's only parameter, so it sits at offset 0 of the kernarg segment; taking &a instead would make the
-    // compiler copy the whole struct to scratch.
-    typedef const CapeArgs __attribute__((address_space(4))) *KernargPtr;
-    KernargPtr late = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(late) : : "memory");
+    // (the output pointers are fetched from the kernel arguments only now: late_kernargs, xp_lcl_node.hpp)
+    const auto late = late_kernargs<CapeArgs>();
     Scan::Result r = sc.finish(late->post_zero != 0);
     if (FAMILY) late->flags[c] = fam.bad ? 1 : 0;
     store_scan_result(late->s, c, r, status | r.status);
@@ -665,7 +552,7 @@ template <typename T, int PMODE> __global__ __launch_bounds__(256) void k_select
     const double *es = stage_es_table(a.es_tab, s_es);
     int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.ncol) return;
-    Parcel pc = (PMODE == PM_MU) ? select_mu<T, false>(a, c, es, a.depth) : select_ml<T, false>(a, c, es, a.depth);
+    Parcel pc = choose_parcel<T, false>(a, PMODE, c, es, a.depth);
     st(a.s.par_p, a.s.f64, c, pc.p); st(a.s.par_t, a.s.f64, c, pc.t); st(a.s.par_td, a.s.f64, c, pc.td);
     sti(a.s.parcel_idx, c, pc.idx);
 }
@@ -683,15 +570,15 @@ void k_mixed_layer(View pv, View vv, int64_t nlev, int64_t ncol, double depth_in
         if (!isnan_(p) && p < top) {
             double cb = flog(pb), ca = flog(p), va = v;
             if (pb == top) { ca = cb; va = vb; }
-            layer_mean_step<T>(s, pp, vp, top, interp_rule(vb, va, flog(top), cb, ca));
+            layer_mean_step(s, pp, vp, top, interp_rule(vb, va, flog(top), cb, ca));
             closed = true;
             break;
         }
-        if (k > 0) layer_mean_step<T>(s, pp, vp, p, v);
+        if (k > 0) layer_mean_step(s, pp, vp, p, v);
         pp = p; vp = v;
         if (!isnan_(p)) { pb = p; vb = v; }
     }
-    if (!closed) layer_mean_step<T>(s, pp, vp, top, (pb == top) ? vb : qnan());
+    if (!closed) layer_mean_step(s, pp, vp, top, (pb == top) ? vb : qnan());
     st(out, f64, c, (1.0 / fabs(top - bottom)) * s);
 }
 

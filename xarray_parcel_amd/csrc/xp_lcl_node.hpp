@@ -1,11 +1,15 @@
-// xp_lcl_node.hpp -- the node a lifted parcel feeds while it is at or below its LCL ("phase A" of the level loops), once:
+// xp_lcl_node.hpp -- what the kernels that lift a parcel share up to its LCL, once.
+// The start of a column (start_column): a parcel's LCL, what it carries up to it (BelowLcl) and the initialised scan --
+// for the fused several-parcels kernel and the effective inflow layer; k_cape_cin spells the same statements out (it says why).
+// The node a lifted parcel feeds while it is at or below its LCL ("phase A" of the level loops):
 // the pieces -- the snap onto the LCL, the bracket slots, the environment at the LCL, the environment's virtual temperature
 // behind one range test, the two tie rules -- and below_lcl_node, their composition for the kernels without profile
 // output (the fused several-parcels kernel, xp_multi.hpp, and the effective inflow layer, xp_effective.hpp).  k_cape_cin
 // (xp_kernels.hpp) composes the same pieces itself, around its profile output.  The public contract is that the three
 // agree bit for bit (tests/test_gpu_multi.py, tests/test_gpu_effective_layer.py): a rule changes here or nowhere.
-// Also here: the views and stores of the kernels, the store groups of a column's scalars, and the tile loop of the
-// persistent kernels.
+// Also here: the views and stores of the kernels, the store groups of a column's scalars, the late kernel-argument
+// pointer they are stored through, and the tile loop of the persistent kernels.
+// How the levels are read: xp_level_reader.hpp; the profile output: xp_profile_out.hpp.
 #pragma once
 #include "xp_device.hpp"
 
@@ -54,6 +58,18 @@ template <typename S> XP_DEV void store_scan_result(const S &s, int64_t c, const
     st(s.lfc_p, f64, c, r.lfc_p); st(s.lfc_t, f64, c, r.lfc_t);
     st(s.el_p, f64, c, r.el_p); st(s.el_t, f64, c, r.el_t);
     sti(s.lfc_idx, c, r.lfc_idx); sti(s.el_idx, c, r.el_idx); sti(s.status, c, status);
+}
+
+// The output pointers are fetched from the kernel arguments only after the level loop, through a pointer the compiler
+// cannot see through, so that it does not load all of them up front and carry ~26 scalar registers across the level loop
+// (where they were being spilled into VGPR lanes and read back lane by lane: 840 v_readlane in the family kernel).
+// Args is the kernel's only parameter, so it sits at offset 0 of the kernarg segment; taking its address instead would
+// make the compiler copy the whole struct to scratch.
+template <typename Args> XP_DEV const Args __attribute__((address_space(4))) *late_kernargs() {
+    typedef const Args __attribute__((address_space(4))) *KernargPtr;
+    KernargPtr late = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(late) : : "memory");
+    return late;
 }
 
 // ---- the tile loop of the persistent kernels -------------------------------------------------------------------------
@@ -148,6 +164,33 @@ template <typename F> XP_DEV void lcl_ties(bool need_w, bool cross, bool sat, do
 // What a parcel carries up to its LCL: the LCL (pressure, its library logarithm), the dry adiabat (parcel temperature,
 // ln of its pressure, 1 + 0.608 x its mixing ratio: pf.py:748), and whether the LCL lies on the parcel's own level.
 struct BelowLcl { double lp, x_lcl, t0, x0, vfac; bool sat; };
+
+// The start of a column: the parcel's LCL, what it carries up to it, and the scan -- initialised, with the LCL temperature
+// the correction switch picks in its SL_LCL_T slot (pf.py:1442 / 1461) and the bracket slots cleared.  status takes
+// ST_LCL_NOT_CONVERGED.  Returns false for a NaN parcel / LCL, which blanks the whole profile (pf.py:965-985): the scan
+// is not touched then, `n` carries no adiabat, and the caller stores its blank column.
+// need_w: somebody wants virtual temperatures (the correction switch, or profile output).  FLAT: see xp::lcl.
+// ln p bookkeeping.  Levels use the table logarithm; the LCL node uses the library log (its crossing tests
+// "p* < p_lcl" then break ties as on the CPU); a level that sits exactly on the LCL pressure takes the LCL's
+// value so that the interval between the two stays zero-width; and the parcel's own ln p (x0) is whatever its
+// level gets, so that the surface parcel reproduces its level bit for bit (T0 * exp(0)) -- the reference's lfc_el
+// branches on that exact equality (pf.py:1117-1120).
+template <bool FLAT = false>
+XP_DEV bool start_column(const double *es, const Parcel &pc, bool need_w, bool vtc, bool pos_neg, double *slot,
+                         Lcl &l, BelowLcl &n, Scan &sc, int &status) {
+    l = lcl<FLAT>(pc.p, pc.t, pc.td);
+    status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
+    n.lp = l.p; n.x_lcl = qnan(); n.t0 = pc.t; n.x0 = qnan(); n.vfac = 1.0; n.sat = false;
+    if (isnan_(l.p)) return false;
+    n.vfac = need_w ? virt_factor_tab(es, pc.t, pc.td, pc.p, false) : 1.0;     // 1 + 0.608 w of the parcel (pf.py:748, 767)
+    n.x_lcl = log(l.p);
+    n.sat = (l.p == pc.p);
+    n.x0 = n.sat ? n.x_lcl : log_tab<true>(es, pc.p);
+    sc.init(l.p, n.x_lcl, pos_neg, slot);
+    slot[SL_LCL_T * SLOT_STRIDE] = vtc ? l.tv : l.t;
+    clear_bracket(slot);
+    return true;
+}
 
 // One node of a lane at / below / just above its LCL.  Every lane feeds exactly ONE node per call (k_cape_cin's `source`
 // says why): with `skew` unset (P, T_, Td_) is the level just loaded -- fed on the dry adiabat, or, when it lies above the

@@ -39,9 +39,6 @@ struct MultiArgs {
     double depth[MULTI_MAX];
     ScalarsOut s[MULTI_MAX];
     int32_t *flags[MULTI_MAX];        // 1 = the column of this chain must be redone by the RK4 kernel
-    void *li[MULTI_MAX];              // lifted index per chain (pf.py:1722), nullable
-    double li_x;                      // ln of its pressure
-    int li_f64;
 };
 
 struct Lev { double P, X, T, Td, tve; };      // one level with its environment node: pressure, ln p, T, Td, Tv (or T)
@@ -52,8 +49,6 @@ struct Chain {
     int first;             // first level of the grid that belongs to this chain's profile (INT_MAX: blank chain)
     int status;
     bool done;             // the LCL node has been fed: the chain consumes `prev` from now on
-    double li_p, li_e, li_q;   // lifted index: last valid-pressure node (pressure, environment T, parcel T or -Tv where only Tv is known)
-    bool li_done;
     Scan sc;
     Family fam;
 };
@@ -94,67 +89,29 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
         });
     };
 
-    const int64_t lane_off = (int64_t)c * b.p.cs * (int64_t)sizeof(T), row_step = b.p.ls * (int64_t)sizeof(T);
-    typedef const char __attribute__((address_space(1))) *GPtr;
-    typedef const T __attribute__((address_space(1))) *GT;
-    // three per-lane row pointers that walk up the levels with a one-level look-ahead (k_cape_cin's seek / load3)
-    GPtr lp_, lt_, ld_;
-    double np_, nt_, ntd_;
-    auto load3 = [&]() __attribute__((always_inline)) {
-        np_ = (double)*(GT)lp_; nt_ = (double)*(GT)lt_; ntd_ = (double)*(GT)ld_;
-        lp_ += row_step; lt_ += row_step; ld_ += row_step;
-        asm volatile("" : "+v"(lp_), "+v"(lt_), "+v"(ld_));
-    };
-    auto seek = [&](const int k) __attribute__((always_inline)) {             // start the walk at level k: its values are requested
-        const int64_t o = (int64_t)(k < nlev ? k : 0) * row_step + lane_off;
-        lp_ = (GPtr)b.p.data + o; lt_ = (GPtr)b.t.data + o; ld_ = (GPtr)b.td.data + o;
-        np_ = nt_ = ntd_ = qnan();
-        if (k < nlev) load3();
-    };
+    // three per-lane row pointers that walk up the levels with a one-level look-ahead (xp_level_reader.hpp)
+    LevelReader<T> rd(b.p, b.t, b.td, c);
 
     // ---- per chain, one after the other: parcel, LCL, label, and the levels up to the LCL ---------------------------------
     // (every lane walks from ITS first level with its own row pointers until the whole wavefront is past its LCLs -- ~10-15
     // iterations; these rows are read again by the shared walk below, out of L2)
     each([&](Chain &h, auto ic) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;
-        const int mode = a.mode[i];
-        Parcel pc;
-        if (mode == PM_SURFACE) {
-            pc.p = ld<T>(b.p, 0, c); pc.t = ld<T>(b.t, 0, c); pc.td = ld<T>(b.td, 0, c);
-            pc.first = 0; pc.idx = 0; pc.prepend = false;
-        } else if (mode == PM_MU) {
-            pc = select_mu<T, false>(b, c, es, a.depth[i]);
-        } else {
-            pc = select_ml<T, false>(b, c, es, a.depth[i]);
-        }
-        const Lcl l = lcl(pc.p, pc.t, pc.td);
+        const Parcel pc = choose_parcel<T, false>(b, a.mode[i], c, es, a.depth[i]);
         const ScalarsOut &s = a.s[i];
-        double *const slot = s_slot + i * (SLOT_FIELDS * SLOT_STRIDE) + threadIdx.x;
-        h.status = l.not_converged ? ST_LCL_NOT_CONVERGED : 0;
-        h.n.lp = l.p; h.lt = l.t; h.n.x_lcl = qnan(); h.n.t0 = pc.t; h.n.x0 = qnan(); h.n.vfac = 1.0;
-        h.n.sat = false; h.done = true; h.first = DEAD;
-        h.li_p = h.li_e = h.li_q = qnan(); h.li_done = false;
+        Lcl l;
+        h.done = true; h.first = DEAD;
         h.fam.tab = s_fam; h.fam.q = 0; h.fam.s = 0.0; h.fam.bad = false; h.fam.poison();
-        if (isnan_(l.p)) {
-            h.sc.init(l.p, qnan(), pos_neg, slot);
-            store_blank_column(s, c, pc, l, h.status);
-            st(a.li[i], a.li_f64, c, qnan());
+        if (!start_column(es, pc, need_w, vtc, pos_neg, s_slot + i * (SLOT_FIELDS * SLOT_STRIDE) + threadIdx.x, l, h.n, h.sc, h.status)) {
+            store_blank_column(s, c, pc, l, h.status);                              // (a blank chain: its scan is never fed nor finished)
             a.flags[i][c] = 0;
         } else {
             store_parcel_and_lcl(s, c, pc, l);
-            h.n.vfac = need_w ? virt_factor_tab(es, pc.t, pc.td, pc.p, false) : 1.0; // pf.py:748
-            // ln p bookkeeping as in k_cape_cin: library log for the LCL, table logarithm for levels, and the parcel's own
-            // ln p is whatever its level gets (the surface parcel reproduces its level bit for bit, pf.py:1117-1120)
-            h.n.x_lcl = log(l.p);
-            h.n.sat = (l.p == pc.p);
-            h.n.x0 = h.n.sat ? h.n.x_lcl : log_tab<true>(es, pc.p);
-            h.sc.init(l.p, h.n.x_lcl, pos_neg, slot);
-            slot[SL_LCL_T * SLOT_STRIDE] = vtc ? l.tv : l.t;                       // pf.py:1442 / 1461
             h.fam.start(s_fam, es, l.p, h.n.x_lcl, l.t, l.tv);
-            clear_bracket(slot);
             h.done = false;
             h.first = (int)pc.first;
         }
+        h.lt = l.t;
         // mixed layer: the parcel is the new level 0 of its profile (pf.py:1641-1644)
         const bool pre = pc.prepend && h.first != DEAD;
         if (__builtin_amdgcn_ballot_w64(pre) != 0ull && pre) {
@@ -166,13 +123,15 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
         // levels first, first + 1, ... while some lane of the wavefront is at or below its LCL; a lane past its LCL is one
         // level behind its loads (the level that crossed waits in wP, wT, wM)
         int k = h.first == DEAD ? nlev + 1 : h.first;
-        seek(k);
+        rd.start(k, nlev);
         double wP = qnan(), wT = qnan(), wM = qnan();
         for (; k <= nlev; ++k) {
             if (__ballot(!h.done) == 0ull) break;
             const bool in = k < nlev;
-            const double P = in ? np_ : qnan(), T_ = in ? nt_ : qnan(), M_ = in ? ntd_ : qnan();
-            if (k + 1 < nlev) load3();
+            double P, T_, M_;
+            rd.peek(P, T_, M_);
+            P = in ? P : qnan(); T_ = in ? T_ : qnan(); M_ = in ? M_ : qnan();
+            if (k + 1 < nlev) rd.request();
             const bool skew = h.done;
             if (!skew || k > h.first) feed(h, skew ? wP : P, skew ? wT : T_, skew ? wM : M_, skew, !in);
             wP = P; wT = T_; wM = M_;
@@ -191,7 +150,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
     if constexpr (NP > 2) fmin = h2.first < fmin ? h2.first : fmin;
     int ku = nlev + 1;
     for (int probe = 1; probe <= nlev; ++probe) if (__ballot(fmin <= probe) != 0ull) { ku = probe - 1; break; }
-    seek(ku);
+    rd.start(ku, nlev);
     Lev cur, prev;
     prev.P = prev.X = prev.T = prev.Td = prev.tve = qnan();
     for (int k = ku; k <= nlev; ++k) {
@@ -203,8 +162,8 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
             }
         });
         if (k < nlev) {
-            cur.P = np_; cur.T = nt_; cur.Td = ntd_;
-            if (k + 1 < nlev) load3();
+            rd.peek(cur.P, cur.T, cur.Td);
+            if (k + 1 < nlev) rd.request();
             cur.X = log_tab<true>(es, cur.P);
             cur.tve = need_w ? virt_env_ranged(es, cur.T, cur.Td, cur.P) : cur.T;
             prev = cur;
@@ -213,9 +172,7 @@ __global__ __launch_bounds__(XP_CAPE_THREADS) void k_cape_cin_multi(MultiArgs a)
 
     // ---- results -------------------------------------------------------------------------------------------------------
     // (output pointers fetched from the kernel arguments only now, as in k_cape_cin: not carried across the walk)
-    typedef const MultiArgs __attribute__((address_space(4))) *KernargPtr;
-    KernargPtr late = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(late) : : "memory");
+    const auto late = late_kernargs<MultiArgs>();
     const bool post_zero = late->base.post_zero != 0;
     each([&](Chain &h, auto ic) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;

@@ -260,7 +260,7 @@ void k_rebase_select(CapeArgs a, double *thr, int32_t *level_any) {
     const double *es = stage_es_table(a.es_tab, s_es);
     int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.ncol) return;
-    Parcel pc = (PMODE == PM_MU) ? select_mu<T, false>(a, c, es, a.depth) : select_ml<T, false>(a, c, es, a.depth);
+    Parcel pc = choose_parcel<T, false>(a, PMODE, c, es, a.depth);
     st(a.s.par_p, a.s.f64, c, pc.p); st(a.s.par_t, a.s.f64, c, pc.t); st(a.s.par_td, a.s.f64, c, pc.td);
     sti(a.s.parcel_idx, c, pc.idx);
     double t = pc.p;                                                       // MU: keep p <= p_parcel (pf.py:1551)
