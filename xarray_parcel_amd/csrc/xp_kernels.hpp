@@ -624,7 +624,7 @@ void k_moist_lapse(View pv, int64_t nlev, int64_t ncol, const void *pt, const vo
     for (int64_t k = 0; k < nlev; ++k) {
         double p = ld<T>(pv, k, c);
         if (p <= p0) st(out.data, f64, k * out.ls + c * out.cs, m.at(p, flog(p), tb));
-        else if (isnan_(p)) st(out.data, f64, k * out.ls + c * out.cs, qnan());
+        else if (!(p > p0)) st(out.data, f64, k * out.ls + c * out.cs, qnan());      // a NaN level, or a NaN reference pressure
     }
     m.start(es, p0, x0, t0, table_mode != 0, tb);
     for (int64_t k = nlev - 1; k >= 0; --k) {
@@ -653,7 +653,9 @@ void k_parcel_profile(View pv, int64_t nlev, int64_t ncol, const void *pp, const
         double tp, w;
         if (P >= l.p) {
             tp = t0 * fpow(P / p0, KAPPA);
-            w = (P == l.p) ? mix_of_e(sat_vapor_pressure(l.t), P) : w_parcel;
+            // a level ON the LCL is saturated at the moist adiabat's temperature there (pf.py:773): the LCL temperature in
+            // exact mode (no step is taken), the table's value in table mode
+            w = (P == l.p) ? mix_of_e(sat_vapor_pressure(m.at(P, x_lcl, tb)), P) : w_parcel;
         } else {
             tp = m.at(P, flog(P), tb);
             w = mix_of_e(sat_vapor_pressure(tp), P);
@@ -676,7 +678,9 @@ void k_lfc_el(View pv, View parv, View envv, int64_t nlev, int64_t ncol, const v
     sc.slot[SL_LCL_T * SLOT_STRIDE] = lt;
     for (int64_t k = 0; k < nlev; ++k) {
         double P = ld<T>(pv, k, c);
-        sc.node(P, flog(P), ld<T>(parv, k, c), ld<T>(envv, k, c), false);
+        // a node ON the LCL (the inserted LCL row, a saturated parcel's own level) shares the LCL's ln p, as in k_cape_cin:
+        // the reference takes one logarithm of one number for both, and "crossing above the LCL" compares the two
+        sc.node(P, (P == lp) ? sc.x_lcl : flog(P), ld<T>(parv, k, c), ld<T>(envv, k, c), false);
     }
     Scan::Result r = sc.finish(false);
     s.cape = s.cin = nullptr;                                              // lfc_el has no CAPE / CIN
