@@ -476,6 +476,63 @@ int xp_significant_tornado(int64_t n, int32_t dtype, int32_t mem, const void *sb
 int xp_supercell_composite(int64_t n, int32_t dtype, int32_t mem, const void *mucape, const void *srh, const void *shear,
                            void *out, void *stream);
 
+/* The wind over 1 ... 4 caller-chosen layers in one upward pass: metpy.calc.mean_pressure_weighted and bulk_shear (the ln p
+   one), the wind at each layer's bottom and the layer's strongest wind.  pressure, u, v and (nullable) height on one vertical;
+   a supplied height takes part in the NaN drop and in the ordering check.  With p0, z0 the lowest valid level, layer i is
+     XP_LAYER_PRESSURE        pb = bottom hPa (NaN: p0), pt = top hPa;
+     XP_LAYER_PRESSURE_DEPTH  pb as above, pt = pb - top: MetPy's bottom=, depth= in hPa;
+     XP_LAYER_HEIGHT          bottom, top in metres above z0 (NaN bottom: 0): pb = np.interp(z0 + bottom, z, p),
+                              pt = np.interp(z0 + top, z, p), linear in height and exact at a level (the bound rule of
+                              xp_bunkers_storm_motion); needs height.
+   The layer's points are those of MetPy's get_layer: the valid levels with pt <= p <= pb (close counting as inside), plus pb
+   and pt themselves where no selected level is close to them, u and v there linear in ln p between the levels on either
+   side, in order of decreasing pressure (P, U, V).  Per layer, ncol values each:
+     mean_u, mean_v      trapz(U P, P) / (0.5 (P_last^2 - P_first^2));
+     shear_u, shear_v    the wind at the last point (the top) minus the wind at the first (the bottom);
+     bottom_u, bottom_v  the wind at the first point;
+     max_u, max_v, max_pressure   the point of largest hypot(u, v), the first such point winning ties: the layer's strongest
+                         wind, since speed is convex along a linearly interpolated segment.
+   A layer with pt >= pb, with pb > p0, with pt below the smallest valid pressure (plain comparisons: MetPy raises) or, by
+   height, with a bound above the highest valid height gets NaN and the column XP_ST_NO_LAYER; the other layers are not
+   affected.  Levels are read up to and including the first one beyond the deepest top (every level, while some layer's top
+   has not been reached).  One pass: only the level just below the one that first reaches a bottom bound is looked back at,
+   which matters for levels closer than 1e-5 (relative) in pressure.  XP_E_ARG: nlayer outside 1 ... 4, an unknown kind, a
+   non-finite top, an infinite bottom, a depth <= 0 (XP_LAYER_PRESSURE_DEPTH's top; top <= bottom by height), a negative
+   bottom height, a layer by height without height. */
+enum { XP_LAYER_PRESSURE = 0, XP_LAYER_PRESSURE_DEPTH = 1, XP_LAYER_HEIGHT = 2 };
+typedef struct { int32_t kind; int32_t reserved; double bottom, top; } xp_wind_layer;
+typedef struct {
+    void *mean_u[4], *mean_v[4], *shear_u[4], *shear_v[4], *bottom_u[4], *bottom_v[4];   /* m/s, ncol each, per layer */
+    void *max_u[4], *max_v[4], *max_pressure[4];                                         /* m/s, m/s, hPa */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_HEIGHT | XP_ST_BAD_PRESSURE */
+    int32_t dtype, mem;
+} xp_wind_layers_out;
+int xp_wind_layers(const xp_view *pressure, const xp_view *u, const xp_view *v, const xp_view *height, int32_t nlayer,
+                   const xp_wind_layer *layers, xp_wind_layers_out *out, void *stream);
+
+/* metpy.calc.critical_angle per point [degrees]: the angle between a = (shear_u, shear_v), the 0-500 m ln p bulk shear, and
+   b = (storm_u - surface_u, storm_v - surface_v), evaluated as atan2(|a x b|, a . b) -- mathematically MetPy's
+   arccos(a . b / (|a| |b|)), but well conditioned near 0 and 180 degrees, where that form can leave [-1, 1] by rounding.
+   NaN where either vector is exactly zero; NaN propagates.  n elements of dtype in mem each; no argument may be NULL. */
+int xp_critical_angle(int64_t n, int32_t dtype, int32_t mem, const void *shear_u, const void *shear_v, const void *surface_u,
+                      const void *surface_v, const void *storm_u, const void *storm_v, void *out, void *stream);
+
+/* Corfidi (2003) MCS motion per point: upwind = mean - llj, downwind = mean + upwind, in that operation order; mean the
+   850-300 hPa pressure-weighted mean wind, llj the low-level jet.  Inputs as above; every output may be NULL. */
+int xp_corfidi_storm_motion(int64_t n, int32_t dtype, int32_t mem, const void *mean_u, const void *mean_v, const void *llj_u,
+                            const void *llj_v, void *upwind_u, void *upwind_v, void *downwind_u, void *downwind_v,
+                            void *stream);
+
+/* SPC's effective-layer significant tornado parameter per point.  With clip(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x)
+   (NaN passes through): lcl_term = (2000 - clip(lcl_height, 1000, 2000)) / 1000; cin_term = (200 + clip(mlcin, -200, -50))
+   / 150 (CIN <= 0 as everywhere in this library); shr = (ebwd < 12.5 ? 0 : min(ebwd, 30)) / 20;
+   stp = ((((mlcape / 1500) * lcl_term) * (esrh / 150)) * shr) * cin_term.  base_height (nullable): the height of the effective
+   inflow base (xp_effective_inflow_layer); where it is > 0 the layer is not surface based and the result is 0, whatever the
+   other arguments (SPC's rule).  Otherwise NaN propagates.  The other arguments may not be NULL. */
+int xp_significant_tornado_effective(int64_t n, int32_t dtype, int32_t mem, const void *mlcape, const void *mlcin,
+                                     const void *lcl_height, const void *esrh, const void *ebwd, const void *base_height,
+                                     void *out, void *stream);
+
 /* ---- Array primitives of the reference's implementation -------------------------------------------------------------
    The CAPE / CIN kernels stream a column once and never build the arrays these functions return, but the reference
    exposes them (and its tests call two of them), so a caller of the reference finds them here too.  One variable per

@@ -28,6 +28,7 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
            'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
+           'xp_wind_layers', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
            'xp_last_error')
 
 
@@ -145,6 +146,21 @@ class SrhLayersOut(C.Structure):
                 [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
 
 
+# xp_wind_layers: the layer kinds, one layer of the request, and per layer (up to WIND_MAX_LAYERS) the outputs
+LAYER_PRESSURE, LAYER_PRESSURE_DEPTH, LAYER_HEIGHT = 0, 1, 2
+WIND_MAX_LAYERS = 4
+WIND_LAYERS_OUT = ('mean_u', 'mean_v', 'shear_u', 'shear_v', 'bottom_u', 'bottom_v', 'max_u', 'max_v', 'max_pressure')
+
+
+class WindLayer(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('reserved', C.c_int32), ('bottom', C.c_double), ('top', C.c_double)]
+
+
+class WindLayersOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p * WIND_MAX_LAYERS) for k in WIND_LAYERS_OUT] +
+                [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
+
+
 class Tables(C.Structure):
     _fields_ = [('n_pressure', C.c_int64), ('n_temperature', C.c_int64), ('n_adiabat', C.c_int64),
                 ('p_max', C.c_double), ('p_step', C.c_double), ('t_min', C.c_double), ('t_step', C.c_double),
@@ -202,6 +218,10 @@ ARGTYPES = {
                                           C.POINTER(SrhLayersOut), _ptr),
     'xp_significant_tornado': (_i64, _i32, _i32) + (_ptr,) * 6,
     'xp_supercell_composite': (_i64, _i32, _i32) + (_ptr,) * 5,
+    'xp_wind_layers': (_V, _V, _V, _V, _i32, C.POINTER(WindLayer), C.POINTER(WindLayersOut), _ptr),
+    'xp_critical_angle': (_i64, _i32, _i32) + (_ptr,) * 8,
+    'xp_corfidi_storm_motion': (_i64, _i32, _i32) + (_ptr,) * 9,
+    'xp_significant_tornado_effective': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_last_error': (),
 }
 
@@ -237,7 +257,12 @@ for _m in list(MULTI_FLAGS):
 # The effective-inflow-layer kernel (csrc/xp_effective.hpp): its LCL iteration sits inside the candidate loop, and with
 # machine LICM the fp64 constants of both loops are kept in registers through every ascent (160+ VGPRs instead of 106-112).
 EFFECTIVE_FLAGS = ['-mllvm', '-disable-machine-licm']
-UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS)] + [
+# The wind-layers kernel (csrc/xp_wind_layers.hpp): each layer can add two bound points, each with three logarithms, and
+# with machine LICM their fp64 constants are carried through the level loop (14 VGPRs more in every instantiation: three
+# layers without the strongest wind 131 instead of 119, two with it 143 instead of 128 -- a wave per SIMD each).
+WIND_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
+UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
+         ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS)] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

@@ -1,0 +1,225 @@
+// xp_wind_layers.hpp -- the wind over caller-chosen layers, and three per-point products built on it (MetPy 1.4):
+//   k_wind_layers   metpy.calc.mean_pressure_weighted and bulk_shear over up to four layers given by pressure, by pressure
+//                   depth or by height above the lowest level, the wind at each layer's bottom and the layer's strongest
+//                   wind, one thread per column;
+//   k_critical_angle, k_corfidi_storm_motion, k_significant_tornado_effective   per point.
+// The rules are stated in include/xparcel.h and restated in NumPy in tests/wind_layers_restatement.py.  The column kernel is
+// the walk of k_bunkers_storm_motion (xp_kinematics.hpp) with the layers as arguments: one upward pass with level-major
+// loads (coalesced when col_stride == 1) serves every layer of the call whatever its kind; the points of MetPy's get_layer
+// are emitted in order as the walk passes them -- the levels, and the added bound points interpolated in ln p between the
+// level below and the level above, the only places a logarithm is taken -- into each layer's running sums.  A lane is done at
+// the first level beyond its highest top; the loop ends with a wave-uniform ballot, so levels above the deepest top are never
+// read.  The kernel is instantiated on the number of layers and on whether a strongest-wind output is wanted: a layer's state
+// is 9 doubles, 13 with the strongest wind, and no instantiation may spill (tests/test_wind_layers_cpu.py; the register
+// counts are in DESIGN.md section 7).  It lives in a translation unit of its own (xp_wind_layers_tu.hip).
+#pragma once
+#include "xp_kernels.hpp"
+
+namespace xp {
+
+constexpr int WL_MAX_LAYERS = 4;
+constexpr int WL_PRESSURE = 0, WL_PRESSURE_DEPTH = 1, WL_HEIGHT = 2;   // include/xparcel.h's XP_LAYER_*
+
+struct WindLayersArgs {
+    View p, u, v, z;                                     // z.data == nullptr: no height
+    int64_t nlev, ncol;
+    int n;                                               // layers
+    int kind[WL_MAX_LAYERS];
+    double bottom[WL_MAX_LAYERS], top[WL_MAX_LAYERS];    // as the caller gave them (a NaN bottom pressure: the lowest valid level's)
+    void *mean_u[WL_MAX_LAYERS], *mean_v[WL_MAX_LAYERS], *shear_u[WL_MAX_LAYERS], *shear_v[WL_MAX_LAYERS];
+    void *bottom_u[WL_MAX_LAYERS], *bottom_v[WL_MAX_LAYERS];
+    void *max_u[WL_MAX_LAYERS], *max_v[WL_MAX_LAYERS], *max_p[WL_MAX_LAYERS];
+    int32_t *status;
+};
+
+// (n layers, strongest wind wanted) of a call in the views' dtype: which instantiation runs it
+void launch_wind_layers(const WindLayersArgs &a, bool f64, bool want_max, hipStream_t s);
+void launch_critical_angle(int64_t n, bool f64, const void *const in[6], void *out, hipStream_t s);
+void launch_corfidi(int64_t n, bool f64, const void *const in[4], void *const out[4], hipStream_t s);
+void launch_stp_effective(int64_t n, bool f64, const void *const in[6], void *out, hipStream_t s);
+
+// The running state of one layer.  The trapezoids of mean_pressure_weighted, trapz(U P, P), are summed of the wind relative to
+// the layer's first point (u0, v0), so that mean = u0 + trapz((U - u0) P, P) / (0.5 (P_last^2 - P_first^2)) is exact for a
+// constant wind, and the relative wind of the last point is the bulk shear.
+template <bool MAXW> struct WindLayer {
+    double su, sv, u0, v0, pf, pl, ul, vl;   // sums, first point's wind and pressure, last point: pressure, relative wind
+    double pt;                               // the top pressure once the walk has reached it (NaN before)
+    double ms, mu, mv, mp;                   // MAXW: the strongest point so far: speed, wind, pressure
+    bool begun, started, top_close, fin;     // the bottom pressure is known; a point has been emitted; ...; finished
+    XP_DEV void init() {
+        su = sv = 0.0; u0 = v0 = pf = pl = ul = vl = pt = qnan(); begun = started = top_close = fin = false;
+        if constexpr (MAXW) { ms = -1.0; mu = mv = mp = qnan(); }
+    }
+    XP_DEV void emit(double p, double u, double v, double s) {          // s: hypot(u, v)
+#pragma clang fp contract(off)
+        if constexpr (MAXW) {
+            if (s > ms) { ms = s; mu = u; mv = v; mp = p; }             // (the first of equals stays)
+        }
+        if (started) {
+            u -= u0; v -= v0;
+            const double h = (p - pl) * 0.5;
+            su += h * (u * p + ul * pl); sv += h * (v * p + vl * pl);
+        } else { started = true; pf = p; u0 = u; v0 = v; u = v = 0.0; }
+        pl = p; ul = u; vl = v;
+    }
+    // an added bound point at pressure pe between the previous level (pp: higher pressure) and this one: u, v linear in ln p
+    XP_DEV void emit_between(double pe, double pp, double up, double vp, double p, double u, double v) {
+#pragma clang fp contract(off)
+        const double xe = flog(pe), xp_ = flog(pp), x = flog(p);
+        const double f = (xe - x) / (xp_ - x);
+        const double ue = u + f * (up - u), ve = v + f * (vp - v);
+        emit(pe, ue, ve, MAXW ? hypot(ue, ve) : 0.0);
+    }
+    // One valid level (p, u, v; s its speed) with the previous valid level (pp, up, vp) below it if has_prev.  pb, b_now: the
+    // bottom pressure, which became known at this level -- the first one at or beyond it; ptn, t_now: the same for the top.
+    XP_DEV void level(double p, double u, double v, double s, double pp, double up, double vp, bool has_prev, double pb,
+                      bool b_now, double ptn, bool t_now) {
+        if (fin) return;
+        if (b_now) {
+            begun = true;
+            if (has_prev && isclose_(pp, pb)) emit(pp, up, vp, MAXW ? hypot(up, vp) : 0.0);   // the level below, close to pb
+            else if (!isclose_(p, pb)) emit_between(pb, pp, up, vp, p, u, v);                 // pb itself, between the levels
+        }
+        if (!begun) return;
+        if (t_now) { pt = ptn; top_close = started && isclose_(pl, pt); }      // was the last point close to the top?
+        if (isnan_(pt) || p >= pt || isclose_(p, pt)) {
+            emit(p, u, v, s);
+            top_close = top_close || (!isnan_(pt) && isclose_(p, pt));
+        } else {                                         // the first level beyond the top: pt closes the layer
+            // (pt appeared at this level: had it appeared earlier, that level was in the layer and close to it)
+            if (!top_close && t_now) emit_between(pt, pp, up, vp, p, u, v);
+            fin = true;
+        }
+    }
+};
+
+// np.interp(zc, z, p) at the first level (z, p) with z >= zc, the previous valid level (zp, pp) below it
+XP_DEV double interp_p(double zc, double zp, double pp, double z, double p, bool has_prev) {
+#pragma clang fp contract(off)
+    return (z == zc || !has_prev) ? p : (p - pp) / (z - zp) * (zc - zp) + pp;
+}
+
+template <typename T, int NL, bool MAXW> __global__ __launch_bounds__(256)
+void k_wind_layers(WindLayersArgs a) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.ncol) return;
+    constexpr int f64 = sizeof(T) == 8;
+    const bool hz = a.z.data != nullptr;
+    WindLayer<MAXW> L[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) L[i].init();
+    double z0 = qnan(), p0 = qnan();
+    double zp = qnan(), pp = qnan(), up = qnan(), vp = qnan();
+    bool has_prev = false, done = false;
+    int bad = 0;
+    for (int64_t k = 0; k < a.nlev; ++k) {
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+        if (done) continue;
+        const double p = ld<T>(a.p, k, c), u = ld<T>(a.u, k, c), v = ld<T>(a.v, k, c);
+        const double z = hz ? ld<T>(a.z, k, c) : 0.0;
+        if (isnan_(p) || isnan_(u) || isnan_(v) || isnan_(z)) continue;      // missing level: dropped
+        if (has_prev) {
+            bad = ((!hz || z > zp) ? 0 : ST_BAD_HEIGHT) | (p < pp ? 0 : ST_BAD_PRESSURE);
+            if (bad) { done = true; continue; }
+        } else {
+            z0 = z; p0 = p;
+        }
+        const double s = MAXW ? hypot(u, v) : 0.0;
+        bool all_fin = true;
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            WindLayer<MAXW> &r = L[i];
+            if (r.fin) continue;
+            double pb = qnan(), ptn = qnan();
+            bool b_now, t_now;
+            if (a.kind[i] == WL_HEIGHT) {
+                const double zb = z0 + a.bottom[i], zt = z0 + a.top[i];
+                b_now = !r.begun && z >= zb;
+                t_now = isnan_(r.pt) && z >= zt;
+                if (b_now) pb = interp_p(zb, zp, pp, z, p, has_prev);
+                if (t_now) ptn = interp_p(zt, zp, pp, z, p, has_prev);
+            } else {
+                pb = isnan_(a.bottom[i]) ? p0 : a.bottom[i];
+                ptn = a.kind[i] == WL_PRESSURE ? a.top[i] : pb - a.top[i];
+                // a layer that is empty or begins below the lowest level: left out (no point emitted, no top reached)
+                if (!has_prev && (!(ptn < pb) || pb > p0)) { r.fin = true; continue; }
+                b_now = !r.begun && p <= pb;
+                t_now = isnan_(r.pt) && p <= ptn;
+            }
+            r.level(p, u, v, s, pp, up, vp, has_prev, pb, b_now, ptn, t_now);
+            all_fin = all_fin && r.fin;
+        }
+        done = all_fin;
+        zp = z; pp = p; up = u; vp = v; has_prev = true;
+    }
+    int status = bad;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        const WindLayer<MAXW> &r = L[i];
+        const bool ok = !bad && !isnan_(r.pt);           // the walk reached the top, and with it the bottom below it
+        if (!bad && !ok) status |= ST_NO_LAYER;
+        const double den = 0.5 * ((r.pl - r.pf) * (r.pl + r.pf));
+        st(a.mean_u[i], f64, c, ok ? r.u0 + r.su / den : qnan()); st(a.mean_v[i], f64, c, ok ? r.v0 + r.sv / den : qnan());
+        st(a.shear_u[i], f64, c, ok ? r.ul : qnan()); st(a.shear_v[i], f64, c, ok ? r.vl : qnan());
+        st(a.bottom_u[i], f64, c, ok ? r.u0 : qnan()); st(a.bottom_v[i], f64, c, ok ? r.v0 : qnan());
+        if constexpr (MAXW) {
+            st(a.max_u[i], f64, c, ok ? r.mu : qnan()); st(a.max_v[i], f64, c, ok ? r.mv : qnan());
+            st(a.max_p[i], f64, c, ok ? r.mp : qnan());
+        }
+    }
+    sti(a.status, c, status);
+}
+
+// ---- per point ---------------------------------------------------------------------------------------------------------
+// metpy.calc.critical_angle as atan2(|a x b|, a . b) [degrees]: a the 0-500 m shear, b the storm-relative surface inflow
+XP_DEV double critical_angle_value(double au, double av, double su, double sv, double cu, double cv) {
+#pragma clang fp contract(off)
+    const double bu = cu - su, bv = cv - sv;
+    if ((au == 0.0 && av == 0.0) || (bu == 0.0 && bv == 0.0)) return qnan();
+    const double cross = au * bv - av * bu, dot = au * bu + av * bv;
+    return atan2(fabs(cross), dot) * (180.0 / 3.141592653589793);
+}
+// SPC's effective-layer significant tornado parameter; comparisons with NaN are false, so NaN propagates through the clips
+XP_DEV double stp_effective_value(double mlcape, double mlcin, double lcl_height, double esrh, double ebwd) {
+#pragma clang fp contract(off)
+    double lcl = lcl_height < 1000.0 ? 1000.0 : (lcl_height > 2000.0 ? 2000.0 : lcl_height);
+    lcl = (2000.0 - lcl) / 1000.0;
+    double cin = mlcin < -200.0 ? -200.0 : (mlcin > -50.0 ? -50.0 : mlcin);
+    cin = (200.0 + cin) / 150.0;
+    double shr = ebwd < 12.5 ? 0.0 : (ebwd > 30.0 ? 30.0 : ebwd);
+    shr = shr / 20.0;
+    return ((((mlcape / 1500.0) * lcl) * (esrh / 150.0)) * shr) * cin;
+}
+template <typename T> __global__ __launch_bounds__(256)
+void k_critical_angle(int64_t n, const void *shear_u, const void *shear_v, const void *surface_u, const void *surface_v,
+                      const void *storm_u, const void *storm_v, void *out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    st(out, sizeof(T) == 8, c, critical_angle_value(ld1<T>(shear_u, c), ld1<T>(shear_v, c), ld1<T>(surface_u, c),
+                                                    ld1<T>(surface_v, c), ld1<T>(storm_u, c), ld1<T>(storm_v, c)));
+}
+// Corfidi (2003): upwind = mean - jet, downwind = mean + upwind
+template <typename T> __global__ __launch_bounds__(256)
+void k_corfidi_storm_motion(int64_t n, const void *mean_u, const void *mean_v, const void *llj_u, const void *llj_v,
+                            void *upwind_u, void *upwind_v, void *downwind_u, void *downwind_v) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    constexpr int f64 = sizeof(T) == 8;
+    const double mu = ld1<T>(mean_u, c), mv = ld1<T>(mean_v, c);
+    const double uu = mu - ld1<T>(llj_u, c), uv = mv - ld1<T>(llj_v, c);
+    st(upwind_u, f64, c, uu); st(upwind_v, f64, c, uv);
+    st(downwind_u, f64, c, mu + uu); st(downwind_v, f64, c, mv + uv);
+}
+template <typename T> __global__ __launch_bounds__(256)
+void k_significant_tornado_effective(int64_t n, const void *mlcape, const void *mlcin, const void *lcl_height,
+                                     const void *esrh, const void *ebwd, const void *base_height, void *out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    double r = stp_effective_value(ld1<T>(mlcape, c), ld1<T>(mlcin, c), ld1<T>(lcl_height, c), ld1<T>(esrh, c), ld1<T>(ebwd, c));
+    if (base_height && ld1<T>(base_height, c) > 0.0) r = 0.0;             // the inflow layer is not surface based
+    st(out, sizeof(T) == 8, c, r);
+}
+
+}  // namespace xp

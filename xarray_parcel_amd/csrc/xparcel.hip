@@ -18,11 +18,14 @@
 #include "xp_dcape.hpp"
 #include "xp_kinematics.hpp"
 #include "xp_effective.hpp"
+#include "xp_wind_layers.hpp"
 
 static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_ST_LCL_NOT_CONVERGED &&
               xp::ST_NAN_PRESSURE == XP_ST_NAN_PRESSURE && xp::ST_BAD_PRESSURE == XP_ST_BAD_PRESSURE &&
               xp::ST_NO_LAYER == XP_ST_NO_LAYER && xp::ST_BAD_HEIGHT == XP_ST_BAD_HEIGHT &&
               xp::ST_LAYER_OPEN == XP_ST_LAYER_OPEN, "the kernels' status bits are the ABI's");
+static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
+              xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
 
 namespace {
 
@@ -1156,6 +1159,102 @@ int xp_supercell_composite(int64_t n, int32_t dtype, int32_t mem, const void *mu
     for (int i = 0; i < 3; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
     if ((rc = st.out(out, b, mem, &od))) return rc;
     by_dtype(dtype, [&](auto z) { launch(xp::k_supercell_composite<decltype(z)>, n, st, n, in[0], in[1], in[2], od); });
+    return st.finish();
+}
+
+int xp_wind_layers(const xp_view *p, const xp_view *u, const xp_view *v, const xp_view *z, int32_t nlayer,
+                   const xp_wind_layer *layers, xp_wind_layers_out *out, void *stream) {
+    const char *const entry = "xp_wind_layers";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {u, "u"}, {v, "v"}}))) return rc;
+    if (z && (rc = check_views({{p, "pressure"}, {z, "height"}}))) return rc;
+    if ((rc = check_out(entry, out, p))) return rc;
+    if (nlayer < 1 || nlayer > xp::WL_MAX_LAYERS) return fail(XP_E_ARG, "%s: nlayer must lie in 1 ... 4, got %d", entry, (int)nlayer);
+    if (!layers) return fail(XP_E_ARG, "%s: layers: null", entry);
+    xp::WindLayersArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nlayer; ++i) {
+        const xp_wind_layer &l = layers[i];
+        double bottom = l.bottom;
+        if (l.kind != XP_LAYER_PRESSURE && l.kind != XP_LAYER_PRESSURE_DEPTH && l.kind != XP_LAYER_HEIGHT)
+            return fail(XP_E_ARG, "%s: layers[%d]: unknown kind %d", entry, i, (int)l.kind);
+        if (!std::isfinite(l.top)) return fail(XP_E_ARG, "%s: layers[%d]: top must be finite", entry, i);
+        if (std::isinf(bottom)) return fail(XP_E_ARG, "%s: layers[%d]: bottom must be finite or NaN", entry, i);
+        if (l.kind == XP_LAYER_PRESSURE_DEPTH && !(l.top > 0.0)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive", entry, i);
+        if (l.kind == XP_LAYER_HEIGHT) {
+            if (!z) return fail(XP_E_ARG, "%s: layers[%d]: a layer by height needs height", entry, i);
+            if (std::isnan(bottom)) bottom = 0.0;
+            if (bottom < 0.0) return fail(XP_E_ARG, "%s: layers[%d]: bottom height must be >= 0", entry, i);
+            if (!(l.top > bottom)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive (top above bottom)", entry, i);
+        }
+        a.kind[i] = l.kind; a.bottom[i] = bottom; a.top[i] = l.top;
+    }
+    const size_t cb = rows_bytes(p, 1);
+    if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
+        (z && (rc = stage_view(st, z, &a.z)))) return rc;
+    bool want_max = false;
+    for (int i = 0; i < nlayer; ++i) {
+        if ((rc = st.out(out->mean_u[i], cb, out->mem, &a.mean_u[i])) || (rc = st.out(out->mean_v[i], cb, out->mem, &a.mean_v[i])) ||
+            (rc = st.out(out->shear_u[i], cb, out->mem, &a.shear_u[i])) || (rc = st.out(out->shear_v[i], cb, out->mem, &a.shear_v[i])) ||
+            (rc = st.out(out->bottom_u[i], cb, out->mem, &a.bottom_u[i])) || (rc = st.out(out->bottom_v[i], cb, out->mem, &a.bottom_v[i])) ||
+            (rc = st.out(out->max_u[i], cb, out->mem, &a.max_u[i])) || (rc = st.out(out->max_v[i], cb, out->mem, &a.max_v[i])) ||
+            (rc = st.out(out->max_pressure[i], cb, out->mem, &a.max_p[i]))) return rc;
+        want_max = want_max || a.max_u[i] || a.max_v[i] || a.max_p[i];
+    }
+    if ((rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = p->nlev; a.ncol = p->ncol; a.n = nlayer;
+    xp::launch_wind_layers(a, p->dtype == XP_F64, want_max, st.s);
+    return st.finish();
+}
+
+int xp_critical_angle(int64_t n, int32_t dtype, int32_t mem, const void *shear_u, const void *shear_v, const void *surface_u,
+                      const void *surface_v, const void *storm_u, const void *storm_v, void *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_critical_angle: bad n / dtype");
+    if (!shear_u || !shear_v || !surface_u || !surface_v || !storm_u || !storm_v || !out) return fail(XP_E_ARG, "xp_critical_angle: null argument");
+    const size_t b = (size_t)n * esize(dtype);
+    const void *src[6] = {shear_u, shear_v, surface_u, surface_v, storm_u, storm_v}, *in[6];
+    void *od;
+    int rc;
+    for (int i = 0; i < 6; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
+    if ((rc = st.out(out, b, mem, &od))) return rc;
+    xp::launch_critical_angle(n, dtype == XP_F64, in, od, st.s);
+    return st.finish();
+}
+
+int xp_corfidi_storm_motion(int64_t n, int32_t dtype, int32_t mem, const void *mean_u, const void *mean_v, const void *llj_u,
+                            const void *llj_v, void *upwind_u, void *upwind_v, void *downwind_u, void *downwind_v,
+                            void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_corfidi_storm_motion: bad n / dtype");
+    if (!mean_u || !mean_v || !llj_u || !llj_v) return fail(XP_E_ARG, "xp_corfidi_storm_motion: null argument");
+    const size_t b = (size_t)n * esize(dtype);
+    const void *src[4] = {mean_u, mean_v, llj_u, llj_v}, *in[4];
+    void *dst[4] = {upwind_u, upwind_v, downwind_u, downwind_v}, *od[4];
+    int rc;
+    for (int i = 0; i < 4; ++i) if ((rc = st.in(src[i], b, mem, &in[i])) || (rc = st.out(dst[i], b, mem, &od[i]))) return rc;
+    xp::launch_corfidi(n, dtype == XP_F64, in, od, st.s);
+    return st.finish();
+}
+
+int xp_significant_tornado_effective(int64_t n, int32_t dtype, int32_t mem, const void *mlcape, const void *mlcin,
+                                     const void *lcl_height, const void *esrh, const void *ebwd, const void *base_height,
+                                     void *out, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_significant_tornado_effective: bad n / dtype");
+    if (!mlcape || !mlcin || !lcl_height || !esrh || !ebwd || !out) return fail(XP_E_ARG, "xp_significant_tornado_effective: null argument");
+    const size_t b = (size_t)n * esize(dtype);
+    const void *src[6] = {mlcape, mlcin, lcl_height, esrh, ebwd, base_height}, *in[6];
+    void *od;
+    int rc;
+    for (int i = 0; i < 6; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
+    if ((rc = st.out(out, b, mem, &od))) return rc;
+    xp::launch_stp_effective(n, dtype == XP_F64, in, od, st.s);
     return st.finish();
 }
 

@@ -1,8 +1,9 @@
 """
 Storm motion, helicity and the composites on DataArrays: metpy.calc.bunkers_storm_motion, storm_relative_helicity,
-significant_tornado and supercell_composite for every column (or point) of a grid, and what feeds the composites' effective
-arguments -- the effective inflow layer and helicity / bulk wind difference between per-column bounds -- through libxparcel
-(numpy_api.bunkers_storm_motion, ...).  The reference has no counterparts, so this lives next to the mirror
+significant_tornado and supercell_composite for every column (or point) of a grid, what feeds the composites' effective
+arguments -- the effective inflow layer and helicity / bulk wind difference between per-column bounds -- and the wind over
+caller-chosen layers with what is built on it (mean_pressure_weighted, bulk_shear, critical_angle, corfidi_storm_motion, the
+effective-layer significant tornado parameter) through libxparcel (numpy_api.bunkers_storm_motion, ...).  The reference has no counterparts, so this lives next to the mirror
 (parcel_functions.py) rather than in it, and is built from the mirror's plumbing: a _Grid splits the inputs and wraps
 the results, _device turns library errors into the mirror's.
 """
@@ -38,11 +39,30 @@ _ATTRS = {
     'candidate_cin': {'long_name': 'CIN of the parcel lifted from the level', 'units': 'J kg$^{-1}$'},
     'significant_tornado': {'long_name': 'Significant tornado parameter', 'units': '1'},
     'supercell_composite': {'long_name': 'Supercell composite parameter', 'units': '1'},
+    'layer_mean_wind_u': {'long_name': 'Pressure-weighted mean wind of the layer, u component', 'units': _WIND},
+    'layer_mean_wind_v': {'long_name': 'Pressure-weighted mean wind of the layer, v component', 'units': _WIND},
+    'bulk_shear_u': {'long_name': 'Bulk shear over the layer (bounds in ln p), u component', 'units': _WIND},
+    'bulk_shear_v': {'long_name': 'Bulk shear over the layer (bounds in ln p), v component', 'units': _WIND},
+    'layer_bottom_wind_u': {'long_name': 'Wind at the bottom of the layer, u component', 'units': _WIND},
+    'layer_bottom_wind_v': {'long_name': 'Wind at the bottom of the layer, v component', 'units': _WIND},
+    'max_wind_u': {'long_name': 'Strongest wind of the layer, u component', 'units': _WIND},
+    'max_wind_v': {'long_name': 'Strongest wind of the layer, v component', 'units': _WIND},
+    'max_wind_pressure': {'long_name': 'Pressure of the strongest wind of the layer', 'units': 'hPa'},
+    'critical_angle': {'long_name': 'Critical angle', 'units': 'degrees'},
+    'corfidi_upwind_u': {'long_name': 'Corfidi upwind-propagating MCS motion, u component', 'units': _WIND},
+    'corfidi_upwind_v': {'long_name': 'Corfidi upwind-propagating MCS motion, v component', 'units': _WIND},
+    'corfidi_downwind_u': {'long_name': 'Corfidi downwind-propagating MCS motion, u component', 'units': _WIND},
+    'corfidi_downwind_v': {'long_name': 'Corfidi downwind-propagating MCS motion, v component', 'units': _WIND},
+    'significant_tornado_effective': {'long_name': 'Significant tornado parameter (effective layer)', 'units': '1'},
 }
 _BUNKERS = {'right_u': 'bunkers_right_u', 'right_v': 'bunkers_right_v', 'left_u': 'bunkers_left_u',
             'left_v': 'bunkers_left_v', 'mean_u': 'mean_wind_u', 'mean_v': 'mean_wind_v'}
 _SRH_NAMES = {'positive': 'positive_srh', 'negative': 'negative_srh', 'total': 'total_srh'}
 _LAYER_NAMES = dict(_SRH_NAMES, shear_u='shear_u', shear_v='shear_v', shear_magnitude='shear_magnitude')
+_WIND_LAYERS = {'mean_u': 'layer_mean_wind_u', 'mean_v': 'layer_mean_wind_v', 'shear_u': 'bulk_shear_u', 'shear_v': 'bulk_shear_v',
+                'bottom_u': 'layer_bottom_wind_u', 'bottom_v': 'layer_bottom_wind_v', 'max_u': 'max_wind_u',
+                'max_v': 'max_wind_v', 'max_pressure': 'max_wind_pressure'}
+_CORFIDI = {k: 'corfidi_' + k for k in ('upwind_u', 'upwind_v', 'downwind_u', 'downwind_v')}
 _EFFECTIVE = ('base_pressure', 'top_pressure', 'base_height', 'top_height', 'base_index', 'top_index', 'status')
 
 
@@ -128,3 +148,65 @@ def supercell_composite(mucape, effective_storm_helicity, effective_shear):
     g = _Grid(mucape, None)
     out = _device(_api.supercell_composite, *(g.values(x) for x in (mucape, effective_storm_helicity, effective_shear)))
     return g.horiz(out, 'supercell_composite', _ATTRS['supercell_composite'])
+
+
+def wind_layers(pressure, u, v, height=None, layers=(), vert_dim=VERT):
+    """The wind over up to four layers of every column in one pass: `layers` as in numpy_api.wind_layers -- {'bottom': 850,
+    'top': 300} or {'depth': 100} in hPa, {'bottom_height': 0, 'top_height': 6000} in metres above the lowest valid level
+    (needs `height`).  Returns a Dataset under the leading dim 'wind_layer' (the layer's index): the pressure-weighted mean
+    wind, the ln p bulk shear, the wind at the bottom, the strongest wind and its pressure, and the per-column status.
+    Layers that a column does not span are NaN."""
+    g = _Grid(pressure, vert_dim)
+    res = _device(_api.wind_layers, g.values(pressure), g.values(u), g.values(v), None if height is None else g.values(height),
+                  layers=layers)
+    ds = _per_layer(g, res, _WIND_LAYERS, 'wind_layer', np.arange(len(layers)))
+    ds['status'] = g.horiz(_host(res['status']), 'status', _ATTRS['status'])
+    return ds
+
+
+def _pair(g, fn, names, *args, **kw):
+    res = _device(fn, *args, **kw)
+    return Dataset({name: g.horiz(_host(x), name, _ATTRS[name]) for name, x in zip(names, res)})
+
+
+def mean_pressure_weighted(pressure, u, v, height=None, bottom=None, depth=100.0, vert_dim=VERT):
+    """metpy.calc.mean_pressure_weighted of the wind for every column, as a Dataset of layer_mean_wind_u / _v.  bottom,
+    depth: metres (bottom above the lowest valid level) if `height` is given and `bottom` is not None, hPa otherwise
+    (bottom=None: the lowest valid level) -- numpy_api.mean_pressure_weighted states the rule."""
+    g = _Grid(pressure, vert_dim)
+    return _pair(g, _api.mean_pressure_weighted, ('layer_mean_wind_u', 'layer_mean_wind_v'), g.values(pressure), g.values(u),
+                 g.values(v), None if height is None else g.values(height), bottom=bottom, depth=depth)
+
+
+def bulk_shear(pressure, u, v, height=None, bottom=None, depth=100.0, vert_dim=VERT):
+    """metpy.calc.bulk_shear for every column, as a Dataset of bulk_shear_u / _v; bottom, depth as in mean_pressure_weighted."""
+    g = _Grid(pressure, vert_dim)
+    return _pair(g, _api.bulk_shear, ('bulk_shear_u', 'bulk_shear_v'), g.values(pressure), g.values(u), g.values(v),
+                 None if height is None else g.values(height), bottom=bottom, depth=depth)
+
+
+def critical_angle(pressure, u, v, height, storm_u, storm_v, vert_dim=VERT):
+    """metpy.calc.critical_angle [degrees] for every column: the angle between the 0-500 m bulk shear and the storm-relative
+    inflow at the lowest valid level; storm_u / storm_v scalars or DataArrays on the horizontal dims."""
+    g = _Grid(pressure, vert_dim)
+    out = _device(_api.critical_angle, g.values(pressure), g.values(u), g.values(v), g.values(height), _per_col(g, storm_u),
+                  _per_col(g, storm_v))
+    return g.horiz(out, 'critical_angle', _ATTRS['critical_angle'])
+
+
+def corfidi_storm_motion(pressure, u, v, llj_u=None, llj_v=None, vert_dim=VERT):
+    """Corfidi upwind- and downwind-propagating MCS motion of every column, as a Dataset; the low-level jet (scalars or
+    DataArrays on the horizontal dims, both or neither) defaults to the strongest wind at or below 850 hPa."""
+    g = _Grid(pressure, vert_dim)
+    res = _device(_api.corfidi_storm_motion, g.values(pressure), g.values(u), g.values(v), llj_u=_per_col(g, llj_u),
+                  llj_v=_per_col(g, llj_v))
+    return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _CORFIDI.items()})
+
+
+def significant_tornado_effective(mlcape, mlcin, lcl_height, esrh, ebwd, base_height=None):
+    """SPC's effective-layer significant tornado parameter per point; base_height: effective_inflow_layer's base_height
+    (where it is > 0 the result is 0)."""
+    g = _Grid(mlcape, None)
+    args = [g.values(x) for x in (mlcape, mlcin, lcl_height, esrh, ebwd)]
+    out = _device(_api.significant_tornado_effective, *args, base_height=None if base_height is None else g.values(base_height))
+    return g.horiz(out, 'significant_tornado_effective', _ATTRS['significant_tornado_effective'])

@@ -828,6 +828,133 @@ def supercell_composite(mucape, effective_storm_helicity, effective_shear):
     return out
 
 
+def _wind_layer(spec):
+    """One layer of wind_layers() as (kind, bottom, top) of xp_wind_layer.  A dict: bottom= [hPa; None or absent: the lowest
+    valid level] with top= [hPa] or depth= [hPa], or bottom_height= [m above the lowest valid level; default 0] with
+    top_height= [m].  A tuple: ('pressure', bottom, top), ('pressure_depth', bottom, depth) or ('height', bottom, top)."""
+    kinds = {'pressure': L.LAYER_PRESSURE, 'pressure_depth': L.LAYER_PRESSURE_DEPTH, 'height': L.LAYER_HEIGHT}
+    if isinstance(spec, dict):
+        assert set(spec) <= {'bottom', 'top', 'depth', 'bottom_height', 'top_height'}, 'layer: unknown key in %r' % (spec,)
+        if 'top_height' in spec:
+            assert set(spec) <= {'bottom_height', 'top_height'}, 'layer: heights and pressures cannot be mixed'
+            kind, bottom, top = 'height', spec.get('bottom_height', 0.0), spec['top_height']
+        else:
+            assert ('top' in spec) != ('depth' in spec) and 'bottom_height' not in spec, 'layer: give top= or depth= (hPa), or top_height='
+            kind, bottom, top = ('pressure', spec.get('bottom'), spec['top']) if 'top' in spec else ('pressure_depth', spec.get('bottom'), spec['depth'])
+    else:
+        kind, bottom, top = spec
+    assert kind in kinds, "layer: kind must be 'pressure', 'pressure_depth' or 'height'"
+    return kinds[kind], float('nan') if bottom is None else float(bottom), float(top)
+
+
+def wind_layers(pressure, u, v, height=None, layers=(), want=None):
+    """The wind over up to four layers of every column in one pass (xp_wind_layers): pressure [hPa], u, v [m/s] and, for
+    layers given by height, height [m] on one vertical, (nlev, ...).  `layers`: a sequence of layers, each a dict or a tuple
+    (see _wind_layer): {'bottom': 850, 'top': 300}, {'depth': 100} (the lowest 100 hPa), {'bottom_height': 0, 'top_height':
+    6000}.  Returns a dict with a leading layer axis: 'mean_u', 'mean_v' (metpy.calc.mean_pressure_weighted), 'shear_u',
+    'shear_v' (metpy.calc.bulk_shear: top minus bottom, the bounds interpolated in ln p), 'bottom_u', 'bottom_v' (the wind
+    at the layer's bottom), 'max_u', 'max_v', 'max_pressure' (the layer's strongest wind and where it blows) -- or those of
+    them that `want` names -- and the per-column 'status' (XP_ST_NO_LAYER: some layer is empty or not spanned by the column,
+    its values NaN; ST_BAD_HEIGHT / ST_BAD_PRESSURE: levels out of order, everything NaN)."""
+    specs = [_wind_layer(s) for s in layers]
+    assert 1 <= len(specs) <= L.WIND_MAX_LAYERS, 'layers: one to four layers'
+    assert height is not None or all(k != L.LAYER_HEIGHT for k, _, _ in specs), 'a layer given by height needs height'
+    keys = L.WIND_LAYERS_OUT if want is None else tuple(want)
+    assert set(keys) <= set(L.WIND_LAYERS_OUT), 'want: unknown output'
+    c = _Call(pressure, u, v, *(() if height is None else (height,)))
+    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, u, v, height must share a shape'
+    n = len(specs)
+    res = {k: c.out((n,) + c.hshape) for k in keys}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = L.WindLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in keys:
+        arr = getattr(out, k)
+        for i in range(n):
+            arr[i] = _ptr(res[k][i:i + 1])
+    views = [c.view(a) for a in c.ins] + [None]
+    c.run('xp_wind_layers', *views[:4], n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]), out)
+    return res
+
+
+def _one_layer(pressure, u, v, height, bottom, depth, want):
+    """The layer of mean_pressure_weighted / bulk_shear, which take MetPy's bottom= and depth= without its units: with
+    `height` AND `bottom` given, bottom and depth are metres, bottom counted from the lowest valid level; otherwise they are
+    hPa, bottom=None being the lowest valid level."""
+    if height is not None and bottom is not None:
+        layer = ('height', bottom, float(bottom) + float(depth))
+    else:
+        height, layer = None, ('pressure_depth', bottom, depth)
+    res = wind_layers(pressure, u, v, height, [layer], want=want)
+    return tuple(res[k][0] for k in want), res['status']
+
+
+def mean_pressure_weighted(pressure, u, v, height=None, bottom=None, depth=100.0):
+    """metpy.calc.mean_pressure_weighted of the wind for every column: (mean_u, mean_v) [m/s] over the layer from `bottom` up
+    `depth`.  The exact rule for the two, MetPy's taking them with units: if `height` [m] is given and `bottom` is not
+    None, bottom and depth are metres and bottom is counted from the lowest valid level (0: that level); in every other
+    case they are hPa and bottom=None is the lowest valid level -- so the defaults are MetPy's, the lowest 100 hPa.  Columns
+    that do not span the layer are NaN."""
+    return _one_layer(pressure, u, v, height, bottom, depth, ('mean_u', 'mean_v'))[0]
+
+
+def bulk_shear(pressure, u, v, height=None, bottom=None, depth=100.0):
+    """metpy.calc.bulk_shear for every column: (shear_u, shear_v) [m/s], the wind at the top of the layer minus the wind at
+    its bottom, each interpolated in ln p where it lies between levels.  bottom, depth: as in mean_pressure_weighted."""
+    return _one_layer(pressure, u, v, height, bottom, depth, ('shear_u', 'shear_v'))[0]
+
+
+def _per_point(entry, ins, per_col, nout, extra=()):
+    """A per-point entry point on the arrays `ins` (one shape) and the per-column arguments `per_col` (scalars broadcast;
+    CUDA tensors among them take part in deciding the device): `nout` outputs of that shape."""
+    c = _Call(*ins, *[x for x in per_col if _is_torch(x)])
+    assert all(a.shape == c.ins[0].shape for a in c.ins[:len(ins)]), 'per-point arguments must share a shape'
+    shape = tuple(c.ins[0].shape)
+    n = int(np.prod(shape))
+    cols = []
+    for x in per_col:
+        if x is not None and not _is_torch(x) and np.ndim(x) == 0:
+            x = np.full(n, x, dtype=c.dtype)
+        cols.append(None if x is None else c.array(x).reshape(-1))
+    assert all(a is None or int(np.prod(a.shape)) == n for a in cols), 'per-point arguments must share a shape'
+    outs = [c.out(shape) for _ in range(nout)]
+    c.run(entry, n, c.xp_dtype, c.mem, *c.ins[:len(ins)], *cols, *extra, *outs)
+    return outs
+
+
+def critical_angle(pressure, u, v, height, storm_u, storm_v):
+    """metpy.calc.critical_angle for every column [degrees]: the angle between the 0-500 m bulk shear and the storm-relative
+    inflow at the lowest valid level, storm_u / storm_v being scalars or one value per column (e.g. bunkers_storm_motion's
+    right_u, right_v; CUDA tensors stay on the device).  One wind_layers call (0-500 m above the lowest valid level by
+    height: shear_* and bottom_*), then xp_critical_angle.  NaN where the column does not reach 500 m or a vector is zero."""
+    wl = wind_layers(pressure, u, v, height, [('height', 0.0, 500.0)], want=('shear_u', 'shear_v', 'bottom_u', 'bottom_v'))
+    return _per_point('xp_critical_angle', [wl[k][0] for k in ('shear_u', 'shear_v', 'bottom_u', 'bottom_v')],
+                      (storm_u, storm_v), 1)[0]
+
+
+def corfidi_storm_motion(pressure, u, v, llj_u=None, llj_v=None):
+    """Corfidi (2003) upwind- and downwind-propagating MCS motion for every column (metpy.calc.corfidi_storm_motion): the
+    mean wind is the 850-300 hPa pressure-weighted mean; the low-level jet llj_u / llj_v (both or neither; scalars or one
+    value per column) defaults to the strongest wind at or below 850 hPa -- both from ONE wind_layers call.  Returns a dict of
+    'upwind_u', 'upwind_v', 'downwind_u', 'downwind_v' [m/s] and the 'status' of the wind_layers call; columns whose lowest
+    level lies above 850 hPa or that end below 300 hPa are NaN."""
+    assert (llj_u is None) == (llj_v is None), 'llj_u, llj_v: give both or neither'
+    layers, want = [('pressure', 850.0, 300.0)], ('mean_u', 'mean_v')
+    if llj_u is None:
+        layers, want = layers + [('pressure', None, 850.0)], want + ('max_u', 'max_v')
+    wl = wind_layers(pressure, u, v, None, layers, want=want)
+    ins = [wl['mean_u'][0], wl['mean_v'][0]] + ([wl['max_u'][1], wl['max_v'][1]] if llj_u is None else [])
+    outs = _per_point('xp_corfidi_storm_motion', ins, () if llj_u is None else (llj_u, llj_v), 4)
+    return dict(zip(('upwind_u', 'upwind_v', 'downwind_u', 'downwind_v'), outs), status=wl['status'])
+
+
+def significant_tornado_effective(mlcape, mlcin, lcl_height, esrh, ebwd, base_height=None):
+    """SPC's effective-layer significant tornado parameter per point (xp_significant_tornado_effective): mixed-layer CAPE
+    and CIN [J/kg; CIN <= 0], mixed-layer LCL height [m], effective SRH [m^2/s^2] and effective bulk wind difference [m/s].
+    base_height [m]: the effective inflow base (effective_inflow_layer's base_height); where it is > 0 the result is 0."""
+    ins = [mlcape, mlcin, lcl_height, esrh, ebwd] + ([] if base_height is None else [base_height])
+    return _per_point('xp_significant_tornado_effective', ins, (), 1, extra=(None,) if base_height is None else ())[0]
+
+
 def conv_properties(dat, ignore_nans=False, moist=None):
     """pf.py:1951: the reference's convective-property bundle for a grid, ONE library call (xp_conv_properties): the
     q -> dewpoint step, the NaN mask, the fixed-level interpolations and the freezing / melting levels are one pass over
