@@ -293,6 +293,30 @@ def test_per_point_kernels_vs_restatement():
             want = R.significant_tornado_effective(*s[:5], base_height=b).astype(dtype)
             assert stp.dtype == dtype and np.array_equal(stp, want, equal_nan=True), (dtype, b is None)
     assert np.isnan(stp[[24, 25]]).all() and stp[21] == 0.0 and np.isnan(stp[4]) and np.isnan(stp[10]) and (stp == 0.0).sum() >= 2500
+    # n = 1 (one lane of one workgroup) through all six products, against the restatements of this file and its neighbours
+    one = [np.array([t]) for t in (2500.0, -60.0, 1200.0, 180.0, 22.0, 0.0)]
+    w = [np.array([t]) for t in (3.0, -1.0, 6.0, 2.0, 9.0, -4.0)]
+    assert np.array_equal(xa.significant_tornado_effective(*one[:5], base_height=one[5]), R.significant_tornado_effective(*one[:5], base_height=one[5]))
+    assert np.array_equal(xa.significant_tornado(one[0], one[2], one[3], one[4]), K.significant_tornado(one[0], one[2], one[3], one[4]))
+    assert np.array_equal(xa.supercell_composite(one[0], one[3], one[4]), K.supercell_composite(one[0], one[3], one[4]))
+    assert abs(xa._per_point('xp_critical_angle', w, (), 1)[0][0] - R.critical_angle(*w)[0]) <= 1e-12
+    for g, want in zip(xa._per_point('xp_corfidi_storm_motion', w[:4], (), 4), R.corfidi_storm_motion(*w[:4])):
+        assert g.shape == (1,) and np.array_equal(g, want)
+    ship = xa.significant_hail_parameter(*[np.array([t]) for t in (2000.0, 0.012, -7.0, 258.15, 20.0, 3000.0)])
+    assert ship.shape == (1,) and np.isfinite(ship[0]) and ship[0] > 0.0
+    # n = 0: XP_OK, and nothing is written -- the buffers handed over hold eight elements each
+    lib = L.init(0)
+    x, y = np.ones(8), np.full(8, -77.0)
+    xd, yd = x.ctypes.data, y.ctypes.data
+    for D in (L.XP_F64, L.XP_F32):
+        H = L.XP_MEM_HOST
+        assert lib.xp_significant_hail_parameter(0, D, H, xd, xd, xd, xd, xd, xd, yd, None) == L.XP_OK
+        assert lib.xp_significant_tornado(0, D, H, xd, xd, xd, xd, yd, None) == L.XP_OK
+        assert lib.xp_supercell_composite(0, D, H, xd, xd, xd, yd, None) == L.XP_OK
+        assert lib.xp_critical_angle(0, D, H, xd, xd, xd, xd, xd, xd, yd, None) == L.XP_OK
+        assert lib.xp_corfidi_storm_motion(0, D, H, xd, xd, xd, xd, yd, yd, yd, yd, None) == L.XP_OK
+        assert lib.xp_significant_tornado_effective(0, D, H, xd, xd, xd, xd, xd, xd, yd, None) == L.XP_OK
+        assert np.all(y == -77.0) and np.all(x == 1.0)
 
 
 # -- 5. the chains, on the device ----------------------------------------------------------------------------------------------

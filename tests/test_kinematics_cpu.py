@@ -286,9 +286,12 @@ def test_parcel_functions_gains_nothing():
 @needs_hipcc
 def test_kernels_keep_four_waves_per_simd_without_spills(tmp_path):
     rec = resources(tmp_path, 'xparcel.hip')
-    kernels = [n for n in rec if re.search(r'k_(bunkers_storm_motion|storm_relative_helicity|significant_tornado|'
-                                           r'supercell_composite)I', n)]
+    # the two composites are instantiations of the one per-point kernel (csrc/xp_per_point.hpp) on their operations
+    kernels = [n for n in rec if re.search(r'k_(bunkers_storm_motion|storm_relative_helicity)I[df]E|'
+                                           r'k_per_pointI[df]NS_\d+(StpOp|ScpOp)E', n)]
     assert len(kernels) == 8, sorted(rec)
+    for k in ('k_bunkers_storm_motion', 'k_storm_relative_helicity', 'StpOp', 'ScpOp'):
+        assert sum(k in n for n in kernels) == 2, (k, kernels)
     for n in kernels:
         assert rec[n]['in_asm'] and not rec[n]['scratch_insts'], n
         assert rec[n]['vgprs'] <= 128 and rec[n]['occupancy'] >= 4 and rec[n]['scratch'] == 0, (n, rec[n])

@@ -356,9 +356,11 @@ def test_no_instantiation_spills(tmp_path):
         if m:
             walk[(m.group(1), int(m.group(2)), int(m.group(3)))] = r
     assert sorted(walk) == sorted((t, n, m) for t in 'df' for n in (1, 2, 3, 4) for m in (0, 1)), sorted(rec)
-    point = [n for n in rec if re.search(r'k_(critical_angle|corfidi_storm_motion|significant_tornado_effective)I', n)]
-    assert len(point) == 6
-    for key, r in list(walk.items()) + [(n, rec[n]) for n in point]:
+    # the three per-point products are instantiations of k_per_point, which lives in the main unit
+    main = resources(tmp_path, 'xparcel.hip')
+    point = [n for n in main if re.search(r'k_per_pointI[df]NS_\d+(CriticalAngleOp|CorfidiOp|StpEffectiveOp)E', n)]
+    assert len(point) == 6, sorted(main)
+    for key, r in list(walk.items()) + [(n, main[n]) for n in point]:
         print(key, r)
         assert r['in_asm'] and r['vgpr_spill'] == 0 and r['scratch'] == 0 and not r['scratch_insts'] and not r['spills'], (key, r)
         assert r['occupancy'] >= 2, (key, r)

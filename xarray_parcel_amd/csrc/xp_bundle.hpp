@@ -178,14 +178,6 @@ XP_DEV double ship_value(double mucape, double mixing_ratio, double lapse, doubl
     ship = (flh >= 2400.0) ? ship : ship * (flh / 2400.0);
     return ship;
 }
-template <typename T> __global__ __launch_bounds__(256)
-void k_ship(int64_t n, const void *mucape, const void *mixing_ratio, const void *lapse, const void *temp_500, const void *shear,
-            const void *flh, void *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    st(out, sizeof(T) == 8, c, ship_value(ld1<T>(mucape, c), ld1<T>(mixing_ratio, c), ld1<T>(lapse, c), ld1<T>(temp_500, c),
-                                          ld1<T>(shear, c), ld1<T>(flh, c)));
-}
 
 // storm_proxies (pf.py:2323-2407): the nine hail / storm proxies and SHIP from the bundle's per-point values.  Comparisons
 // with NaN are false, as in NumPy.

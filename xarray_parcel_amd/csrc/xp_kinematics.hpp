@@ -3,7 +3,8 @@
 //   k_storm_relative_helicity  metpy.calc.storm_relative_helicity for up to four depths, one thread per column;
 //   k_helicity_layers          the same between per-column bounds (up to four tops sharing a bottom), plus the bulk wind
 //                              difference over each layer -- both are helicity_walk, one with LAYERS and one without;
-//   k_significant_tornado, k_supercell_composite   per point, in MetPy's operation order.
+//   stp_value, scp_value       metpy.calc.significant_tornado and supercell_composite per point, in MetPy's operation
+//                              order (their kernel is k_per_point, xp_per_point.hpp).
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/kinematics_restatement.py.  Each column kernel
 // makes one upward pass with level-major loads (coalesced when col_stride == 1): the layer points of MetPy's get_layer /
 // get_layer_heights are emitted in order as the walk passes them -- the levels themselves, and the added bound points
@@ -297,18 +298,6 @@ XP_DEV double scp_value(double mucape, double srh, double shear) {
     double shr = shear < 10.0 ? 0.0 : (shear > 20.0 ? 20.0 : shear);
     shr = shr / 20.0;
     return (mucape / 1000.0) * (srh / 50.0) * shr;
-}
-template <typename T> __global__ __launch_bounds__(256)
-void k_significant_tornado(int64_t n, const void *sbcape, const void *lcl_height, const void *srh, const void *shear, void *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    st(out, sizeof(T) == 8, c, stp_value(ld1<T>(sbcape, c), ld1<T>(lcl_height, c), ld1<T>(srh, c), ld1<T>(shear, c)));
-}
-template <typename T> __global__ __launch_bounds__(256)
-void k_supercell_composite(int64_t n, const void *mucape, const void *srh, const void *shear, void *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    st(out, sizeof(T) == 8, c, scp_value(ld1<T>(mucape, c), ld1<T>(srh, c), ld1<T>(shear, c)));
 }
 
 }  // namespace xp

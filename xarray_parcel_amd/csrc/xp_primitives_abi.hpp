@@ -219,19 +219,8 @@ int xp_wind_shear(const xp_view *wind_u, const xp_view *wind_v, const xp_view *h
 int xp_significant_hail_parameter(int64_t n, int32_t dtype, int32_t mem, const void *mucape, const void *mixing_ratio,
                                   const void *lapse, const void *temp_500, const void *shear, const void *flh, void *out,
                                   void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_significant_hail_parameter: bad n / dtype");
-    if (!mucape || !mixing_ratio || !lapse || !temp_500 || !shear || !flh || !out) return fail(XP_E_ARG, "xp_significant_hail_parameter: null argument");
-    const size_t b = (size_t)n * esize(dtype);
-    const void *in[6];
-    const void *src[6] = {mucape, mixing_ratio, lapse, temp_500, shear, flh};
-    void *od;
-    int rc;
-    for (int i = 0; i < 6; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
-    if ((rc = st.out(out, b, mem, &od))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_ship<decltype(z)>, n, st, n, in[0], in[1], in[2], in[3], in[4], in[5], od); });
-    return st.finish();
+    return per_point<xp::ShipOp>("xp_significant_hail_parameter", n, dtype, mem, {mucape, mixing_ratio, lapse, temp_500, shear, flh}, 6,
+                                 {out}, true, stream);
 }
 
 int xp_storm_proxies(int64_t n, int32_t dtype, int32_t mem, const xp_proxies_in *in, xp_proxies_out *out, void *stream) {

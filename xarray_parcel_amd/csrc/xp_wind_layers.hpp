@@ -1,8 +1,8 @@
-// xp_wind_layers.hpp -- the wind over caller-chosen layers, and three per-point products built on it (MetPy 1.4):
+// xp_wind_layers.hpp -- the wind over caller-chosen layers, and two per-point products built on it (MetPy 1.4):
 //   k_wind_layers   metpy.calc.mean_pressure_weighted and bulk_shear over up to four layers given by pressure, by pressure
 //                   depth or by height above the lowest level, the wind at each layer's bottom and the layer's strongest
 //                   wind, one thread per column;
-//   k_critical_angle, k_corfidi_storm_motion, k_significant_tornado_effective   per point.
+//   critical_angle_value, stp_effective_value   per point (their kernel is k_per_point, xp_per_point.hpp).
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/wind_layers_restatement.py.  The column kernel is
 // the walk of k_bunkers_storm_motion (xp_kinematics.hpp) with the layers as arguments: one upward pass with level-major
 // loads (coalesced when col_stride == 1) serves every layer of the call whatever its kind; the points of MetPy's get_layer
@@ -34,9 +34,6 @@ struct WindLayersArgs {
 
 // (n layers, strongest wind wanted) of a call in the views' dtype: which instantiation runs it
 void launch_wind_layers(const WindLayersArgs &a, bool f64, bool want_max, hipStream_t s);
-void launch_critical_angle(int64_t n, bool f64, const void *const in[6], void *out, hipStream_t s);
-void launch_corfidi(int64_t n, bool f64, const void *const in[4], void *const out[4], hipStream_t s);
-void launch_stp_effective(int64_t n, bool f64, const void *const in[6], void *out, hipStream_t s);
 
 // The running state of one layer.  The trapezoids of mean_pressure_weighted, trapz(U P, P), are summed of the wind relative to
 // the layer's first point (u0, v0), so that mean = u0 + trapz((U - u0) P, P) / (0.5 (P_last^2 - P_first^2)) is exact for a
@@ -171,7 +168,7 @@ void k_wind_layers(WindLayersArgs a) {
     sti(a.status, c, status);
 }
 
-// ---- per point ---------------------------------------------------------------------------------------------------------
+// ---- per point: the value functions ------------------------------------------------------------------------------------
 // metpy.calc.critical_angle as atan2(|a x b|, a . b) [degrees]: a the 0-500 m shear, b the storm-relative surface inflow
 XP_DEV double critical_angle_value(double au, double av, double su, double sv, double cu, double cv) {
 #pragma clang fp contract(off)
@@ -190,36 +187,6 @@ XP_DEV double stp_effective_value(double mlcape, double mlcin, double lcl_height
     double shr = ebwd < 12.5 ? 0.0 : (ebwd > 30.0 ? 30.0 : ebwd);
     shr = shr / 20.0;
     return ((((mlcape / 1500.0) * lcl) * (esrh / 150.0)) * shr) * cin;
-}
-template <typename T> __global__ __launch_bounds__(256)
-void k_critical_angle(int64_t n, const void *shear_u, const void *shear_v, const void *surface_u, const void *surface_v,
-                      const void *storm_u, const void *storm_v, void *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    st(out, sizeof(T) == 8, c, critical_angle_value(ld1<T>(shear_u, c), ld1<T>(shear_v, c), ld1<T>(surface_u, c),
-                                                    ld1<T>(surface_v, c), ld1<T>(storm_u, c), ld1<T>(storm_v, c)));
-}
-// Corfidi (2003): upwind = mean - jet, downwind = mean + upwind
-template <typename T> __global__ __launch_bounds__(256)
-void k_corfidi_storm_motion(int64_t n, const void *mean_u, const void *mean_v, const void *llj_u, const void *llj_v,
-                            void *upwind_u, void *upwind_v, void *downwind_u, void *downwind_v) {
-#pragma clang fp contract(off)
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    constexpr int f64 = sizeof(T) == 8;
-    const double mu = ld1<T>(mean_u, c), mv = ld1<T>(mean_v, c);
-    const double uu = mu - ld1<T>(llj_u, c), uv = mv - ld1<T>(llj_v, c);
-    st(upwind_u, f64, c, uu); st(upwind_v, f64, c, uv);
-    st(downwind_u, f64, c, mu + uu); st(downwind_v, f64, c, mv + uv);
-}
-template <typename T> __global__ __launch_bounds__(256)
-void k_significant_tornado_effective(int64_t n, const void *mlcape, const void *mlcin, const void *lcl_height,
-                                     const void *esrh, const void *ebwd, const void *base_height, void *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    double r = stp_effective_value(ld1<T>(mlcape, c), ld1<T>(mlcin, c), ld1<T>(lcl_height, c), ld1<T>(esrh, c), ld1<T>(ebwd, c));
-    if (base_height && ld1<T>(base_height, c) > 0.0) r = 0.0;             // the inflow layer is not surface based
-    st(out, sizeof(T) == 8, c, r);
 }
 
 }  // namespace xp

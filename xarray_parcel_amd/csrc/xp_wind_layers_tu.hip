@@ -1,4 +1,4 @@
-// The translation unit of k_wind_layers and the per-point kernels of xp_wind_layers.hpp, and their launchers.
+// The translation unit of k_wind_layers (xp_wind_layers.hpp) and its launcher.
 #include <hip/hip_runtime.h>
 
 #include "xp_wind_layers.hpp"
@@ -23,24 +23,6 @@ void launch_wind_layers(const WindLayersArgs &a, bool f64, bool want_max, hipStr
     if (a.ncol <= 0) return;
     if (f64) { if (want_max) launch_nl<double, true>(a, s); else launch_nl<double, false>(a, s); }
     else { if (want_max) launch_nl<float, true>(a, s); else launch_nl<float, false>(a, s); }
-}
-
-void launch_critical_angle(int64_t n, bool f64, const void *const in[6], void *out, hipStream_t s) {
-    if (n <= 0) return;
-    if (f64) hipLaunchKernelGGL(k_critical_angle<double>, grid(n), dim3(256), 0, s, n, in[0], in[1], in[2], in[3], in[4], in[5], out);
-    else hipLaunchKernelGGL(k_critical_angle<float>, grid(n), dim3(256), 0, s, n, in[0], in[1], in[2], in[3], in[4], in[5], out);
-}
-
-void launch_corfidi(int64_t n, bool f64, const void *const in[4], void *const out[4], hipStream_t s) {
-    if (n <= 0) return;
-    if (f64) hipLaunchKernelGGL(k_corfidi_storm_motion<double>, grid(n), dim3(256), 0, s, n, in[0], in[1], in[2], in[3], out[0], out[1], out[2], out[3]);
-    else hipLaunchKernelGGL(k_corfidi_storm_motion<float>, grid(n), dim3(256), 0, s, n, in[0], in[1], in[2], in[3], out[0], out[1], out[2], out[3]);
-}
-
-void launch_stp_effective(int64_t n, bool f64, const void *const in[6], void *out, hipStream_t s) {
-    if (n <= 0) return;
-    if (f64) hipLaunchKernelGGL(k_significant_tornado_effective<double>, grid(n), dim3(256), 0, s, n, in[0], in[1], in[2], in[3], in[4], in[5], out);
-    else hipLaunchKernelGGL(k_significant_tornado_effective<float>, grid(n), dim3(256), 0, s, n, in[0], in[1], in[2], in[3], in[4], in[5], out);
 }
 
 }  // namespace xp

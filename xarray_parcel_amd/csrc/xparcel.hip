@@ -19,6 +19,7 @@
 #include "xp_kinematics.hpp"
 #include "xp_effective.hpp"
 #include "xp_wind_layers.hpp"
+#include "xp_per_point.hpp"
 
 static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_ST_LCL_NOT_CONVERGED &&
               xp::ST_NAN_PRESSURE == XP_ST_NAN_PRESSURE && xp::ST_BAD_PRESSURE == XP_ST_BAD_PRESSURE &&
@@ -325,6 +326,29 @@ template <typename F> void by_dtype(int dtype, F &&f) {
 // one thread per element of an n-element grid, 256 per workgroup, on the call's stream; n == 0 launches nothing
 template <typename... P, typename... A> void launch(void (*k)(P...), int64_t n, const Stager &st, const A &...args) {
     if (n > 0) hipLaunchKernelGGL(k, dim3(blocks(n)), dim3(256), 0, st.s, args...);
+}
+
+// A per-point entry point (kernel and operations: xp_per_point.hpp): n points of dtype in mem.  The first n_required of
+// `in` must be given, the rest may be null, and so may the outputs unless out_required.
+template <typename Op> int per_point(const char *entry, int64_t n, int32_t dtype, int32_t mem, std::initializer_list<const void *> in,
+                                     int n_required, std::initializer_list<void *> out, bool out_required, void *stream) {
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "%s: bad n / dtype", entry);
+    bool null = false;
+    for (int i = 0; i < n_required; ++i) null = null || !in.begin()[i];
+    for (void *o : out) null = null || (out_required && !o);
+    if (null) return fail(XP_E_ARG, "%s: null argument", entry);
+    const size_t b = (size_t)n * esize(dtype);
+    xp::PointArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n;
+    int rc, i = 0;
+    for (const void *p : in) if ((rc = st.in(p, b, mem, &a.in[i++]))) return rc;
+    i = 0;
+    for (void *p : out) if ((rc = st.out(p, b, mem, &a.out[i++]))) return rc;
+    by_dtype(dtype, [&](auto z) { launch(xp::k_per_point<decltype(z), Op>, n, st, a); });
+    return st.finish();
 }
 
 int stage_scalars(Stager &st, xp_scalars_out *s, int64_t ncol, xp::ScalarsOut *o) {
@@ -1132,34 +1156,12 @@ int xp_storm_relative_helicity_layers(const xp_view *z, const xp_view *u, const 
 
 int xp_significant_tornado(int64_t n, int32_t dtype, int32_t mem, const void *sbcape, const void *lcl_height, const void *srh,
                            const void *shear, void *out, void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_significant_tornado: bad n / dtype");
-    if (!sbcape || !lcl_height || !srh || !shear || !out) return fail(XP_E_ARG, "xp_significant_tornado: null argument");
-    const size_t b = (size_t)n * esize(dtype);
-    const void *src[4] = {sbcape, lcl_height, srh, shear}, *in[4];
-    void *od;
-    int rc;
-    for (int i = 0; i < 4; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
-    if ((rc = st.out(out, b, mem, &od))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_significant_tornado<decltype(z)>, n, st, n, in[0], in[1], in[2], in[3], od); });
-    return st.finish();
+    return per_point<xp::StpOp>("xp_significant_tornado", n, dtype, mem, {sbcape, lcl_height, srh, shear}, 4, {out}, true, stream);
 }
 
 int xp_supercell_composite(int64_t n, int32_t dtype, int32_t mem, const void *mucape, const void *srh, const void *shear,
                            void *out, void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_supercell_composite: bad n / dtype");
-    if (!mucape || !srh || !shear || !out) return fail(XP_E_ARG, "xp_supercell_composite: null argument");
-    const size_t b = (size_t)n * esize(dtype);
-    const void *src[3] = {mucape, srh, shear}, *in[3];
-    void *od;
-    int rc;
-    for (int i = 0; i < 3; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
-    if ((rc = st.out(out, b, mem, &od))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_supercell_composite<decltype(z)>, n, st, n, in[0], in[1], in[2], od); });
-    return st.finish();
+    return per_point<xp::ScpOp>("xp_supercell_composite", n, dtype, mem, {mucape, srh, shear}, 3, {out}, true, stream);
 }
 
 int xp_wind_layers(const xp_view *p, const xp_view *u, const xp_view *v, const xp_view *z, int32_t nlayer,
@@ -1211,51 +1213,22 @@ int xp_wind_layers(const xp_view *p, const xp_view *u, const xp_view *v, const x
 
 int xp_critical_angle(int64_t n, int32_t dtype, int32_t mem, const void *shear_u, const void *shear_v, const void *surface_u,
                       const void *surface_v, const void *storm_u, const void *storm_v, void *out, void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_critical_angle: bad n / dtype");
-    if (!shear_u || !shear_v || !surface_u || !surface_v || !storm_u || !storm_v || !out) return fail(XP_E_ARG, "xp_critical_angle: null argument");
-    const size_t b = (size_t)n * esize(dtype);
-    const void *src[6] = {shear_u, shear_v, surface_u, surface_v, storm_u, storm_v}, *in[6];
-    void *od;
-    int rc;
-    for (int i = 0; i < 6; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
-    if ((rc = st.out(out, b, mem, &od))) return rc;
-    xp::launch_critical_angle(n, dtype == XP_F64, in, od, st.s);
-    return st.finish();
+    return per_point<xp::CriticalAngleOp>("xp_critical_angle", n, dtype, mem, {shear_u, shear_v, surface_u, surface_v, storm_u, storm_v}, 6,
+                                          {out}, true, stream);
 }
 
 int xp_corfidi_storm_motion(int64_t n, int32_t dtype, int32_t mem, const void *mean_u, const void *mean_v, const void *llj_u,
                             const void *llj_v, void *upwind_u, void *upwind_v, void *downwind_u, void *downwind_v,
                             void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_corfidi_storm_motion: bad n / dtype");
-    if (!mean_u || !mean_v || !llj_u || !llj_v) return fail(XP_E_ARG, "xp_corfidi_storm_motion: null argument");
-    const size_t b = (size_t)n * esize(dtype);
-    const void *src[4] = {mean_u, mean_v, llj_u, llj_v}, *in[4];
-    void *dst[4] = {upwind_u, upwind_v, downwind_u, downwind_v}, *od[4];
-    int rc;
-    for (int i = 0; i < 4; ++i) if ((rc = st.in(src[i], b, mem, &in[i])) || (rc = st.out(dst[i], b, mem, &od[i]))) return rc;
-    xp::launch_corfidi(n, dtype == XP_F64, in, od, st.s);
-    return st.finish();
+    return per_point<xp::CorfidiOp>("xp_corfidi_storm_motion", n, dtype, mem, {mean_u, mean_v, llj_u, llj_v}, 4,
+                                    {upwind_u, upwind_v, downwind_u, downwind_v}, false, stream);
 }
 
 int xp_significant_tornado_effective(int64_t n, int32_t dtype, int32_t mem, const void *mlcape, const void *mlcin,
                                      const void *lcl_height, const void *esrh, const void *ebwd, const void *base_height,
                                      void *out, void *stream) {
-    Entry st(stream);
-    if (st.rc) return st.rc;
-    if (n < 0 || (dtype != XP_F32 && dtype != XP_F64)) return fail(XP_E_ARG, "xp_significant_tornado_effective: bad n / dtype");
-    if (!mlcape || !mlcin || !lcl_height || !esrh || !ebwd || !out) return fail(XP_E_ARG, "xp_significant_tornado_effective: null argument");
-    const size_t b = (size_t)n * esize(dtype);
-    const void *src[6] = {mlcape, mlcin, lcl_height, esrh, ebwd, base_height}, *in[6];
-    void *od;
-    int rc;
-    for (int i = 0; i < 6; ++i) if ((rc = st.in(src[i], b, mem, &in[i]))) return rc;
-    if ((rc = st.out(out, b, mem, &od))) return rc;
-    xp::launch_stp_effective(n, dtype == XP_F64, in, od, st.s);
-    return st.finish();
+    return per_point<xp::StpEffectiveOp>("xp_significant_tornado_effective", n, dtype, mem,
+                                         {mlcape, mlcin, lcl_height, esrh, ebwd, base_height}, 5, {out}, true, stream);
 }
 
 int xp_interp_level(const xp_view *coords, const xp_view *x, const void *at, int32_t at_is_scalar, int32_t log_coords,

@@ -733,10 +733,7 @@ def wind_shear(surface_wind_u, surface_wind_v, wind_u, wind_v, height, shear_hei
 
 def significant_hail_parameter(mucape, mixing_ratio, lapse, temp_500, shear, flh):
     """pf.py:2261 (SPC SHIP) with the reference's validity windows (xp_significant_hail_parameter)."""
-    c = _Call(mucape, mixing_ratio, lapse, temp_500, shear, flh)
-    out = c.out(c.ins[0].shape)
-    c.run('xp_significant_hail_parameter', _flat(c.ins), c.xp_dtype, c.mem, *c.ins, out)
-    return out
+    return _per_point('xp_significant_hail_parameter', [mucape, mixing_ratio, lapse, temp_500, shear, flh], (), 1)[0]
 
 
 def bunkers_storm_motion(pressure, u, v, height):
@@ -814,18 +811,12 @@ def storm_relative_helicity_layers(height, u, v, bottom, top, storm_u=0.0, storm
 def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):
     """metpy.calc.significant_tornado per point (xp_significant_tornado): sbcape [J/kg], LCL height [m], 0-1 km SRH
     [m^2/s^2], 0-6 km bulk shear [m/s]."""
-    c = _Call(sbcape, lcl_height, storm_helicity_1km, shear_6km)
-    out = c.out(c.ins[0].shape)
-    c.run('xp_significant_tornado', _flat(c.ins), c.xp_dtype, c.mem, *c.ins, out)
-    return out
+    return _per_point('xp_significant_tornado', [sbcape, lcl_height, storm_helicity_1km, shear_6km], (), 1)[0]
 
 
 def supercell_composite(mucape, effective_storm_helicity, effective_shear):
     """metpy.calc.supercell_composite per point (xp_supercell_composite): mucape [J/kg], SRH [m^2/s^2], shear [m/s]."""
-    c = _Call(mucape, effective_storm_helicity, effective_shear)
-    out = c.out(c.ins[0].shape)
-    c.run('xp_supercell_composite', _flat(c.ins), c.xp_dtype, c.mem, *c.ins, out)
-    return out
+    return _per_point('xp_supercell_composite', [mucape, effective_storm_helicity, effective_shear], (), 1)[0]
 
 
 def _wind_layer(spec):
