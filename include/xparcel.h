@@ -319,6 +319,47 @@ int xp_effective_inflow_layer(const xp_view *pressure, const xp_view *temperatur
                               const xp_view *height, double cape_min, double cin_min, double search_depth,
                               const xp_opts *opts, xp_effective_layer_out *out, void *stream);
 
+/* CAPE and CIN over 1 ... 4 per-column pressure layers of ONE ascent (0-3 km CAPE, hail-growth-zone CAPE; the reference
+   and MetPy 1.4 have no counterpart).  Views, parcel and options as in xp_cape_cin; bottom and top are arrays of nlayer
+   pointers to ncol pressures each [hPa], in the views' dtype and mem; `bottom`, or any bottom[i], may be NULL.
+   The NODES are exactly the nodes xp_cape_cin scans for the chosen parcel: the levels from the parcel's first level, the
+   LCL node, and the prepended mixed-layer parcel where there is one; each with X = ln p and y = parcel - environment
+   (virtual temperatures under the correction switch).  y(x) is piecewise linear in ln p through the nodes, with its zeros
+   where the scan puts them; F+(x) and F-(x) are the positive and the negative area of y from the first node up to x (an
+   interval with a NaN end contributes nothing): at every node the running sums xp_cape_cin itself keeps.  With L the LFC
+   (or the LCL that replaces it), E the EL (or the lowest valid pressure when there is none) and cL = F+(ln L),
+   cE = F+(ln E), nL = F-(ln L) -- the terms of xp_cape_cin's own CAPE = Rd (cE - cL), CIN = Rd nL -- layer i with the
+   bounds pb > pt has
+       cape[i] = (E < L)  ? Rd * max(0, min(cE, F+(ln pt)) - max(cL, F+(ln pb))) : 0.0
+       cin[i]  = isnan(L) ? 0.0 : Rd * min(0, max(nL, F-(ln pt)) - F-(ln pb))
+   i.e. the positive area inside the layer between LFC and EL, and the negative area inside the layer below the LFC
+   (F+ never decreases and F- never increases with height, so the min / max form is exact).
+   Bottom bound: a NULL array, a NaN pb, or a pb above the first node's pressure means "from the first node" (F = 0).
+   Top bound: a pt below the last valid node's pressure means "to the top" (F = the final sums): bottom NULL and a tiny pt
+   give total_cape / total_cin bit for bit.  A NaN pt, or pt >= pb with both non-NaN, gives NaN for that layer and
+   XP_ST_NO_LAYER for the column; the other layers are unaffected.  A NaN parcel or LCL gives 0.0 for every (valid) layer,
+   as xp_cape_cin gives the column.  A bound inside an interval: F there is the sum below plus the area of the part of
+   the interval up to the bound, y at the bound linear in ln p between the two nodes -- one trapezoid, or the lower
+   triangle plus part of the upper one when the bound lies above the interval's zero; ln of a bound is the library log.
+   F is continuous, so on which side of a node a bound within an ulp of it falls does not matter (nothing bit-exact is
+   promised there).
+   total_cape, total_cin, lfc_pressure, el_pressure, lcl_pressure and the other status bits are what xp_cape_cin writes
+   for the same arguments.  opts: pos_cape_neg_cin must be set (cin[i] <= 0 by construction, so post_zero_cin changes
+   nothing); moist_mode XP_MOIST_EXACT or XP_MOIST_TABLE (XP_MOIST_FAMILY is treated as exact); humidity must be
+   XP_HUM_DEWPOINT.  nlayer outside 1 ... 4, a NULL top or top[i], mismatched views, XP_HUM_SPECIFIC,
+   pos_cape_neg_cin == 0 and an unknown moist_mode return XP_E_ARG; a bad lcl_interp XP_E_INTERP.  Every output may be
+   NULL; the outputs share the views' dtype and mem. */
+typedef struct {
+    void *cape[4], *cin[4];               /* J/kg, ncol each, per layer (entries past nlayer unused) */
+    void *total_cape, *total_cin;         /* J/kg, ncol: the whole ascent, as xp_cape_cin */
+    void *lfc_pressure, *el_pressure, *lcl_pressure;   /* hPa, ncol */
+    int32_t *status;          /* xp_cape_cin's bits | XP_ST_NO_LAYER */
+    int32_t dtype, mem;
+} xp_cape_layers_out;
+int xp_cape_cin_layers(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint, const xp_parcel *parcel,
+                       const xp_opts *opts, int32_t nlayer, const void *const *bottom, const void *const *top,
+                       xp_cape_layers_out *out, void *stream);
+
 /* pf.py:1758-1811 linear_interp / pf.py:1813-1828 log_interp: value of `variable` at coordinate `at` (one value per
    column, or a single value for all when at_is_scalar) between the bracketing levels of `coords`; duplicates of a
    bracketing coordinate are averaged, no extrapolation (NaN).  log_coords != 0 interpolates in ln(coords), ln(at).

@@ -22,7 +22,7 @@ ST_TOP_NAN, ST_LCL_NOT_CONVERGED, ST_NAN_PRESSURE, ST_BAD_PRESSURE = 1, 2, 4, 8
 # every symbol include/xparcel.h declares
 SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_family_table', 'xp_set_family_table', 'xp_cape_cin', 'xp_cape_cin_multi', 'xp_lcl', 'xp_dry_lapse',
            'xp_moist_lapse', 'xp_parcel_profile', 'xp_lfc_el', 'xp_cape_cin_base', 'xp_select_parcel',
-           'xp_mixed_layer', 'xp_wet_bulb_temperature', 'xp_downdraft_cape', 'xp_effective_inflow_layer', 'xp_interp_level', 'xp_interp_levels',
+           'xp_mixed_layer', 'xp_wet_bulb_temperature', 'xp_downdraft_cape', 'xp_effective_inflow_layer', 'xp_cape_cin_layers', 'xp_interp_level', 'xp_interp_levels',
            'xp_dewpoint_from_specific_humidity',
            'xp_crossing_level', 'xp_mixing_ratio', 'xp_conv_properties', 'xp_insert_level', 'xp_find_intersections', 'xp_trapz',
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
@@ -137,6 +137,17 @@ class EffectiveLayerOut(C.Structure):
                 [('dtype', C.c_int32), ('mem', C.c_int32)])
 
 
+# xp_cape_cin_layers: per layer (up to CAPE_MAX_LAYERS) CAPE and CIN, and the whole ascent's scalars
+CAPE_MAX_LAYERS = 4
+CAPE_LAYERS_OUT = ('cape', 'cin')
+CAPE_LAYERS_TOTAL = ('total_cape', 'total_cin', 'lfc_pressure', 'el_pressure', 'lcl_pressure')
+
+
+class CapeLayersOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p * CAPE_MAX_LAYERS) for k in CAPE_LAYERS_OUT] + [(k, C.c_void_p) for k in CAPE_LAYERS_TOTAL] +
+                [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
+
+
 # xp_storm_relative_helicity_layers: per layer (up to SRH_MAX_DEPTHS) the helicity sums and the bulk wind difference
 SRH_LAYERS_OUT = SRH_OUT + ('shear_u', 'shear_v')
 
@@ -194,6 +205,7 @@ ARGTYPES = {
     'xp_wet_bulb_temperature': (_V, _V, _V, _i32, _ptr, _ptr),
     'xp_downdraft_cape': (_V, _V, _V, _f64, _f64, _i32, C.POINTER(DcapeOut), _ptr),
     'xp_effective_inflow_layer': (_V, _V, _V, _V, _f64, _f64, _f64, _O, C.POINTER(EffectiveLayerOut), _ptr),
+    'xp_cape_cin_layers': (_V, _V, _V, _P, _O, _i32, C.POINTER(_ptr), C.POINTER(_ptr), C.POINTER(CapeLayersOut), _ptr),
     'xp_interp_level': (_V, _V, _ptr, _i32, _i32, _ptr, _ptr),
     'xp_interp_levels': (_V, _i32, C.POINTER(_V), _i32, _ptr, _i32, C.POINTER(_ptr), _ptr),
     'xp_dewpoint_from_specific_humidity': (_V, _V, _V, _ptr, _ptr),
@@ -261,8 +273,12 @@ EFFECTIVE_FLAGS = ['-mllvm', '-disable-machine-licm']
 # with machine LICM their fp64 constants are carried through the level loop (14 VGPRs more in every instantiation: three
 # layers without the strongest wind 131 instead of 119, two with it 143 instead of 128 -- a wave per SIMD each).
 WIND_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The layer CAPE / CIN kernel (csrc/xp_cape_layers.hpp): the ascent of the effective-inflow kernel, and its flag for its reason
+# (104-111 VGPRs without a spill).
+CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
-         ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS)] + [
+         ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
+         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS)] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

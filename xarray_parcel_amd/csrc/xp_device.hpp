@@ -1084,6 +1084,19 @@ struct Scan {
         r.lfc_p = lfc_p; r.lfc_t = lfc_t; r.el_p = el_p; r.el_t = el_t; r.lfc_idx = lfc_idx; r.el_idx = el_idx;
         return r;
     }
+    // What finish() formed r.cape and r.cin from, read back beside its Result (the layer kernel, xp_cape_layers.hpp, clips
+    // the same sums to its layer bounds): L the LFC pressure -- the LCL's where it replaced the LFC (lfc_idx == -2) -- and E
+    // the EL pressure, or the lowest valid pressure where there is no EL; cL, nL / cE the running sums as they stood there.
+    struct Terms { double L, E, cL, cE, nL; };
+    XP_DEV Terms terms(const Result &r) const {
+        Terms t;
+        const bool replace = r.lfc_idx == -2, el_ok = !isnan_(r.el_p);
+        t.L = r.lfc_p;
+        t.cL = slot[(replace ? SL_CAPE_LCL : SL_CAPE_LFC) * SLOT_STRIDE]; t.nL = slot[(replace ? SL_CIN_LCL : SL_CIN_LFC) * SLOT_STRIDE];
+        t.E = el_ok ? r.el_p : slot[SL_MIN_P * SLOT_STRIDE];
+        t.cE = el_ok ? slot[SL_CAPE_EL * SLOT_STRIDE] : cape;
+        return t;
+    }
 };
 
 }  // namespace xp

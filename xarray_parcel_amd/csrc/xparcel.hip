@@ -18,6 +18,7 @@
 #include "xp_dcape.hpp"
 #include "xp_kinematics.hpp"
 #include "xp_effective.hpp"
+#include "xp_cape_layers.hpp"
 #include "xp_wind_layers.hpp"
 #include "xp_per_point.hpp"
 
@@ -1099,6 +1100,38 @@ int xp_effective_inflow_layer(const xp_view *p, const xp_view *t, const xp_view 
     a.pos_neg = opts.pos_cape_neg_cin; a.post_zero = opts.post_zero_cin;
     a.tb = ts.tb; a.es_tab = ts.es;
     xp::launch_effective_inflow(a, p->dtype == XP_F64, tm != 0, st.s);
+    return st.finish();
+}
+
+int xp_cape_cin_layers(const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel, const xp_opts *o,
+                       int32_t nlayer, const void *const *bottom, const void *const *top, xp_cape_layers_out *out, void *stream) {
+    const char *const entry = "xp_cape_cin_layers";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    const xp_opts opts = o ? *o : default_opts();
+    int rc;
+    xp::CapeLayersArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = check_cape(p, t, td, 1, parcel, opts)) || (rc = check_out(entry, out, p))) return rc;
+    if (opts.humidity != XP_HUM_DEWPOINT) return fail(XP_E_ARG, "%s: humidity must be XP_HUM_DEWPOINT", entry);
+    if (!opts.pos_cape_neg_cin) return fail(XP_E_ARG, "%s: layers are defined for pos_cape_neg_cin only", entry);
+    if (nlayer < 1 || nlayer > xp::CL_MAX_LAYERS) return fail(XP_E_ARG, "%s: nlayer must lie in 1 ... 4, got %d", entry, (int)nlayer);
+    if (!top) return fail(XP_E_ARG, "%s: top: null", entry);
+    for (int i = 0; i < nlayer; ++i)
+        if (!top[i]) return fail(XP_E_ARG, "%s: top[%d]: null", entry, i);
+    if ((rc = stage_cape(st, p, t, td, opts, &a.base)) || (rc = set_parcel(st, *parcel, p, &a.base))) return rc;
+    const size_t cb = rows_bytes(p, 1);
+    for (int i = 0; i < nlayer; ++i)
+        if ((rc = st.in(bottom ? bottom[i] : nullptr, cb, p->mem, &a.bottom[i])) || (rc = st.in(top[i], cb, p->mem, &a.top[i])) ||
+            (rc = st.out(out->cape[i], cb, out->mem, &a.cape[i])) || (rc = st.out(out->cin[i], cb, out->mem, &a.cin[i]))) return rc;
+    if ((rc = st.out(out->total_cape, cb, out->mem, &a.total_cape)) || (rc = st.out(out->total_cin, cb, out->mem, &a.total_cin)) ||
+        (rc = st.out(out->lfc_pressure, cb, out->mem, &a.lfc_p)) || (rc = st.out(out->el_pressure, cb, out->mem, &a.el_p)) ||
+        (rc = st.out(out->lcl_pressure, cb, out->mem, &a.lcl_p)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.pmode = parcel->mode == XP_PARCEL_SURFACE ? xp::PM_SURFACE : parcel->mode == XP_PARCEL_MOST_UNSTABLE ? xp::PM_MU
+            : parcel->mode == XP_PARCEL_MIXED_LAYER ? xp::PM_ML : xp::PM_EXPLICIT;
+    a.nlayer = nlayer;
+    xp::launch_cape_layers(a, p->dtype == XP_F64, a.base.table_mode != 0, st.s);
     return st.finish();
 }
 

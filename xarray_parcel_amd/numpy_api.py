@@ -416,6 +416,115 @@ def effective_inflow_layer(pressure, temperature, dewpoint, height=None, cape_mi
     return res
 
 
+_LAYER_BOUND_KEYS = ('', '_height', '_temperature')
+
+
+def _lowest_valid_height(pressure, height):
+    """The height of the lowest level of every column at which pressure and height are both non-NaN (NaN: no such level),
+    in the arrays' own memory space."""
+    if _is_torch(height):
+        valid = ~(torch.isnan(pressure) | torch.isnan(height))
+        z0 = torch.gather(height, 0, valid.to(torch.uint8).argmax(0, keepdim=True))[0]
+        return torch.where(valid.any(0), z0, torch.full_like(z0, float('nan')))
+    valid = ~(np.isnan(pressure) | np.isnan(height))
+    z0 = np.take_along_axis(height, valid.argmax(0)[None], 0)[0]
+    return np.where(valid.any(0), z0, np.nan).astype(height.dtype)
+
+
+def _layer_bound(c, spec, side, p, t, z, z0):
+    """One bound of a cape_cin_layers layer as a per-column pressure [hPa] in the call's space, or None (no bottom)."""
+    given = [k for k in _LAYER_BOUND_KEYS if spec.get(side + k) is not None]
+    assert len(given) <= 1, f'layers: give {side} at most once (pressure, height or temperature)'
+    if not given:
+        assert side == 'bottom', 'layers: every layer needs a top'
+        return None
+    value = spec[side + given[0]]
+    if given[0] == '':
+        return c.per_col(value)
+    assert z is not None, 'layers: a bound by height or temperature needs height'
+    if given[0] == '_height':
+        at = z0 + c.per_col(value).reshape(z0.shape)
+    else:
+        assert np.ndim(value) == 0 and not _is_torch(value), 'layers: a temperature bound is one value [K]'
+        at = crossing_level(z, t, float(value))
+    return c.per_col(interp_level(z, p, at))
+
+
+def cape_cin_layers(pressure, temperature, dewpoint, layers, height=None, parcel='surface', depth=None, parcel_values=None,
+                    moist=None, **cape_cin_options):
+    """CAPE and CIN over 1 ... 4 layers of ONE ascent per column (xp_cape_cin_layers): the positive area inside the layer
+    between LFC and EL, and the negative area inside the layer below the LFC, of the profile cape_cin_columns lifts for
+    the same parcel -- clipped out of its running sums, no profile arrays.  `layers`: a sequence of dicts that give each
+    bound at most once, as
+      'bottom' / 'top'                          a pressure [hPa], a scalar or one value per column;
+      'bottom_height' / 'top_height'            metres above the lowest level with a valid pressure and height; the pressure
+                                                is interp_level(height, pressure, z0 + h), linear in height (the rule of
+                                                wind_layers' layers by height);
+      'bottom_temperature' / 'top_temperature'  [K]: the height is crossing_level(height, temperature, value), the lowest
+                                                crossing (freezing_level_height's rule), turned into a pressure likewise.
+    No bottom: from the first node of the ascent.  Bounds by height or temperature need `height`; they are resolved with
+    the library's own entry points in the inputs' memory space.  parcel, depth, parcel_values, moist and the options as in
+    cape_cin_columns (pos_cape_neg_cin must stay True; 'family' runs as 'exact'; dewpoints only).
+    Returns a dict: 'cape', 'cin' [J/kg] of shape (nlayer,) + columns, 'bottom_pressure', 'top_pressure' (the resolved
+    bounds; NaN bottom = from the first node), and per column 'total_cape', 'total_cin', 'lfc_pressure', 'el_pressure',
+    'lcl_pressure', 'status' (cape_cin_columns' bits, and XP_ST_NO_LAYER where a layer has a NaN top or top >= bottom: that
+    layer is NaN)."""
+    assert 'humidity' not in cape_cin_options, 'cape_cin_layers takes dewpoints'
+    layers = list(layers)
+    n = len(layers)
+    assert 1 <= n <= L.CAPE_MAX_LAYERS, 'layers: one to four layers'
+    assert all(set(l) <= {s + k for s in ('bottom', 'top') for k in _LAYER_BOUND_KEYS} for l in layers), 'layers: unknown key'
+    bound_arrays = [v for l in layers for v in l.values() if _is_torch(v)]
+    pv = list(parcel_values) if parcel == 'explicit' else []
+    c = _Call(*((pressure, temperature, dewpoint) + (() if height is None else (height,))), *[x for x in pv + bound_arrays if _is_torch(x)])
+    p, t, td = c.ins[:3]
+    z = None if height is None else c.ins[3]
+    assert p.shape == t.shape == td.shape and (z is None or z.shape == p.shape), 'pressure, temperature, dewpoint, height must share a shape'
+    o = _opts(moist=moist or _DEFAULT['moist'], **cape_cin_options)
+    if depth is None:
+        depth = 300.0 if parcel == 'most_unstable' else 100.0                # pf.py:1558, 1652
+    pc = L.Parcel(L.PARCEL[parcel], 0, float(depth), None, None, None)
+    if parcel == 'explicit':
+        pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in pv)
+    by_height = any(l.get(s + '_height') is not None for l in layers for s in ('bottom', 'top'))
+    z0 = _lowest_valid_height(p, z) if by_height and z is not None else None
+    bottoms = [_layer_bound(c, l, 'bottom', p, t, z, z0) for l in layers]
+    tops = [_layer_bound(c, l, 'top', p, t, z, z0) for l in layers]
+    res = {k: c.out((n,) + c.hshape) for k in L.CAPE_LAYERS_OUT}
+    res.update({k: c.out(c.hshape) for k in L.CAPE_LAYERS_TOTAL})
+    res['status'] = c.out(c.hshape, np.int32)
+    out = L.CapeLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in L.CAPE_LAYERS_OUT:
+        arr = getattr(out, k)
+        for i in range(n):
+            arr[i] = _ptr(res[k][i])
+    for k in L.CAPE_LAYERS_TOTAL:
+        setattr(out, k, _ptr(res[k]))
+    c.run('xp_cape_cin_layers', c.view(p), c.view(t), c.view(td), pc, o, n,
+          (C.c_void_p * n)(*[None if b is None else _ptr(b) for b in bottoms]), (C.c_void_p * n)(*map(_ptr, tops)), out)
+    nan = c.out(c.hshape)
+    nan[...] = float('nan')
+    stack = torch.stack if c.device is not None else np.stack
+    res['bottom_pressure'] = stack([nan if b is None else b.reshape(c.hshape) for b in bottoms])
+    res['top_pressure'] = stack([b.reshape(c.hshape) for b in tops])
+    return res
+
+
+def cape_3km(pressure, temperature, dewpoint, height, **kwargs):
+    """0-3 km CAPE [J/kg] per column: cape_cin_layers between the first node of the ascent and 3000 m above the lowest
+    valid level.  kwargs: parcel, depth, parcel_values, moist and the CAPE / CIN options."""
+    return cape_cin_layers(pressure, temperature, dewpoint, [{'top_height': 3000.0}], height=height, **kwargs)['cape'][0]
+
+
+def hail_growth_zone_cape(pressure, temperature, dewpoint, height, **kwargs):
+    """Hail-growth-zone CAPE [J/kg] per column: cape_cin_layers between the environment's lowest -10 degC and -30 degC
+    levels.  NaN (XP_ST_NO_LAYER) where the column has no -30 degC crossing or the two come in the wrong order; a column
+    without a -10 degC crossing (a surface already colder) has no bottom, i.e. the layer starts at the first node of the
+    ascent.  kwargs as cape_3km."""
+    return cape_cin_layers(pressure, temperature, dewpoint, [{'bottom_temperature': 263.15, 'top_temperature': 243.15}],
+                           height=height, **kwargs)['cape'][0]
+
+
 def interp_level(coords, variable, at, log=False):
     """pf.py:1758 linear_interp (log=False) / pf.py:1813 log_interp (log=True) of one variable."""
     c = _Call(coords, variable)
