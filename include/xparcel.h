@@ -574,6 +574,63 @@ int xp_significant_tornado_effective(int64_t n, int32_t dtype, int32_t mem, cons
                                      const void *lcl_height, const void *esrh, const void *ebwd, const void *base_height,
                                      void *out, void *stream);
 
+/* The buoyancy-dilution potential NCAPE of entraining CAPE (Peters, Chavas, Su, Morrison and Coffer 2023, J. Atmos. Sci.; the
+   reference and MetPy 1.4 have no counterpart) for every column: an integral over the environment alone, between the LFC and
+   the EL that xp_cape_cin wrote for the parcel of interest.  pressure [hPa], temperature, dewpoint [K] and height [m] on one
+   vertical; lfc_pressure (L) and el_pressure (E) [hPa]: ncol values each, in the views' dtype and mem.  All arithmetic is in
+   double, in the order written here, without contraction.
+   A level is valid when p, T, Td and z are all non-NaN; the others are dropped.  z0, p0: the lowest valid level; p_top: the
+   pressure of the highest.  With g = 9.80665 and the library's cp, Lv, at every valid level k:
+       w = w_s(p, Td), q = w / (1 + w);   ws = w_s(p, T), qs = ws / (1 + ws)          (Bolton's e_s, as everywhere)
+       h = (cp T + Lv q) + g z,   hs = (cp T + Lv qs) + g z                            moist static energy, and saturated
+       I_0 = 0, I_k = I_(k-1) + (0.5 (h_k + h_(k-1))) (z_k - z_(k-1))                  trapz(h, z) from z0
+       hbar_0 = h_0, hbar_k = I_k / (z_k - z0)                                         the mean of h below the level
+       b_k = -(g / (cp T_k)) (hbar_k - hs_k).
+   The bounds, in this order:
+     - L NaN (no LFC: CAPE is 0): ncape = 0.0, both heights NaN, no status bit -- whatever the column holds;
+     - L and E both non-NaN and E >= L: the outputs NaN, XP_ST_NO_LAYER;
+     - E NaN with L valid: the integral runs to the highest valid level;
+     - otherwise both are clamped into [p_top, p0]; a layer that is empty after clamping gives 0.0 (and equal heights);
+     - fewer than two valid levels: the outputs NaN, XP_ST_NO_LAYER.
+   A bound pb that lies between the valid level below (pp, zp, bp) and the valid level above (p, z, b), pp > pb > p, is the point
+       f = (ln pb - ln p) / (ln pp - ln p);   z_b = z + f (zp - z);   b_b = b + f (bp - b)
+   -- z linear in ln p, b linear in z; a bound equal to a level's pressure is that level.  Then
+       ncape = trapz(b, z) over z_L, the valid levels strictly between, and z_E     [J/kg],
+   which is continuous in the bounds: on which side of a level a bound within an ulp of it falls does not matter, and nothing
+   bit-exact is promised there.  lfc_height, el_height: z_L - z0, z_E - z0 [m above the lowest valid level: the height
+   convention of xp_storm_relative_helicity_layers].
+   Levels are read up to and including the first valid level at or beyond E (p <= E), and at least two of them; among the
+   valid levels read, a height not above the level below gives XP_ST_BAD_HEIGHT, a pressure not below it XP_ST_BAD_PRESSURE,
+   and the outputs are NaN.  Every output may be NULL; the outputs share the views' dtype and mem.  Strided device views are
+   read in place.  XP_E_ARG: a NULL or mismatched view, a NULL lfc_pressure or el_pressure, a NULL out or one whose dtype or
+   mem differs from the views'. */
+typedef struct {
+    void *ncape;              /* J/kg, ncol */
+    void *lfc_height;         /* m above the lowest valid level */
+    void *el_height;          /* the same */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_HEIGHT | XP_ST_BAD_PRESSURE */
+    int32_t dtype, mem;
+} xp_ncape_out;
+int xp_ncape(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint, const xp_view *height,
+             const void *lfc_pressure, const void *el_pressure, xp_ncape_out *out, void *stream);
+
+/* Entraining CAPE per point: the dimensional form of Peters et al.'s (2023) analytic E_A.  cape, ncape [J/kg], el_height [m
+   above the lowest valid level: xp_ncape's], sr_u, sr_v [m/s]: the storm-relative 0-1 km mean wind.  A NaN in any input, or
+   el_height <= 0, gives NaN in every output.  Otherwise, in double and in this order, without contraction:
+       C = k^2 a^2 pi^2 Lmix / (4 Pr s^2) = 82.87727046436741    (k = 0.42, a = 0.8, Lmix = 120 m, Pr = 1/3, s = 1.1)
+       psi = C / el_height
+       cape <= 0: ecape = ecape_a = 0
+       V = max(hypot(sr_u, sr_v), 1e-3);  K = 0.5 (V V);  e = psi / (V V)
+       B = (1 + psi) + (2 e) ncape;  x = (8 e) (cape - psi ncape);  r = B B + x
+       r < 0: ecape = ecape_a = 0                                 (entrainment leaves no updraft)
+       s = sqrt(r);  num = B >= 0 ? (B + s == 0 ? 0 : x / (B + s)) : s - B        (no cancellation)
+       ecape_a = max(0, K + num / (4 e));  ecape = max(0, ecape_a - K)
+   ecape_a includes the inflow's kinetic energy K, ecape does not.  The floor on V is a definition: the expression is
+   continuous there and tends to max(0, -ncape) as V -> 0.  n elements of dtype in mem each; no input may be NULL, every output
+   may. */
+int xp_ecape(int64_t n, int32_t dtype, int32_t mem, const void *cape, const void *ncape, const void *el_height,
+             const void *sr_u, const void *sr_v, void *ecape, void *ecape_a, void *psi, void *stream);
+
 /* ---- Array primitives of the reference's implementation -------------------------------------------------------------
    The CAPE / CIN kernels stream a column once and never build the arrays these functions return, but the reference
    exposes them (and its tests call two of them), so a caller of the reference finds them here too.  One variable per

@@ -29,7 +29,7 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
            'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
            'xp_wind_layers', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
-           'xp_last_error')
+           'xp_ncape', 'xp_ecape', 'xp_last_error')
 
 
 class View(C.Structure):
@@ -172,6 +172,16 @@ class WindLayersOut(C.Structure):
                 [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
 
 
+# xp_ncape: its per-column outputs; xp_ecape: its per-point inputs and outputs
+NCAPE_OUT = ('ncape', 'lfc_height', 'el_height', 'status')
+ECAPE_IN = ('cape', 'ncape', 'el_height', 'sr_u', 'sr_v')
+ECAPE_OUT = ('ecape', 'ecape_a', 'psi')
+
+
+class NcapeOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in NCAPE_OUT] + [('dtype', C.c_int32), ('mem', C.c_int32)]
+
+
 class Tables(C.Structure):
     _fields_ = [('n_pressure', C.c_int64), ('n_temperature', C.c_int64), ('n_adiabat', C.c_int64),
                 ('p_max', C.c_double), ('p_step', C.c_double), ('t_min', C.c_double), ('t_step', C.c_double),
@@ -234,6 +244,8 @@ ARGTYPES = {
     'xp_critical_angle': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_corfidi_storm_motion': (_i64, _i32, _i32) + (_ptr,) * 9,
     'xp_significant_tornado_effective': (_i64, _i32, _i32) + (_ptr,) * 8,
+    'xp_ncape': (_V, _V, _V, _V, _ptr, _ptr, C.POINTER(NcapeOut), _ptr),
+    'xp_ecape': (_i64, _i32, _i32) + (_ptr,) * 9,
     'xp_last_error': (),
 }
 
@@ -278,7 +290,7 @@ WIND_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
-         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS)] + [
+         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', [])] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

@@ -24,6 +24,7 @@ constexpr double EPS = 0.6219569100577033;
 constexpr double KAPPA = 2.0 / 7.0;
 constexpr double CP_D = RD / KAPPA;
 constexpr double LV = 2.50084e6;
+constexpr double G = 9.80665;         // standard gravity [m/s^2] (metpy.constants.g)
 constexpr double VT_EPS = 0.608;      // hard-coded in pf.py:782
 constexpr double RK4_H_MAX = 0.1;     // exact-mode step bound in ln p (shared with the oracle)
 constexpr double LCL_SNAP = 1e-11;    // a level this close (relative) to p_lcl counts as lying on the LCL

@@ -1,11 +1,12 @@
 // xp_per_point.hpp -- the per-point products: ONE kernel, k_per_point, instantiated on the operation.  An operation names its
 // inputs and outputs (NIN <= 6, NOUT <= 4) and maps the values of one point, as doubles, through the product's value function,
-// which lives with the kernels it belongs to (xp_bundle.hpp, xp_kinematics.hpp, xp_wind_layers.hpp) and keeps MetPy's / the
+// which lives with the kernels it belongs to (xp_bundle.hpp, xp_kinematics.hpp, xp_wind_layers.hpp, xp_ecape.hpp) and keeps MetPy's / the
 // reference's operation order under fp contract(off).  have[i]: input i was given (an input an entry point lets be null).
 #pragma once
 #include "xp_bundle.hpp"
 #include "xp_kinematics.hpp"
 #include "xp_wind_layers.hpp"
+#include "xp_ecape.hpp"
 
 namespace xp {
 
@@ -62,6 +63,10 @@ struct StpEffectiveOp {                                  // xp_significant_torna
         y[0] = stp_effective_value(x[0], x[1], x[2], x[3], x[4]);
         if (have[5] && x[5] > 0.0) y[0] = 0.0;           // the inflow layer is not surface based
     }
+};
+struct EcapeOp {                                         // xp_ecape: cape, ncape, el_height, sr_u, sr_v -> ecape, ecape_a, psi
+    static constexpr int NIN = 5, NOUT = 3;
+    static XP_DEV void apply(const double *x, const bool *, double *y) { ecape_value(x[0], x[1], x[2], x[3], x[4], y); }
 };
 
 }  // namespace xp

@@ -20,6 +20,7 @@
 #include "xp_effective.hpp"
 #include "xp_cape_layers.hpp"
 #include "xp_wind_layers.hpp"
+#include "xp_ecape.hpp"
 #include "xp_per_point.hpp"
 
 static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_ST_LCL_NOT_CONVERGED &&
@@ -1262,6 +1263,39 @@ int xp_significant_tornado_effective(int64_t n, int32_t dtype, int32_t mem, cons
                                      void *out, void *stream) {
     return per_point<xp::StpEffectiveOp>("xp_significant_tornado_effective", n, dtype, mem,
                                          {mlcape, mlcin, lcl_height, esrh, ebwd, base_height}, 5, {out}, true, stream);
+}
+
+int xp_ncape(const xp_view *p, const xp_view *t, const xp_view *td, const xp_view *z, const void *lfc_pressure,
+             const void *el_pressure, xp_ncape_out *out, void *stream) {
+    const char *const entry = "xp_ncape";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}, {z, "height"}}))) return rc;
+    if (!lfc_pressure) return fail(XP_E_ARG, "%s: lfc_pressure: null", entry);
+    if (!el_pressure) return fail(XP_E_ARG, "%s: el_pressure: null", entry);
+    if ((rc = check_out(entry, out, p))) return rc;
+    const size_t cb = rows_bytes(p, 1);
+    xp::NcapeArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) || (rc = stage_view(st, td, &a.td)) ||
+        (rc = stage_view(st, z, &a.z)) || (rc = st.in(lfc_pressure, cb, p->mem, &a.lfc_p)) ||
+        (rc = st.in(el_pressure, cb, p->mem, &a.el_p)) || (rc = st.out(out->ncape, cb, out->mem, &a.ncape)) ||
+        (rc = st.out(out->lfc_height, cb, out->mem, &a.lfc_z)) || (rc = st.out(out->el_height, cb, out->mem, &a.el_z)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = p->nlev; a.ncol = p->ncol;
+    xp::launch_ncape(a, p->dtype == XP_F64, st.s);
+    return st.finish();
+}
+
+int xp_ecape(int64_t n, int32_t dtype, int32_t mem, const void *cape, const void *ncape, const void *el_height,
+             const void *sr_u, const void *sr_v, void *ecape, void *ecape_a, void *psi, void *stream) {
+    const void *const in[5] = {cape, ncape, el_height, sr_u, sr_v};
+    const char *const name[5] = {"cape", "ncape", "el_height", "sr_u", "sr_v"};
+    for (int i = 0; i < 5 && g.init; ++i)                // (not initialised: per_point's XP_E_NOT_INIT comes first)
+        if (!in[i]) return fail(XP_E_ARG, "xp_ecape: %s: null", name[i]);
+    return per_point<xp::EcapeOp>("xp_ecape", n, dtype, mem, {cape, ncape, el_height, sr_u, sr_v}, 5, {ecape, ecape_a, psi}, false,
+                                  stream);
 }
 
 int xp_interp_level(const xp_view *coords, const xp_view *x, const void *at, int32_t at_is_scalar, int32_t log_coords,

@@ -1055,6 +1055,76 @@ def significant_tornado_effective(mlcape, mlcin, lcl_height, esrh, ebwd, base_he
     return _per_point('xp_significant_tornado_effective', ins, (), 1, extra=(None,) if base_height is None else ())[0]
 
 
+def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure):
+    """The buoyancy-dilution potential NCAPE of entraining CAPE (Peters et al. 2023) for every column (xp_ncape): the integral
+    over height, between the LFC and the EL, of -(g / (cp T)) (hbar - hs) of the ENVIRONMENT -- hbar the mean moist static
+    energy from the lowest valid level up to the height in question, hs the saturated moist static energy there.  pressure
+    [hPa], temperature, dewpoint [K], height [m] on one vertical, (nlev, ...); lfc_pressure, el_pressure [hPa]: one value per
+    column, what cape_cin_columns returns for the parcel of interest (NaN LFC: ncape 0; NaN EL: up to the highest valid
+    level).  Returns a dict of per-column 'ncape' [J/kg], 'lfc_height', 'el_height' [m above the lowest valid level] and
+    'status' (XP_ST_NO_LAYER: EL not above the LFC or fewer than two valid levels; ST_BAD_HEIGHT / ST_BAD_PRESSURE: levels out
+    of order; everything NaN)."""
+    c = _Call(pressure, temperature, dewpoint, height, *[x for x in (lfc_pressure, el_pressure) if _is_torch(x)])
+    assert all(a.shape == c.ins[0].shape for a in c.ins[:4]), 'pressure, temperature, dewpoint, height must share a shape'
+    res = {k: c.out(c.hshape, np.int32 if k == 'status' else None) for k in L.NCAPE_OUT}
+    out = L.NcapeOut(dtype=c.xp_dtype, mem=c.mem)
+    for k, a in res.items():
+        setattr(out, k, _ptr(a))
+    c.run('xp_ncape', *map(c.view, c.ins[:4]), c.per_col(lfc_pressure), c.per_col(el_pressure), out)
+    return res
+
+
+def ecape_from_ncape(cape, ncape, el_height, sr_u, sr_v):
+    """Entraining CAPE per point (xp_ecape; include/xparcel.h has the formula): cape, ncape [J/kg], el_height [m above the
+    lowest valid level: ncape()'s] and the storm-relative 0-1 km mean wind sr_u, sr_v [m/s], all of one shape.  Returns a dict
+    of 'ecape' [J/kg], 'ecape_a' (ecape plus the inflow's kinetic energy) and 'psi' (the entrainment parameter, 1);
+    NaN where an input is NaN or el_height <= 0."""
+    return dict(zip(L.ECAPE_OUT, _per_point('xp_ecape', [cape, ncape, el_height, sr_u, sr_v], (), 3)))
+
+
+def _in_space_of(x, ref):
+    """A per-column argument (scalar, array or tensor) in the memory space and dtype of the per-column result `ref`."""
+    if _is_torch(ref):
+        x = x if _is_torch(x) else torch.as_tensor(np.asarray(x))
+        return x.to(ref.device, ref.dtype)
+    return np.asarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=ref.dtype)
+
+
+def ecape(pressure, temperature, dewpoint, height, u, v, parcel='most_unstable', depth=None, storm='right', storm_u=None,
+          storm_v=None, moist=None, **cape_cin_options):
+    """Entraining CAPE of every column from the sounding grid, end to end on the device (NumPy arrays are staged per call;
+    CUDA tensors stay where they are): pressure [hPa], temperature, dewpoint [K], height [m], u, v [m/s] on one vertical,
+    (nlev, ...).  The chain:
+      1. cape_cin_columns for `parcel` ('surface', 'most_unstable', 'mixed_layer'; depth, moist and cape_cin_options as
+         there): cape, cin, lfc_pressure, el_pressure;
+      2. ncape between that LFC and EL;
+      3. the storm motion: bunkers_storm_motion's `storm` = 'right', 'left' or 'mean' -- unless storm_u and storm_v (scalars
+         or one value per column) are given;
+      4. the 0-1 km inflow: wind_layers over 0 ... 1000 m above the lowest valid level -- its PRESSURE-WEIGHTED mean
+         (metpy.calc.mean_pressure_weighted), not a plain average of the levels;
+      5. sr_u, sr_v = that mean minus the storm motion;
+      6. ecape_from_ncape.
+    Returns a dict of per-column 'ecape', 'ecape_a', 'psi', 'ncape', 'cape', 'cin', 'lfc_height', 'el_height', 'sr_u', 'sr_v'
+    and 'status': the OR of the status words of the calls above.  A column without an LFC has cape 0, ncape 0 and no EL
+    height, hence NaN ecape, ecape_a and psi."""
+    assert storm in ('right', 'left', 'mean'), "storm must be 'right', 'left' or 'mean'"
+    assert (storm_u is None) == (storm_v is None), 'storm_u, storm_v: give both or neither'
+    cc = cape_cin_columns(pressure, temperature, dewpoint, parcel=parcel, depth=depth, moist=moist,
+                          want=('cape', 'cin', 'lfc_pressure', 'el_pressure', 'status'), **cape_cin_options)
+    nc = ncape(pressure, temperature, dewpoint, height, cc['lfc_pressure'], cc['el_pressure'])
+    status = cc['status'] | nc['status']
+    if storm_u is None:
+        bm = bunkers_storm_motion(pressure, u, v, height)
+        storm_u, storm_v, status = bm[storm + '_u'], bm[storm + '_v'], status | bm['status']
+    wl = wind_layers(pressure, u, v, height, [{'bottom_height': 0.0, 'top_height': 1000.0}], want=('mean_u', 'mean_v'))
+    mean_u, mean_v = wl['mean_u'][0], wl['mean_v'][0]
+    sr_u, sr_v = mean_u - _in_space_of(storm_u, mean_u), mean_v - _in_space_of(storm_v, mean_v)
+    res = ecape_from_ncape(cc['cape'], nc['ncape'], nc['el_height'], sr_u, sr_v)
+    res.update(ncape=nc['ncape'], cape=cc['cape'], cin=cc['cin'], lfc_height=nc['lfc_height'], el_height=nc['el_height'],
+               sr_u=sr_u, sr_v=sr_v, status=status | wl['status'])
+    return res
+
+
 def conv_properties(dat, ignore_nans=False, moist=None):
     """pf.py:1951: the reference's convective-property bundle for a grid, ONE library call (xp_conv_properties): the
     q -> dewpoint step, the NaN mask, the fixed-level interpolations and the freezing / melting levels are one pass over
