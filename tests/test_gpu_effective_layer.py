@@ -185,7 +185,8 @@ def test_candidates_are_bit_identical_to_cape_cin(dtype):
 # -- 3. thresholds, options, input kinds, NULL outputs, argument errors ---------------------------------------------------------
 @pytest.mark.parametrize('kw', [dict(cape_min=500.0, cin_min=-50.0), dict(cape_min=0.5, cin_min=-1000.0, search_depth=150.0),
                                 dict(search_depth=1.0), dict(search_depth=1e4), dict(virtual_temperature_correction=False),
-                                dict(lcl_interp='linear'), dict(pos_cape_neg_cin=False), dict(post_zero_cin=True)])
+                                dict(lcl_interp='linear'), dict(pos_cape_neg_cin=False), dict(post_zero_cin=True),
+                                dict(pos_cape_neg_cin=False, post_zero_cin=True)])
 def test_thresholds_and_options(kw):
     p, t, td, z = inflow_inputs(40, 1000, seed=17, dtype=np.float64)
     got = xa.effective_inflow_layer(p, t, td, height=z, want_candidates=True, **kw)

@@ -40,7 +40,8 @@ def test_kat_through_c_abi(name):
 
 
 MODES = [dict(), dict(virtual_temperature_correction=False, lcl_interp='linear'), dict(pos_cape_neg_cin=False),
-         dict(post_zero_cin=True, lcl_interp='linear', virtual_temperature_correction=True)]
+         dict(post_zero_cin=True, lcl_interp='linear', virtual_temperature_correction=True),
+         dict(pos_cape_neg_cin=False, post_zero_cin=True)]              # the one combination in which post_zero_cin changes a result
 FKEYS = ('cape', 'cin', 'lcl_pressure', 'lcl_temperature', 'lcl_virtual_temperature', 'lfc_pressure',
          'lfc_temperature', 'el_pressure', 'el_temperature')
 IKEYS = ('lfc_index', 'el_index', 'status', 'parcel_index')
