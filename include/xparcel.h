@@ -551,6 +551,57 @@ typedef struct {
 int xp_wind_layers(const xp_view *pressure, const xp_view *u, const xp_view *v, const xp_view *height, int32_t nlayer,
                    const xp_wind_layer *layers, xp_wind_layers_out *out, void *stream);
 
+/* Temperature and humidity over 1 ... 4 caller-chosen layers in one upward pass: metpy.calc.precipitable_water, the layer means
+   of mixing ratio and relative humidity, thickness and lapse rate between the bounds, and the layer's extremes of equivalent
+   potential temperature.  pressure [hPa] and the nullable temperature, dewpoint [K] and height [m] on one vertical, as
+   (nlev, ncol) views of one shape, dtype and mem.  A level is valid when every SUPPLIED view is non-NaN there; the others
+   are dropped.  p0, z0: the lowest valid level.  A supplied height takes part in the ordering check.  All arithmetic is fp64,
+   without contraction.
+   At every valid level, once, shared by the layers: e = e_s(Td), es = e_s(T) (Bolton's formula, as everywhere in the
+   library), w = eps e / (p - e), rh = e / es, th = theta_e(p, T, Td) (Bolton's eq. 39, metpy.calc.equivalent_potential_
+   temperature).
+   The layer kinds and the points are those of xp_wind_layers: XP_LAYER_PRESSURE, XP_LAYER_PRESSURE_DEPTH, XP_LAYER_HEIGHT give
+   pb and pt as there; the points are the valid levels with pt <= p <= pb (close counting as inside) plus pb and pt themselves
+   where no selected level is close to them, in order of decreasing pressure.  At an added bound point T, Td and z are each
+   linear in ln p between the levels on either side, and e, es, w, rh, th are evaluated FROM THE INTERPOLATED T, Td -- what
+   MetPy's precipitable_water does with get_layer on the dewpoint.  Two extensions:
+     open top            a NaN scalar top with XP_LAYER_PRESSURE: to the highest valid level (precipitable_water's default).
+                         The whole column is read and its last valid level closes the layer: pt is that level's pressure;
+     per-column bounds   bottom_columns / top_columns (each nullable): nlayer pointers, each NULL or ncol values [hPa] in the
+                         views' dtype and mem.  A non-NULL entry needs XP_LAYER_PRESSURE and replaces that layer's scalar.  A NaN
+                         element of a bottom array is p0; a NaN element of a top array gives NaN for that layer and
+                         XP_ST_NO_LAYER (xp_cape_cin_layers' rules).  A column whose layer is empty (pt >= pb, or pb > p0) is
+                         finished with that layer at its first level, as with scalar bounds.
+   With the points P, T, Td, z (first ... last), S = trapz(w, P) (negative), R = trapz(rh, P), D = P_last - P_first, per layer,
+   ncol values each:
+     precipitable_water [mm]          (-S) * (1e5 / (g rho_l)): hPa -> Pa, m -> mm, g = 9.80665, rho_l = 999.97495 kg m^-3
+                                      (MetPy 1.4's metpy.constants.rho_l; part of this definition);
+     mean_mixing_ratio [kg/kg]        S / D;
+     mean_relative_humidity [0 ... 1] R / D;
+     thickness [m]                    z_last - z_first;
+     lapse_rate [K/km]                -(T_last - T_first) / thickness * 1000: positive where it cools upward;
+     theta_e_min, theta_e_min_pressure   the smallest th over the layer's points and its P, the first of equals winning;
+     theta_e_max, theta_e_max_pressure   the largest, likewise.
+   The extremes are over the POINTS, not over the continuous profile between them (the convention of xp_downdraft_cape's
+   source-level search).  A layer of one point has D = 0: its means are 0/0.
+   A layer with pt >= pb, with pb > p0, with pt below the smallest valid pressure or, by height, with a bound above the highest
+   valid height gets NaN and the column XP_ST_NO_LAYER; XP_ST_BAD_HEIGHT / XP_ST_BAD_PRESSURE and the levels read as in
+   xp_wind_layers.  XP_E_ARG, outputs untouched: everything xp_wind_layers rejects except the NaN top of an
+   XP_LAYER_PRESSURE layer (a scalar that a per-column array replaces is not looked at); a NULL pressure; a per-column array
+   on a layer of another kind; a wanted output whose input view is NULL -- temperature is needed by mean_relative_humidity,
+   lapse_rate and theta_e_*, dewpoint by everything except thickness and lapse_rate, height by thickness, lapse_rate and
+   layers by height.  Every output may be NULL; strided device views are read in place. */
+typedef struct {
+    void *precipitable_water[4], *mean_mixing_ratio[4], *mean_relative_humidity[4];   /* mm, kg/kg, 0 ... 1; ncol each, per layer */
+    void *thickness[4], *lapse_rate[4];                                               /* m, K/km */
+    void *theta_e_min[4], *theta_e_min_pressure[4], *theta_e_max[4], *theta_e_max_pressure[4];   /* K, hPa, K, hPa */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_HEIGHT | XP_ST_BAD_PRESSURE */
+    int32_t dtype, mem;
+} xp_thermo_layers_out;
+int xp_thermo_layers(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint, const xp_view *height,
+                     int32_t nlayer, const xp_wind_layer *layers, const void *const *bottom_columns,
+                     const void *const *top_columns, xp_thermo_layers_out *out, void *stream);
+
 /* metpy.calc.critical_angle per point [degrees]: the angle between a = (shear_u, shear_v), the 0-500 m ln p bulk shear, and
    b = (storm_u - surface_u, storm_v - surface_v), evaluated as atan2(|a x b|, a . b) -- mathematically MetPy's
    arccos(a . b / (|a| |b|)), but well conditioned near 0 and 180 degrees, where that form can leave [-1, 1] by rounding.

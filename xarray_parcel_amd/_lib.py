@@ -28,7 +28,7 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
            'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
-           'xp_wind_layers', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
+           'xp_wind_layers', 'xp_thermo_layers', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
            'xp_ncape', 'xp_ecape', 'xp_last_error')
 
 
@@ -172,6 +172,23 @@ class WindLayersOut(C.Structure):
                 [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
 
 
+# xp_thermo_layers: xp_wind_layers' layers (a NaN top by pressure: to the highest valid level) and, per layer, the outputs
+THERMO_MAX_LAYERS = 4
+THERMO_LAYERS_OUT = ('precipitable_water', 'mean_mixing_ratio', 'mean_relative_humidity', 'thickness', 'lapse_rate',
+                     'theta_e_min', 'theta_e_min_pressure', 'theta_e_max', 'theta_e_max_pressure')
+# the input views (temperature, dewpoint, height) each output reads besides pressure
+THERMO_LAYERS_NEEDS = {'precipitable_water': ('dewpoint',), 'mean_mixing_ratio': ('dewpoint',),
+                       'mean_relative_humidity': ('temperature', 'dewpoint'), 'thickness': ('height',),
+                       'lapse_rate': ('temperature', 'height'), 'theta_e_min': ('temperature', 'dewpoint'),
+                       'theta_e_min_pressure': ('temperature', 'dewpoint'), 'theta_e_max': ('temperature', 'dewpoint'),
+                       'theta_e_max_pressure': ('temperature', 'dewpoint')}
+
+
+class ThermoLayersOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p * THERMO_MAX_LAYERS) for k in THERMO_LAYERS_OUT] +
+                [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
+
+
 # xp_ncape: its per-column outputs; xp_ecape: its per-point inputs and outputs
 NCAPE_OUT = ('ncape', 'lfc_height', 'el_height', 'status')
 ECAPE_IN = ('cape', 'ncape', 'el_height', 'sr_u', 'sr_v')
@@ -241,6 +258,8 @@ ARGTYPES = {
     'xp_significant_tornado': (_i64, _i32, _i32) + (_ptr,) * 6,
     'xp_supercell_composite': (_i64, _i32, _i32) + (_ptr,) * 5,
     'xp_wind_layers': (_V, _V, _V, _V, _i32, C.POINTER(WindLayer), C.POINTER(WindLayersOut), _ptr),
+    'xp_thermo_layers': (_V, _V, _V, _V, _i32, C.POINTER(WindLayer), C.POINTER(_ptr), C.POINTER(_ptr),
+                         C.POINTER(ThermoLayersOut), _ptr),
     'xp_critical_angle': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_corfidi_storm_motion': (_i64, _i32, _i32) + (_ptr,) * 9,
     'xp_significant_tornado_effective': (_i64, _i32, _i32) + (_ptr,) * 8,
@@ -285,11 +304,14 @@ EFFECTIVE_FLAGS = ['-mllvm', '-disable-machine-licm']
 # with machine LICM their fp64 constants are carried through the level loop (14 VGPRs more in every instantiation: three
 # layers without the strongest wind 131 instead of 119, two with it 143 instead of 128 -- a wave per SIMD each).
 WIND_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The thermodynamic-layers kernel (csrc/xp_thermo_layers.hpp): the same walk, the same bound points, the same flag.
+THERMO_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 # The layer CAPE / CIN kernel (csrc/xp_cape_layers.hpp): the ascent of the effective-inflow kernel, and its flag for its reason
 # (104-111 VGPRs without a spill).
 CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
+         ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
          ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', [])] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [

@@ -20,6 +20,7 @@
 #include "xp_effective.hpp"
 #include "xp_cape_layers.hpp"
 #include "xp_wind_layers.hpp"
+#include "xp_thermo_layers.hpp"
 #include "xp_ecape.hpp"
 #include "xp_per_point.hpp"
 
@@ -1242,6 +1243,79 @@ int xp_wind_layers(const xp_view *p, const xp_view *u, const xp_view *v, const x
     if ((rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
     a.nlev = p->nlev; a.ncol = p->ncol; a.n = nlayer;
     xp::launch_wind_layers(a, p->dtype == XP_F64, want_max, st.s);
+    return st.finish();
+}
+
+int xp_thermo_layers(const xp_view *p, const xp_view *t, const xp_view *td, const xp_view *z, int32_t nlayer,
+                     const xp_wind_layer *layers, const void *const *bottom_columns, const void *const *top_columns,
+                     xp_thermo_layers_out *out, void *stream) {
+    const char *const entry = "xp_thermo_layers";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_view(p, "pressure"))) return rc;
+    if (t && (rc = check_views({{p, "pressure"}, {t, "temperature"}}))) return rc;
+    if (td && (rc = check_views({{p, "pressure"}, {td, "dewpoint"}}))) return rc;
+    if (z && (rc = check_views({{p, "pressure"}, {z, "height"}}))) return rc;
+    if ((rc = check_out(entry, out, p))) return rc;
+    if (nlayer < 1 || nlayer > xp::TL_MAX_LAYERS) return fail(XP_E_ARG, "%s: nlayer must lie in 1 ... 4, got %d", entry, (int)nlayer);
+    if (!layers) return fail(XP_E_ARG, "%s: layers: null", entry);
+    xp::ThermoLayersArgs a;
+    memset(&a, 0, sizeof(a));
+    bool colb = false, moist = false, theta = false;
+    for (int i = 0; i < nlayer; ++i) {
+        const xp_wind_layer &l = layers[i];
+        const void *const bc = bottom_columns ? bottom_columns[i] : nullptr, *const tc = top_columns ? top_columns[i] : nullptr;
+        double bottom = bc ? (double)NAN : l.bottom;
+        const double top = tc ? (double)NAN : l.top;
+        if (l.kind != XP_LAYER_PRESSURE && l.kind != XP_LAYER_PRESSURE_DEPTH && l.kind != XP_LAYER_HEIGHT)
+            return fail(XP_E_ARG, "%s: layers[%d]: unknown kind %d", entry, i, (int)l.kind);
+        if ((bc || tc) && l.kind != XP_LAYER_PRESSURE)
+            return fail(XP_E_ARG, "%s: layers[%d]: per-column bounds need kind XP_LAYER_PRESSURE", entry, i);
+        // a NaN top by pressure is the open one; a top that an array replaces is not looked at
+        if (!tc && !std::isfinite(top) && !(l.kind == XP_LAYER_PRESSURE && std::isnan(top)))
+            return fail(XP_E_ARG, "%s: layers[%d]: top must be finite (or, by pressure, NaN: to the highest valid level)", entry, i);
+        if (std::isinf(bottom)) return fail(XP_E_ARG, "%s: layers[%d]: bottom must be finite or NaN", entry, i);
+        if (l.kind == XP_LAYER_PRESSURE_DEPTH && !(top > 0.0)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive", entry, i);
+        if (l.kind == XP_LAYER_HEIGHT) {
+            if (!z) return fail(XP_E_ARG, "%s: layers[%d]: a layer by height needs height", entry, i);
+            if (std::isnan(bottom)) bottom = 0.0;
+            if (bottom < 0.0) return fail(XP_E_ARG, "%s: layers[%d]: bottom height must be >= 0", entry, i);
+            if (!(top > bottom)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive (top above bottom)", entry, i);
+        }
+        a.kind[i] = l.kind; a.bottom[i] = bottom; a.top[i] = top;
+        a.open[i] = l.kind == XP_LAYER_PRESSURE && !tc && std::isnan(top);
+        colb = colb || bc || tc;
+        // what each wanted output reads
+        const bool rh = out->mean_relative_humidity[i] != nullptr, lapse = out->lapse_rate[i] != nullptr;
+        const bool th = out->theta_e_min[i] || out->theta_e_min_pressure[i] || out->theta_e_max[i] || out->theta_e_max_pressure[i];
+        const bool sums = out->precipitable_water[i] || out->mean_mixing_ratio[i] || rh;
+        if (!t && (rh || lapse || th))
+            return fail(XP_E_ARG, "%s: layers[%d]: mean_relative_humidity, lapse_rate and theta_e_* need temperature", entry, i);
+        if (!td && (sums || th))
+            return fail(XP_E_ARG, "%s: layers[%d]: every output except thickness and lapse_rate needs dewpoint", entry, i);
+        if (!z && (out->thickness[i] || lapse)) return fail(XP_E_ARG, "%s: layers[%d]: thickness and lapse_rate need height", entry, i);
+        moist = moist || sums; theta = theta || th;
+        a.want_rh = a.want_rh || rh;
+    }
+    const size_t cb = rows_bytes(p, 1);
+    if ((rc = stage_view(st, p, &a.p)) || (t && (rc = stage_view(st, t, &a.t))) || (td && (rc = stage_view(st, td, &a.td))) ||
+        (z && (rc = stage_view(st, z, &a.z)))) return rc;
+    for (int i = 0; i < nlayer; ++i) {
+        if ((rc = st.in(bottom_columns ? bottom_columns[i] : nullptr, cb, p->mem, &a.bottom_col[i])) ||
+            (rc = st.in(top_columns ? top_columns[i] : nullptr, cb, p->mem, &a.top_col[i])) ||
+            (rc = st.out(out->precipitable_water[i], cb, out->mem, &a.pw[i])) ||
+            (rc = st.out(out->mean_mixing_ratio[i], cb, out->mem, &a.mean_w[i])) ||
+            (rc = st.out(out->mean_relative_humidity[i], cb, out->mem, &a.mean_rh[i])) ||
+            (rc = st.out(out->thickness[i], cb, out->mem, &a.thickness[i])) || (rc = st.out(out->lapse_rate[i], cb, out->mem, &a.lapse[i])) ||
+            (rc = st.out(out->theta_e_min[i], cb, out->mem, &a.th_min[i])) ||
+            (rc = st.out(out->theta_e_min_pressure[i], cb, out->mem, &a.th_min_p[i])) ||
+            (rc = st.out(out->theta_e_max[i], cb, out->mem, &a.th_max[i])) ||
+            (rc = st.out(out->theta_e_max_pressure[i], cb, out->mem, &a.th_max_p[i]))) return rc;
+    }
+    if ((rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = p->nlev; a.ncol = p->ncol; a.n = nlayer;
+    xp::launch_thermo_layers(a, p->dtype == XP_F64, moist, theta, colb, st.s);
     return st.finish();
 }
 

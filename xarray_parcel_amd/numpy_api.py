@@ -1055,6 +1055,117 @@ def significant_tornado_effective(mlcape, mlcin, lcl_height, esrh, ebwd, base_he
     return _per_point('xp_significant_tornado_effective', ins, (), 1, extra=(None,) if base_height is None else ())[0]
 
 
+def _is_per_column(x):
+    return _is_torch(x) or (x is not None and np.ndim(x) > 0)
+
+
+def _thermo_layer(spec):
+    """One layer of thermo_layers() as (kind, bottom, top, bottom_column, top_column): _wind_layer's layers, and for a layer
+    by pressure -- {'bottom': ..., 'top': ...} or ('pressure', bottom, top) -- top=None (to the highest valid level) and
+    bottom / top given per column (an array or a tensor, which replaces the scalar)."""
+    if isinstance(spec, dict) and 'top' in spec:
+        assert set(spec) <= {'bottom', 'top'}, 'layer: top= [hPa] goes with bottom= only, in %r' % (spec,)
+        bottom, top = spec.get('bottom'), spec['top']
+    elif not isinstance(spec, dict) and len(spec) == 3 and spec[0] == 'pressure':
+        bottom, top = spec[1:]
+    else:
+        return _wind_layer(spec) + (None, None)
+    bcol, tcol = (x if _is_per_column(x) else None for x in (bottom, top))
+    kind, b, t = _wind_layer(('pressure', None if bcol is not None else bottom, float('nan') if tcol is not None or top is None else top))
+    return kind, b, t, bcol, tcol
+
+
+def thermo_layers(pressure, temperature=None, dewpoint=None, height=None, layers=(), want=None):
+    """Temperature and humidity over up to four layers of every column in one pass (xp_thermo_layers): pressure [hPa] and,
+    as far as the wanted outputs read them, temperature, dewpoint [K] and height [m] on one vertical, (nlev, ...).  `layers`:
+    as in wind_layers -- {'bottom': 700, 'top': 500}, {'depth': 100}, {'bottom_height': 0, 'top_height': 3000} -- and, for a
+    layer by pressure, 'top': None (to the highest valid level) and 'bottom' / 'top' given per column (arrays or device
+    tensors of the horizontal shape; a NaN bottom: the lowest valid level; a NaN top: no layer).  Returns a dict with a
+    leading layer axis: 'precipitable_water' [mm] (metpy.calc.precipitable_water), 'mean_mixing_ratio' [kg/kg],
+    'mean_relative_humidity' [0 ... 1] (pressure-weighted layer means), 'thickness' [m], 'lapse_rate' [K/km, positive where
+    it cools upward], 'theta_e_min', 'theta_e_max' [K] with 'theta_e_min_pressure', 'theta_e_max_pressure' [hPa] (over the
+    layer's points) -- those that `want` names; by default every one the supplied inputs allow -- and the per-column 'status'
+    (XP_ST_NO_LAYER: some layer is empty or not spanned by the column, its values NaN; ST_BAD_HEIGHT / ST_BAD_PRESSURE: levels
+    out of order, everything NaN)."""
+    specs = [_thermo_layer(s) for s in layers]
+    n = len(specs)
+    assert 1 <= n <= L.THERMO_MAX_LAYERS, 'layers: one to four layers'
+    assert height is not None or all(s[0] != L.LAYER_HEIGHT for s in specs), 'a layer given by height needs height'
+    given = {'temperature': temperature, 'dewpoint': dewpoint, 'height': height}
+    if want is None:
+        keys = tuple(k for k in L.THERMO_LAYERS_OUT if all(given[v] is not None for v in L.THERMO_LAYERS_NEEDS[k]))
+    else:
+        keys = tuple(want)
+        assert set(keys) <= set(L.THERMO_LAYERS_OUT), 'want: unknown output'
+        for k in keys:
+            assert all(given[v] is not None for v in L.THERMO_LAYERS_NEEDS[k]), '%s needs %s' % (k, ' and '.join(L.THERMO_LAYERS_NEEDS[k]))
+    names = ['pressure'] + [v for v in ('temperature', 'dewpoint', 'height') if given[v] is not None]
+    bounds = [x for s in specs for x in s[3:] if _is_torch(x)]
+    c = _Call(pressure, *[given[v] for v in names[1:]], *bounds)
+    ins = dict(zip(names, c.ins))
+    assert all(a.shape == ins['pressure'].shape for a in ins.values()), 'pressure, temperature, dewpoint, height must share a shape'
+    res = {k: c.out((n,) + c.hshape) for k in keys}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = L.ThermoLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in keys:
+        arr = getattr(out, k)
+        for i in range(n):
+            arr[i] = _ptr(res[k][i:i + 1])
+    cols = [[None if s[j] is None else c.per_col(s[j]) for s in specs] for j in (3, 4)]
+    bcols, tcols = (None if all(x is None for x in col) else (C.c_void_p * n)(*[None if x is None else _ptr(x) for x in col])
+                    for col in cols)
+    views = [c.view(ins[v]) if v in ins else None for v in ('pressure', 'temperature', 'dewpoint', 'height')]
+    c.run('xp_thermo_layers', *views, n, (L.WindLayer * n)(*[L.WindLayer(s[0], 0, s[1], s[2]) for s in specs]), bcols, tcols, out)
+    return res
+
+
+def precipitable_water(pressure, dewpoint, bottom=None, top=None):
+    """metpy.calc.precipitable_water for every column [mm]: -1 / (g rho_l) times the integral of the mixing ratio w(p, Td) over
+    pressure from `bottom` [hPa; None: the lowest valid level] to `top` [hPa; None: the highest valid level], the bounds
+    interpolated in ln p where they lie between levels; bottom / top may be per-column arrays.  NaN where the column does not
+    span the layer."""
+    return thermo_layers(pressure, dewpoint=dewpoint, layers=[{'bottom': bottom, 'top': top}], want=('precipitable_water',))['precipitable_water'][0]
+
+
+def mean_relative_humidity(pressure, temperature, dewpoint, height=None, layer=('pressure', 700.0, 500.0)):
+    """The pressure-weighted mean relative humidity [0 ... 1] of one layer of every column: trapz(e_s(Td) / e_s(T), p) over
+    the layer's depth.  `layer`: one layer of thermo_layers (by height: give `height`); default 700-500 hPa."""
+    return thermo_layers(pressure, temperature, dewpoint, height, layers=[layer], want=('mean_relative_humidity',))['mean_relative_humidity'][0]
+
+
+def layer_lapse_rate(pressure, temperature, height, layer=('pressure', 700.0, 500.0)):
+    """(lapse_rate [K/km, positive where it cools upward], thickness [m]) between the bounds of one layer of every column,
+    temperature and height interpolated in ln p where a bound lies between levels.  `layer`: one layer of thermo_layers;
+    default 700-500 hPa."""
+    res = thermo_layers(pressure, temperature, None, height, layers=[layer], want=('lapse_rate', 'thickness'))
+    return res['lapse_rate'][0], res['thickness'][0]
+
+
+def hail_growth_zone_thickness(pressure, temperature, height):
+    """(thickness [m], lapse_rate [K/km]) of the hail growth zone of every column: the layer between the environment's lowest
+    -10 degC and -30 degC levels, resolved as hail_growth_zone_cape resolves them (crossing_level in height, turned into a
+    pressure by interp_level) in the inputs' memory space and passed on as per-column pressures.  NaN where the column has no
+    -30 degC crossing or the two come in the wrong order; from the lowest valid level where it has no -10 degC crossing."""
+    c = _Call(pressure, temperature, height)
+    p, t, z = c.ins
+    assert p.shape == t.shape == z.shape, 'pressure, temperature, height must share a shape'
+    spec = {'bottom_temperature': 263.15, 'top_temperature': 243.15}
+    bottom, top = (_layer_bound(c, spec, side, p, t, z, None).reshape(c.hshape or (1,)) for side in ('bottom', 'top'))
+    res = thermo_layers(p, t, None, z, layers=[{'bottom': bottom, 'top': top}], want=('thickness', 'lapse_rate'))
+    return res['thickness'][0], res['lapse_rate'][0]
+
+
+def theta_e_difference(pressure, temperature, dewpoint, height):
+    """The theta_e-difference index of every column [K] (Atkins and Wakimoto 1991, wet microbursts): the largest minus the
+    smallest equivalent potential temperature among the points of the lowest 3 km above the lowest valid level, and 0 where
+    the largest lies ABOVE the smallest (theta_e_max_pressure < theta_e_min_pressure).  NaN where the column does not reach
+    3 km."""
+    res = thermo_layers(pressure, temperature, dewpoint, height, layers=[('height', 0.0, 3000.0)],
+                        want=('theta_e_min', 'theta_e_min_pressure', 'theta_e_max', 'theta_e_max_pressure'))
+    diff = res['theta_e_max'][0] - res['theta_e_min'][0]
+    return _where(~(res['theta_e_max_pressure'][0] < res['theta_e_min_pressure'][0]), diff, 0.0)
+
+
 def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure):
     """The buoyancy-dilution potential NCAPE of entraining CAPE (Peters et al. 2023) for every column (xp_ncape): the integral
     over height, between the LFC and the EL, of -(g / (cp T)) (hbar - hs) of the ENVIRONMENT -- hbar the mean moist static
