@@ -484,3 +484,74 @@ def test_raw_abi_errors():
     # and the wind entry still rejects the NaN top that is the open one here
     wout = L.WindLayersOut(dtype=L.XP_F64, mem=L.XP_MEM_HOST, status=res['status'].ctypes.data)
     assert lib.xp_wind_layers(P, T, TD, Z, 1, _abi_layers([(R.PRESSURE, 850.0, NAN)]), wout, None) == L.XP_E_ARG
+
+
+# -- 8. the wind walk and this one choose the same layers -------------------------------------------------------------------
+# one by pressure, one by pressure depth from the lowest valid level, two by height
+SHARED_LAYERS = [('pressure', 850.0, 500.0), ('pressure_depth', None, 150.0), ('height', 0.0, 1000.0), ('height', 500.0, 3000.0)]
+
+
+def shared_inputs(ncol, dtype):
+    """Pressure and height (24, 257) for both entries, and u, v / T, Td with their missing values at the same (level, column):
+    ~6 % of them, the lowest level among them, so that the lowest valid level differs between columns.  In every column one
+    valid level is moved onto a bound of SHARED_LAYERS -- 850 and 500 hPa, p0 - 150 hPa, z0 + 500, 1000 and 3000 m -- or next
+    to it by OFFSETS (relative in pressure; a height offset of 8200 m x the relative one), bound and offset cycling with the
+    column; one column in 13 ends 2.5 km up, one in 17 600 m up, and one in 11 begins above 850 hPa.  ncol == 1: column 5."""
+    rng = np.random.default_rng(23)
+    nlev, n = 24, 257
+    miss = rng.random((nlev, n)) < 0.06
+    miss[:, ::16] = False
+    ok0 = np.argmin(miss, axis=0)                                # the lowest valid level
+    z = rng.integers(0, 1500, n) + np.vstack([np.zeros(n), np.cumsum(rng.uniform(100.0, 700.0, (nlev - 1, n)), axis=0)])
+    psfc = rng.uniform(985.0, 1030.0, n)
+    psfc[3::11] = rng.uniform(780.0, 840.0, psfc[3::11].size)    # (11, 13, 17: every bound and offset meets every kind of column)
+    cols = np.arange(n)
+    z0 = z[ok0, cols]
+    scale = rng.uniform(7600.0, 8800.0, n)
+    targets = [('p', 850.0), ('p', 500.0), ('dp', 150.0), ('z', 500.0), ('z', 1000.0), ('z', 3000.0)]
+    combos = [(t, o) for t in targets for o in OFFSETS]
+    for c in cols:
+        (kind, t), off = combos[c % len(combos)]
+        if kind == 'z':
+            want = z0[c] + t + off * 8200.0
+            k = int(np.argmin(np.where(miss[:, c], np.inf, np.abs(z[:, c] - want))))
+            if ok0[c] < k < nlev - 1 and z[k - 1, c] < want < z[k + 1, c]:
+                z[k, c] = want
+    p = psfc * np.exp(-(z - z[0]) / scale)
+    p0 = p[ok0, cols]
+    for c in cols:
+        (kind, t), off = combos[c % len(combos)]
+        if kind != 'z':
+            want = (t if kind == 'p' else p0[c] - t) * (1.0 + off)
+            k = int(np.argmin(np.where(miss[:, c], np.inf, np.abs(p[:, c] - want))))
+            if ok0[c] < k < nlev - 1 and p[k - 1, c] > want > p[k + 1, c]:
+                p[k, c] = want
+    u = rng.normal(5.0, 8.0, (nlev, n))
+    v = rng.normal(0.0, 8.0, (nlev, n))
+    t = 295.0 - 6.5e-3 * (z - z[0]) + rng.normal(0.0, 0.5, (nlev, n))
+    td = t - np.abs(rng.normal(0.0, 6.0, (nlev, n)))
+    u[miss] = np.nan
+    t[miss] = np.nan
+    p[(z - z0 > 2500.0) & (cols % 13 == 7)] = np.nan
+    p[(z - z0 > 600.0) & (cols % 17 == 9)] = np.nan
+    sel = slice(None) if ncol == n else slice(5, 5 + ncol)
+    return [np.ascontiguousarray(a[:, sel].astype(dtype)) for a in (p, z, u, v, t, td)]
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+@pytest.mark.parametrize('ncol', [257, 1])
+def test_wind_and_thermo_walks_choose_the_same_layers(ncol, dtype):
+    """k_wind_layers and k_thermo_layers take which points a layer has from one rule (csrc/xp_layer_gate.hpp): on the same
+    pressure, height and layers, with the missing levels in the same places, they find the same layers -- the same status in
+    every column, and a layer's mean wind is NaN exactly where its thickness is.  24 x 257: one full workgroup and a one-lane
+    tail.  Nothing is left out of the comparison."""
+    p, z, u, v, t, td = shared_inputs(ncol, dtype)
+    wind = xa.wind_layers(p, u, v, z, layers=SHARED_LAYERS, want=('mean_u',))
+    thermo = xa.thermo_layers(p, t, td, z, layers=SHARED_LAYERS, want=('thickness',))
+    assert wind['status'].shape == thermo['status'].shape == (ncol,)
+    assert np.array_equal(wind['status'], thermo['status'])
+    for i in range(len(SHARED_LAYERS)):
+        assert np.array_equal(np.isnan(wind['mean_u'][i]), np.isnan(thermo['thickness'][i])), i
+    if ncol > 1:                                                 # every layer is found in some columns and missing in others
+        nan_l = np.isnan(thermo['thickness'])
+        assert np.all(nan_l.sum(axis=1) >= 10) and np.all((~nan_l).sum(axis=1) >= 100), nan_l.sum(axis=1)

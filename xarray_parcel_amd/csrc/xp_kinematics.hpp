@@ -6,13 +6,13 @@
 //   stp_value, scp_value       metpy.calc.significant_tornado and supercell_composite per point, in MetPy's operation
 //                              order (their kernel is k_per_point, xp_per_point.hpp).
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/kinematics_restatement.py.  Each column kernel
-// makes one upward pass with level-major loads (coalesced when col_stride == 1): the layer points of MetPy's get_layer /
-// get_layer_heights are emitted in order as the walk passes them -- the levels themselves, and the added bound points
-// interpolated between the level below and the level above -- into running sums (trapezoids for the Bunkers layer means,
-// the helicity terms for SRH).  A lane is done at the first level beyond its highest top; the loop ends with a
-// wave-uniform ballot once every lane is done, so levels above 6 km (Bunkers) or the deepest SRH top are never read.
+// makes one upward pass with level-major loads (coalesced when col_stride == 1): the layer points of MetPy's get_layer
+// (Bunkers; which they are: xp_layer_gate.hpp) / get_layer_heights (SRH) are emitted in order as the walk passes them -- the
+// levels, and the added bound points interpolated between the level below and the level above -- into running sums (trapezoids
+// for the Bunkers layer means, the helicity terms for SRH).  A lane is done at the first level beyond its highest top; the loop
+// ends with a wave-uniform ballot once every lane is done, so levels above 6 km (Bunkers) or the deepest SRH top are never read.
 #pragma once
-#include "xp_kernels.hpp"
+#include "xp_layer_gate.hpp"
 
 namespace xp {
 
@@ -30,49 +30,34 @@ struct StormMotionArgs {
 // trapz(u, p) and trapz(v, p).  The sums are taken of the wind relative to the layer's first point, (u0, v0), and
 // M = u0 + trapz(u - u0, p) / (p_last - p_first): the same mean, exact for a constant wind (so that zero shear is exactly
 // zero and gives MetPy's NaN movers).
-struct LayerMean {
-    double su, sv, u0, v0, pf, pl, ul, vl;   // trapz sums, first point's wind, first and last point (pressure), last point's
-    bool started, top_close, fin;            // wind relative to the first
-    XP_DEV void init() { su = sv = 0.0; u0 = v0 = pf = pl = ul = vl = qnan(); started = top_close = fin = false; }
+struct LayerMean : LayerGate {               // (xp_layer_gate.hpp: which points are the layer's)
+    double su, sv, u0, v0, pf, ul, vl;       // trapz sums, first point's wind and pressure, last point's wind relative to the first
+    XP_DEV void init() { init_gate(); su = sv = 0.0; u0 = v0 = pf = ul = vl = qnan(); }
     XP_DEV void emit(double p, double u, double v) {
         if (started) { u -= u0; v -= v0; su += (p - pl) * (u + ul) * 0.5; sv += (p - pl) * (v + vl) * 0.5; }
         else { started = true; pf = p; u0 = u; v0 = v; u = v = 0.0; }
         pl = p; ul = u; vl = v;
     }
-    // an added bound point at pressure pe between the previous level (pp: higher pressure) and this one: u, v linear in ln p
-    XP_DEV void emit_between(double pe, double pp, double up, double vp, double p, double u, double v) {
-        const double xe = flog(pe), xp_ = flog(pp), x = flog(p);
-        const double f = (xe - x) / (xp_ - x);
-        emit(pe, u + f * (up - u), v + f * (vp - v));
-    }
-    // one valid level (p, u, v), the previous valid level (pp, up, vp) below it if has_prev; pb, pt: the bound pressures
-    // once known (NaN before), b_now / t_now: they became known at this level
-    XP_DEV void level(double p, double u, double v, double pp, double up, double vp, bool has_prev, double pb, bool b_now,
-                      double pt, bool t_now) {
-        if (fin || isnan_(pb)) return;                   // finished, or not begun
-        if (b_now) {
-            if (has_prev && isclose_(pp, pb)) emit(pp, up, vp);          // the level below, close to pb, is the first point
-            else if (!isclose_(p, pb)) emit_between(pb, pp, up, vp, p, u, v);   // pb itself (strictly between the levels)
+    // LayerGate::level's hooks at one valid level (p, u, v) with the previous valid level (pp, up, vp) below it
+    struct Step {
+        LayerMean &r;
+        double p, u, v, pp, up, vp;
+        XP_DEV void below() { r.emit(pp, up, vp); }
+        XP_DEV void bound(double pe) {                                  // u, v linear in ln p
+            const double xe = flog(pe), xp_ = flog(pp), x = flog(p);
+            const double f = (xe - x) / (xp_ - x);
+            r.emit(pe, u + f * (up - u), v + f * (vp - v));
         }
-        if (t_now) top_close = started && isclose_(pl, pt);             // the top appears: was the last point close to it?
-        if (isnan_(pt) || p >= pt || isclose_(p, pt)) {
-            emit(p, u, v);
-            top_close = top_close || (!isnan_(pt) && isclose_(p, pt));
-        } else {                                         // the first level beyond the top: pt closes the layer
-            // (pt appeared at this level: had it appeared earlier, that level was in the layer and close to it)
-            if (!top_close && t_now) emit_between(pt, pp, up, vp, p, u, v);
-            fin = true;
-        }
-    }
+        XP_DEV void here() { r.emit(p, u, v); }
+    };
     XP_DEV double mean_u() const { return u0 + su / (pl - pf); }
     XP_DEV double mean_v() const { return v0 + sv / (pl - pf); }
 };
 
-// np.interp(zc, z, p) at the first level (z, p) with z >= zc, the previous valid level (zp, pp) below it; NaN before that
+// np.interp(zc, z, p) once the walk reaches the first level (z, p) with z >= zc (now); NaN before that
 XP_DEV void bound_p(double &pc, bool &now, double zc, double zp, double pp, double z, double p, bool has_prev) {
-#pragma clang fp contract(off)
     now = isnan_(pc) && z >= zc;
-    if (now) pc = (z == zc || !has_prev) ? p : (p - pp) / (z - zp) * (zc - zp) + pp;
+    if (now) pc = interp_p(zc, zp, pp, z, p, has_prev);
 }
 
 template <typename T> __global__ __launch_bounds__(256)
@@ -101,9 +86,9 @@ void k_bunkers_storm_motion(StormMotionArgs a) {
         bound_p(p500, n500, z0 + 500.0, zp, pp, z, p, has_prev);
         bound_p(p5500, n5500, z0 + 5500.0, zp, pp, z, p, has_prev);
         bound_p(p6000, n6000, z0 + 6000.0, zp, pp, z, p, has_prev);
-        mean.level(p, u, v, pp, up, vp, has_prev, p0, !has_prev, p6000, n6000);
-        low.level(p, u, v, pp, up, vp, has_prev, p0, !has_prev, p500, n500);
-        high.level(p, u, v, pp, up, vp, has_prev, p5500, n5500, p6000, n6000);
+        mean.level(LayerMean::Step{mean, p, u, v, pp, up, vp}, p, pp, has_prev, {p0, !has_prev, p6000, n6000});
+        low.level(LayerMean::Step{low, p, u, v, pp, up, vp}, p, pp, has_prev, {p0, !has_prev, p500, n500});
+        high.level(LayerMean::Step{high, p, u, v, pp, up, vp}, p, pp, has_prev, {p5500, n5500, p6000, n6000});
         done = mean.fin && low.fin && high.fin;
         zp = z; pp = p; up = u; vp = v; has_prev = true;
     }

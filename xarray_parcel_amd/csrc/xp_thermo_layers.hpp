@@ -3,10 +3,10 @@
 // potential temperature, for up to four layers of every column, one thread per column.
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/thermo_layers_restatement.py.  k_thermo_layers is
 // the walk of k_wind_layers (xp_wind_layers.hpp) with other sums: one upward pass with level-major loads serves every layer
-// of the call whatever its kind; the points of MetPy's get_layer are emitted in order as the walk passes them -- the levels,
-// and the added bound points, T, Td and z interpolated in ln p between the level below and the level above -- into each
-// layer's running state.  A lane is done at the first level beyond its highest top; the loop ends with a wave-uniform ballot,
-// so levels above the deepest top are never read (an open top reads the whole column).
+// of the call whatever its kind; the points of MetPy's get_layer (which they are: xp_layer_gate.hpp) are emitted in order as
+// the walk passes them -- at an added bound point T, Td and z are interpolated in ln p -- into each layer's running state.  A
+// lane is done at the first level beyond its highest top; the loop ends with a wave-uniform ballot, so levels above the
+// deepest top are never read (an open top reads the whole column).
 // What a point carries besides p, T, Td, z -- e_s(Td), w, rh, theta_e -- is evaluated ONCE per level into the column's state
 // (Pt) and shared by the layers; at an added bound point it is evaluated from the interpolated T, Td.  A layer keeps only its
 // sums, its first and last point and its theta_e extremes: the previous point of a trapezoid is the previous valid level of
@@ -67,16 +67,15 @@ template <bool MOIST, bool THETA> XP_DEV ThermoPt thermo_between(double pe, cons
     return q;
 }
 
-// The running state of one layer: the trapezoids of w and rh over pressure, the first and the last point, the theta_e extremes.
-template <bool MOIST, bool THETA, bool COLB> struct ThermoLayer {
+// The running state of one layer: a LayerGate plus the trapezoids of w and rh over pressure, the first and the last point, the
+// theta_e extremes.
+template <bool MOIST, bool THETA, bool COLB> struct ThermoLayer : LayerGate {
     double sw, sr;                           // MOIST: trapz(w, P), trapz(rh, P) so far
-    double pf, tf, zf, pl, tl, zl;           // first point, last point
-    double pt;                               // the top pressure once the walk has reached it (NaN before)
+    double pf, tf, zf, tl, zl;               // first point, last point
     double tmin, pmin, tmax, pmax;           // THETA: the extremes so far and their pressures
     double pbc, ptc;                         // COLB: this column's bounds (the scalars where no array replaces them)
-    bool begun, started, top_close, fin;     // the bottom pressure is known; a point has been emitted; ...; finished
     XP_DEV void init() {
-        sw = sr = 0.0; pf = tf = zf = pl = tl = zl = pt = qnan(); begun = started = top_close = fin = false;
+        init_gate(); sw = sr = 0.0; pf = tf = zf = tl = zl = qnan();
         if constexpr (THETA) tmin = pmin = tmax = pmax = qnan();
     }
     // the point q; b: the point before it, if there is one (started)
@@ -97,27 +96,19 @@ template <bool MOIST, bool THETA, bool COLB> struct ThermoLayer {
         }
         pl = q.p; tl = q.t; zl = q.z;
     }
-    // One valid level `cur` with the previous valid level `prev` below it if has_prev.  pb, b_now: the bottom pressure, which
-    // became known at this level -- the first one at or beyond it; ptn, t_now: the same for the top (WindLayer::level).
-    XP_DEV void level(const ThermoPt &cur, const ThermoPt &prev, bool has_prev, double pb, bool b_now, double ptn, bool t_now,
-                      bool want_rh) {
-        if (fin) return;
-        ThermoPt b = prev;                               // the point before the next one emitted, once started
-        if (b_now) {
-            begun = true;
-            if (has_prev && isclose_(prev.p, pb)) emit(prev, prev);                       // the level below, close to pb
-            else if (!isclose_(cur.p, pb)) { b = thermo_between<MOIST, THETA>(pb, prev, cur, want_rh); emit(b, b); }   // pb itself
+    // LayerGate::level's hooks at one valid level `cur` with the previous valid level `prev` below it
+    struct Step {
+        ThermoLayer &r;
+        const ThermoPt &cur, &prev;
+        bool want_rh;
+        ThermoPt b;                          // the point before the next one emitted, once started: prev, or this step's bound point
+        XP_DEV void below() { r.emit(prev, prev); }
+        XP_DEV void bound(double pe) {
+            const ThermoPt q = thermo_between<MOIST, THETA>(pe, prev, cur, want_rh);
+            r.emit(q, b); b = q;
         }
-        if (!begun) return;
-        if (t_now) { pt = ptn; top_close = started && isclose_(pl, pt); }                 // was the last point close to the top?
-        if (isnan_(pt) || cur.p >= pt || isclose_(cur.p, pt)) {
-            emit(cur, b);
-            top_close = top_close || (!isnan_(pt) && isclose_(cur.p, pt));
-        } else {                                         // the first level beyond the top: pt closes the layer
-            if (!top_close && t_now) emit(thermo_between<MOIST, THETA>(pt, prev, cur, want_rh), b);
-            fin = true;
-        }
-    }
+        XP_DEV void here() { r.emit(cur, b); }
+    };
 };
 
 template <typename T, int NL, bool MOIST, bool THETA, bool COLB> __global__ __launch_bounds__(256)
@@ -161,24 +152,9 @@ void k_thermo_layers(ThermoLayersArgs a) {
         for (int i = 0; i < NL; ++i) {
             ThermoLayer<MOIST, THETA, COLB> &r = L[i];
             if (r.fin) continue;
-            double pb = qnan(), ptn = qnan();
-            bool b_now, t_now;
-            if (a.kind[i] == WL_HEIGHT) {
-                const double zb = z0 + a.bottom[i], zt = z0 + a.top[i];
-                b_now = !r.begun && cur.z >= zb;
-                t_now = isnan_(r.pt) && cur.z >= zt;
-                if (b_now) pb = interp_p(zb, prev.z, prev.p, cur.z, cur.p, has_prev);
-                if (t_now) ptn = interp_p(zt, prev.z, prev.p, cur.z, cur.p, has_prev);
-            } else {
-                const double bot = COLB ? r.pbc : a.bottom[i], top = COLB ? r.ptc : a.top[i];
-                pb = isnan_(bot) ? p0 : bot;
-                ptn = a.kind[i] == WL_PRESSURE ? top : pb - top;
-                // a layer that is empty (a NaN top that is not the open one included) or begins below the lowest level: left out
-                if (!has_prev && ((!a.open[i] && !(ptn < pb)) || pb > p0)) { r.fin = true; continue; }
-                b_now = !r.begun && cur.p <= pb;
-                t_now = isnan_(r.pt) && cur.p <= ptn;    // (never, for an open top: every level above the bottom is a point)
-            }
-            r.level(cur, prev, has_prev, pb, b_now, ptn, t_now, want_rh);
+            const LayerBounds b = layer_bounds(r, a.kind[i], COLB ? r.pbc : a.bottom[i], COLB ? r.ptc : a.top[i], a.open[i] != 0, z0, p0,
+                                               prev.z, prev.p, cur.z, cur.p, has_prev);
+            r.level(typename ThermoLayer<MOIST, THETA, COLB>::Step{r, cur, prev, want_rh, prev}, cur.p, prev.p, has_prev, b);
             all_fin = all_fin && r.fin;
         }
         done = all_fin;

@@ -6,19 +6,18 @@
 // The rules are stated in include/xparcel.h and restated in NumPy in tests/wind_layers_restatement.py.  The column kernel is
 // the walk of k_bunkers_storm_motion (xp_kinematics.hpp) with the layers as arguments: one upward pass with level-major
 // loads (coalesced when col_stride == 1) serves every layer of the call whatever its kind; the points of MetPy's get_layer
-// are emitted in order as the walk passes them -- the levels, and the added bound points interpolated in ln p between the
-// level below and the level above, the only places a logarithm is taken -- into each layer's running sums.  A lane is done at
-// the first level beyond its highest top; the loop ends with a wave-uniform ballot, so levels above the deepest top are never
-// read.  The kernel is instantiated on the number of layers and on whether a strongest-wind output is wanted: a layer's state
-// is 9 doubles, 13 with the strongest wind, and no instantiation may spill (tests/test_wind_layers_cpu.py; the register
-// counts are in DESIGN.md section 7).  It lives in a translation unit of its own (xp_wind_layers_tu.hip).
+// (which they are: xp_layer_gate.hpp) are emitted in order as the walk passes them into each layer's running sums, the added
+// bound points being the only places a logarithm is taken.  A lane is done at the first level beyond its highest top; the
+// loop ends with a wave-uniform ballot, so levels above the deepest top are never read.  The kernel is instantiated on the
+// number of layers and on whether a strongest-wind output is wanted: a layer's state is 9 doubles, 13 with the strongest
+// wind, and no instantiation may spill (tests/test_wind_layers_cpu.py; the register counts are in DESIGN.md section 7).  It
+// lives in a translation unit of its own (xp_wind_layers_tu.hip).
 #pragma once
-#include "xp_kernels.hpp"
+#include "xp_layer_gate.hpp"
 
 namespace xp {
 
 constexpr int WL_MAX_LAYERS = 4;
-constexpr int WL_PRESSURE = 0, WL_PRESSURE_DEPTH = 1, WL_HEIGHT = 2;   // include/xparcel.h's XP_LAYER_*
 
 struct WindLayersArgs {
     View p, u, v, z;                                     // z.data == nullptr: no height
@@ -35,16 +34,14 @@ struct WindLayersArgs {
 // (n layers, strongest wind wanted) of a call in the views' dtype: which instantiation runs it
 void launch_wind_layers(const WindLayersArgs &a, bool f64, bool want_max, hipStream_t s);
 
-// The running state of one layer.  The trapezoids of mean_pressure_weighted, trapz(U P, P), are summed of the wind relative to
-// the layer's first point (u0, v0), so that mean = u0 + trapz((U - u0) P, P) / (0.5 (P_last^2 - P_first^2)) is exact for a
-// constant wind, and the relative wind of the last point is the bulk shear.
-template <bool MAXW> struct WindLayer {
-    double su, sv, u0, v0, pf, pl, ul, vl;   // sums, first point's wind and pressure, last point: pressure, relative wind
-    double pt;                               // the top pressure once the walk has reached it (NaN before)
+// The running state of one layer: a LayerGate plus its sums.  The trapezoids of mean_pressure_weighted, trapz(U P, P), are summed
+// of the wind relative to the layer's first point (u0, v0), so that mean = u0 + trapz((U - u0) P, P) / (0.5 (P_last^2 -
+// P_first^2)) is exact for a constant wind, and the relative wind of the last point is the bulk shear.
+template <bool MAXW> struct WindLayer : LayerGate {
+    double su, sv, u0, v0, pf, ul, vl;       // sums, first point's wind and pressure, last point's relative wind
     double ms, mu, mv, mp;                   // MAXW: the strongest point so far: speed, wind, pressure
-    bool begun, started, top_close, fin;     // the bottom pressure is known; a point has been emitted; ...; finished
     XP_DEV void init() {
-        su = sv = 0.0; u0 = v0 = pf = pl = ul = vl = pt = qnan(); begun = started = top_close = fin = false;
+        init_gate(); su = sv = 0.0; u0 = v0 = pf = ul = vl = qnan();
         if constexpr (MAXW) { ms = -1.0; mu = mv = mp = qnan(); }
     }
     XP_DEV void emit(double p, double u, double v, double s) {          // s: hypot(u, v)
@@ -59,42 +56,21 @@ template <bool MAXW> struct WindLayer {
         } else { started = true; pf = p; u0 = u; v0 = v; u = v = 0.0; }
         pl = p; ul = u; vl = v;
     }
-    // an added bound point at pressure pe between the previous level (pp: higher pressure) and this one: u, v linear in ln p
-    XP_DEV void emit_between(double pe, double pp, double up, double vp, double p, double u, double v) {
+    // LayerGate::level's hooks at one valid level (p, u, v; s its speed) with the previous valid level (pp, up, vp) below it
+    struct Step {
+        WindLayer &r;
+        double p, u, v, s, pp, up, vp;
+        XP_DEV void below() { r.emit(pp, up, vp, MAXW ? hypot(up, vp) : 0.0); }
+        XP_DEV void bound(double pe) {                                  // u, v linear in ln p
 #pragma clang fp contract(off)
-        const double xe = flog(pe), xp_ = flog(pp), x = flog(p);
-        const double f = (xe - x) / (xp_ - x);
-        const double ue = u + f * (up - u), ve = v + f * (vp - v);
-        emit(pe, ue, ve, MAXW ? hypot(ue, ve) : 0.0);
-    }
-    // One valid level (p, u, v; s its speed) with the previous valid level (pp, up, vp) below it if has_prev.  pb, b_now: the
-    // bottom pressure, which became known at this level -- the first one at or beyond it; ptn, t_now: the same for the top.
-    XP_DEV void level(double p, double u, double v, double s, double pp, double up, double vp, bool has_prev, double pb,
-                      bool b_now, double ptn, bool t_now) {
-        if (fin) return;
-        if (b_now) {
-            begun = true;
-            if (has_prev && isclose_(pp, pb)) emit(pp, up, vp, MAXW ? hypot(up, vp) : 0.0);   // the level below, close to pb
-            else if (!isclose_(p, pb)) emit_between(pb, pp, up, vp, p, u, v);                 // pb itself, between the levels
+            const double xe = flog(pe), xp_ = flog(pp), x = flog(p);
+            const double f = (xe - x) / (xp_ - x);
+            const double ue = u + f * (up - u), ve = v + f * (vp - v);
+            r.emit(pe, ue, ve, MAXW ? hypot(ue, ve) : 0.0);
         }
-        if (!begun) return;
-        if (t_now) { pt = ptn; top_close = started && isclose_(pl, pt); }      // was the last point close to the top?
-        if (isnan_(pt) || p >= pt || isclose_(p, pt)) {
-            emit(p, u, v, s);
-            top_close = top_close || (!isnan_(pt) && isclose_(p, pt));
-        } else {                                         // the first level beyond the top: pt closes the layer
-            // (pt appeared at this level: had it appeared earlier, that level was in the layer and close to it)
-            if (!top_close && t_now) emit_between(pt, pp, up, vp, p, u, v);
-            fin = true;
-        }
-    }
+        XP_DEV void here() { r.emit(p, u, v, s); }
+    };
 };
-
-// np.interp(zc, z, p) at the first level (z, p) with z >= zc, the previous valid level (zp, pp) below it
-XP_DEV double interp_p(double zc, double zp, double pp, double z, double p, bool has_prev) {
-#pragma clang fp contract(off)
-    return (z == zc || !has_prev) ? p : (p - pp) / (z - zp) * (zc - zp) + pp;
-}
 
 template <typename T, int NL, bool MAXW> __global__ __launch_bounds__(256)
 void k_wind_layers(WindLayersArgs a) {
@@ -128,23 +104,8 @@ void k_wind_layers(WindLayersArgs a) {
         for (int i = 0; i < NL; ++i) {
             WindLayer<MAXW> &r = L[i];
             if (r.fin) continue;
-            double pb = qnan(), ptn = qnan();
-            bool b_now, t_now;
-            if (a.kind[i] == WL_HEIGHT) {
-                const double zb = z0 + a.bottom[i], zt = z0 + a.top[i];
-                b_now = !r.begun && z >= zb;
-                t_now = isnan_(r.pt) && z >= zt;
-                if (b_now) pb = interp_p(zb, zp, pp, z, p, has_prev);
-                if (t_now) ptn = interp_p(zt, zp, pp, z, p, has_prev);
-            } else {
-                pb = isnan_(a.bottom[i]) ? p0 : a.bottom[i];
-                ptn = a.kind[i] == WL_PRESSURE ? a.top[i] : pb - a.top[i];
-                // a layer that is empty or begins below the lowest level: left out (no point emitted, no top reached)
-                if (!has_prev && (!(ptn < pb) || pb > p0)) { r.fin = true; continue; }
-                b_now = !r.begun && p <= pb;
-                t_now = isnan_(r.pt) && p <= ptn;
-            }
-            r.level(p, u, v, s, pp, up, vp, has_prev, pb, b_now, ptn, t_now);
+            const LayerBounds b = layer_bounds(r, a.kind[i], a.bottom[i], a.top[i], false, z0, p0, zp, pp, z, p, has_prev);
+            r.level(typename WindLayer<MAXW>::Step{r, p, u, v, s, pp, up, vp}, p, pp, has_prev, b);
             all_fin = all_fin && r.fin;
         }
         done = all_fin;

@@ -1199,6 +1199,32 @@ int xp_supercell_composite(int64_t n, int32_t dtype, int32_t mem, const void *mu
     return per_point<xp::ScpOp>("xp_supercell_composite", n, dtype, mem, {mucape, srh, shear}, 3, {out}, true, stream);
 }
 
+// One layer of an xp_wind_layers / xp_thermo_layers request, checked; *bottom_out, *top_out: its bounds as the kernels take them
+// (NaN where bottom_col / top_col replaces the scalar; a NaN bottom height: 0).  allow_open: a NaN top by pressure is the open one.
+static int check_layer(const char *entry, int i, const xp_wind_layer &l, bool have_z, const void *bottom_col, const void *top_col,
+                       bool allow_open, double *bottom_out, double *top_out) {
+    double bottom = bottom_col ? (double)NAN : l.bottom;
+    const double top = top_col ? (double)NAN : l.top;
+    if (l.kind != XP_LAYER_PRESSURE && l.kind != XP_LAYER_PRESSURE_DEPTH && l.kind != XP_LAYER_HEIGHT)
+        return fail(XP_E_ARG, "%s: layers[%d]: unknown kind %d", entry, i, (int)l.kind);
+    if ((bottom_col || top_col) && l.kind != XP_LAYER_PRESSURE)
+        return fail(XP_E_ARG, "%s: layers[%d]: per-column bounds need kind XP_LAYER_PRESSURE", entry, i);
+    // a top that an array replaces is not looked at
+    if (!top_col && !std::isfinite(top) && !(allow_open && l.kind == XP_LAYER_PRESSURE && std::isnan(top)))
+        return fail(XP_E_ARG, allow_open ? "%s: layers[%d]: top must be finite (or, by pressure, NaN: to the highest valid level)"
+                                         : "%s: layers[%d]: top must be finite", entry, i);
+    if (std::isinf(bottom)) return fail(XP_E_ARG, "%s: layers[%d]: bottom must be finite or NaN", entry, i);
+    if (l.kind == XP_LAYER_PRESSURE_DEPTH && !(top > 0.0)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive", entry, i);
+    if (l.kind == XP_LAYER_HEIGHT) {
+        if (!have_z) return fail(XP_E_ARG, "%s: layers[%d]: a layer by height needs height", entry, i);
+        if (std::isnan(bottom)) bottom = 0.0;
+        if (bottom < 0.0) return fail(XP_E_ARG, "%s: layers[%d]: bottom height must be >= 0", entry, i);
+        if (!(top > bottom)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive (top above bottom)", entry, i);
+    }
+    *bottom_out = bottom; *top_out = top;
+    return 0;
+}
+
 int xp_wind_layers(const xp_view *p, const xp_view *u, const xp_view *v, const xp_view *z, int32_t nlayer,
                    const xp_wind_layer *layers, xp_wind_layers_out *out, void *stream) {
     const char *const entry = "xp_wind_layers";
@@ -1213,20 +1239,8 @@ int xp_wind_layers(const xp_view *p, const xp_view *u, const xp_view *v, const x
     xp::WindLayersArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < nlayer; ++i) {
-        const xp_wind_layer &l = layers[i];
-        double bottom = l.bottom;
-        if (l.kind != XP_LAYER_PRESSURE && l.kind != XP_LAYER_PRESSURE_DEPTH && l.kind != XP_LAYER_HEIGHT)
-            return fail(XP_E_ARG, "%s: layers[%d]: unknown kind %d", entry, i, (int)l.kind);
-        if (!std::isfinite(l.top)) return fail(XP_E_ARG, "%s: layers[%d]: top must be finite", entry, i);
-        if (std::isinf(bottom)) return fail(XP_E_ARG, "%s: layers[%d]: bottom must be finite or NaN", entry, i);
-        if (l.kind == XP_LAYER_PRESSURE_DEPTH && !(l.top > 0.0)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive", entry, i);
-        if (l.kind == XP_LAYER_HEIGHT) {
-            if (!z) return fail(XP_E_ARG, "%s: layers[%d]: a layer by height needs height", entry, i);
-            if (std::isnan(bottom)) bottom = 0.0;
-            if (bottom < 0.0) return fail(XP_E_ARG, "%s: layers[%d]: bottom height must be >= 0", entry, i);
-            if (!(l.top > bottom)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive (top above bottom)", entry, i);
-        }
-        a.kind[i] = l.kind; a.bottom[i] = bottom; a.top[i] = l.top;
+        if ((rc = check_layer(entry, i, layers[i], z != nullptr, nullptr, nullptr, false, &a.bottom[i], &a.top[i]))) return rc;
+        a.kind[i] = layers[i].kind;
     }
     const size_t cb = rows_bytes(p, 1);
     if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)) ||
@@ -1266,25 +1280,8 @@ int xp_thermo_layers(const xp_view *p, const xp_view *t, const xp_view *td, cons
     for (int i = 0; i < nlayer; ++i) {
         const xp_wind_layer &l = layers[i];
         const void *const bc = bottom_columns ? bottom_columns[i] : nullptr, *const tc = top_columns ? top_columns[i] : nullptr;
-        double bottom = bc ? (double)NAN : l.bottom;
-        const double top = tc ? (double)NAN : l.top;
-        if (l.kind != XP_LAYER_PRESSURE && l.kind != XP_LAYER_PRESSURE_DEPTH && l.kind != XP_LAYER_HEIGHT)
-            return fail(XP_E_ARG, "%s: layers[%d]: unknown kind %d", entry, i, (int)l.kind);
-        if ((bc || tc) && l.kind != XP_LAYER_PRESSURE)
-            return fail(XP_E_ARG, "%s: layers[%d]: per-column bounds need kind XP_LAYER_PRESSURE", entry, i);
-        // a NaN top by pressure is the open one; a top that an array replaces is not looked at
-        if (!tc && !std::isfinite(top) && !(l.kind == XP_LAYER_PRESSURE && std::isnan(top)))
-            return fail(XP_E_ARG, "%s: layers[%d]: top must be finite (or, by pressure, NaN: to the highest valid level)", entry, i);
-        if (std::isinf(bottom)) return fail(XP_E_ARG, "%s: layers[%d]: bottom must be finite or NaN", entry, i);
-        if (l.kind == XP_LAYER_PRESSURE_DEPTH && !(top > 0.0)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive", entry, i);
-        if (l.kind == XP_LAYER_HEIGHT) {
-            if (!z) return fail(XP_E_ARG, "%s: layers[%d]: a layer by height needs height", entry, i);
-            if (std::isnan(bottom)) bottom = 0.0;
-            if (bottom < 0.0) return fail(XP_E_ARG, "%s: layers[%d]: bottom height must be >= 0", entry, i);
-            if (!(top > bottom)) return fail(XP_E_ARG, "%s: layers[%d]: depth must be positive (top above bottom)", entry, i);
-        }
-        a.kind[i] = l.kind; a.bottom[i] = bottom; a.top[i] = top;
-        a.open[i] = l.kind == XP_LAYER_PRESSURE && !tc && std::isnan(top);
+        if ((rc = check_layer(entry, i, l, z != nullptr, bc, tc, true, &a.bottom[i], &a.top[i]))) return rc;
+        a.kind[i] = l.kind; a.open[i] = l.kind == XP_LAYER_PRESSURE && !tc && std::isnan(a.top[i]);
         colb = colb || bc || tc;
         // what each wanted output reads
         const bool rh = out->mean_relative_humidity[i] != nullptr, lapse = out->lapse_rate[i] != nullptr;

@@ -947,6 +947,19 @@ def _wind_layer(spec):
     return kinds[kind], float('nan') if bottom is None else float(bottom), float(top)
 
 
+def _layers_out(c, out_type, keys, n):
+    """What wind_layers and thermo_layers return, and the entry point's output struct pointing into it: one array per key with
+    a leading axis of the n layers, and the per-column 'status'."""
+    res = {k: c.out((n,) + c.hshape) for k in keys}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = out_type(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
+    for k in keys:
+        arr = getattr(out, k)
+        for i in range(n):
+            arr[i] = _ptr(res[k][i:i + 1])
+    return res, out
+
+
 def wind_layers(pressure, u, v, height=None, layers=(), want=None):
     """The wind over up to four layers of every column in one pass (xp_wind_layers): pressure [hPa], u, v [m/s] and, for
     layers given by height, height [m] on one vertical, (nlev, ...).  `layers`: a sequence of layers, each a dict or a tuple
@@ -964,13 +977,7 @@ def wind_layers(pressure, u, v, height=None, layers=(), want=None):
     c = _Call(pressure, u, v, *(() if height is None else (height,)))
     assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, u, v, height must share a shape'
     n = len(specs)
-    res = {k: c.out((n,) + c.hshape) for k in keys}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = L.WindLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in keys:
-        arr = getattr(out, k)
-        for i in range(n):
-            arr[i] = _ptr(res[k][i:i + 1])
+    res, out = _layers_out(c, L.WindLayersOut, keys, n)
     views = [c.view(a) for a in c.ins] + [None]
     c.run('xp_wind_layers', *views[:4], n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]), out)
     return res
@@ -1104,13 +1111,7 @@ def thermo_layers(pressure, temperature=None, dewpoint=None, height=None, layers
     c = _Call(pressure, *[given[v] for v in names[1:]], *bounds)
     ins = dict(zip(names, c.ins))
     assert all(a.shape == ins['pressure'].shape for a in ins.values()), 'pressure, temperature, dewpoint, height must share a shape'
-    res = {k: c.out((n,) + c.hshape) for k in keys}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = L.ThermoLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in keys:
-        arr = getattr(out, k)
-        for i in range(n):
-            arr[i] = _ptr(res[k][i:i + 1])
+    res, out = _layers_out(c, L.ThermoLayersOut, keys, n)
     cols = [[None if s[j] is None else c.per_col(s[j]) for s in specs] for j in (3, 4)]
     bcols, tcols = (None if all(x is None for x in col) else (C.c_void_p * n)(*[None if x is None else _ptr(x) for x in col])
                     for col in cols)
