@@ -105,8 +105,10 @@ enum {
                                    depth's outputs NaN */
     XP_ST_BAD_HEIGHT = 32,      /* xp_bunkers_storm_motion, xp_storm_relative_helicity: a height not above the valid level
                                    below it (heights must increase strictly); every output NaN */
-    XP_ST_LAYER_OPEN = 64       /* xp_effective_inflow_layer: the last candidate of the search window passes, i.e.
+    XP_ST_LAYER_OPEN = 64,      /* xp_effective_inflow_layer: the last candidate of the search window passes, i.e.
                                    search_depth (or the column top) cut the layer, which might extend further */
+    XP_ST_NO_CCL = 128          /* xp_sounding_indices: the dewpoint line of the CCL's mixing ratio never crosses the
+                                   environment temperature; the three CCL outputs NaN */
 };
 
 typedef struct {
@@ -601,6 +603,72 @@ typedef struct {
 int xp_thermo_layers(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint, const xp_view *height,
                      int32_t nlayer, const xp_wind_layer *layers, const void *const *bottom_columns,
                      const void *const *top_columns, xp_thermo_layers_out *out, void *stream);
+
+/* The classic sounding indices and the convective condensation level of every column in ONE upward pass: MetPy 1.4's k_index,
+   total_totals_index, cross_totals, vertical_totals, showalter_index, sweat_index and ccl (the reference has no counterpart),
+   carried over to gridded columns whose levels are not the mandatory ones.  Parity with MetPy itself is UNPINNED: MetPy selects
+   the mandatory levels by equality, the interpolation to the isobars is this library's extension, and the tests hold the kernel
+   to a NumPy restatement of the rules below only (tests/sounding_indices_restatement.py).
+   Inputs: pressure [hPa], temperature, dewpoint [K] as (nlev, ncol) views of one shape, dtype and mem, level 0 lowest, pressure
+   decreasing; u, v [m/s] on the same vertical, nullable, both or neither: only sweat_index reads them.
+   Valid levels: a level is THERMODYNAMICALLY VALID when p, T and Td are all non-NaN, and WIND-VALID when p, u and v are.  Invalid
+   levels are dropped (MetPy's _remove_nans); nothing is interpolated through them.
+   Value at an isobar P* (850, 700, 500 hPa): a valid level with p == P* gives its values as they are; otherwise the value is
+   linear in ln p between the nearest valid level below and the nearest above (MetPy's log_interpolate_1d), NaN without both.
+   T and Td use the thermodynamically valid levels, u and v the wind-valid ones.
+   Span: if the thermodynamically valid levels do not bracket both 850 and 500 hPa (one with p >= 850 and one with p <= 500), the
+   six indices are NaN and the status carries XP_ST_NO_LAYER; sweat_index is NaN too when the wind-valid levels do not.  The CCL
+   outputs do not depend on the span.
+   Indices (differences in K; [degC] = minus 273.15), in double, in this operation order, without contraction:
+     vertical_totals  VT = T850 - T500
+     cross_totals     CT = Td850 - T500
+     total_totals     TT = VT + CT
+     k_index          (VT + Td850[degC]) - (T700 - Td700)
+     showalter_index  T500 - Tp500: the parcel (850 hPa, T850, Td850) is lifted to its LCL (xp_lcl); with an LCL pressure
+                      <= 500 hPa it rises on the dry adiabat alone, Tp500 = T850 (500 / 850)^kappa; otherwise on the moist
+                      adiabat from the LCL to 500 hPa (xp_moist_lapse from (p_lcl, T_lcl), bit for bit) in the call's moist mode:
+                      XP_MOIST_EXACT and XP_MOIST_FAMILY both run RK4, XP_MOIST_TABLE the lookup tables.  No virtual temperature
+                      correction.  An LCL that did not converge gives NaN and XP_ST_LCL_NOT_CONVERGED.
+     sweat_index      (((12 max(Td850[degC], 0) + 20 max(TT - 49, 0)) + 2 f850) + f500) + shear
+                      f = sqrt(u u + v v) / (1852 / 3600) [kt] and dir = 90 - atan2(-v, -u) [degrees], plus 360 where that is <= 0
+                      (so in (0, 360]), both from the INTERPOLATED u, v;  shear = 125 (sin(dir500 - dir850) + 0.2) when
+                      130 <= dir850 <= 250, 210 <= dir500 <= 310, dir500 - dir850 > 0, f850 >= 15 and f500 >= 15 all hold,
+                      otherwise 0.
+   CCL (metpy.calc.ccl): the start level (p0, T0, Td0) is the lowest thermodynamically valid level.  The mixing ratio r is
+   w_s(p0, Td0) with ccl_mixed_layer_depth == 0, otherwise the mixed-layer mean mixing ratio over the lowest
+   ccl_mixed_layer_depth hPa, exactly the one of xp_select_parcel's mixed-layer parcel (pf.py:137-162, 229-289; on the column
+   as given).  rt(p) = dewpoint(e = p r / (eps + r)) at every thermodynamically valid level -- except that with depth 0 rt at
+   the start level IS Td0, not the round trip through r, so that a saturated surface has rt - T == 0 exactly there.  With
+   d = rt - T, every pair of consecutive valid levels whose sign(d) differ (zero being a sign of its own, as for np.sign; a NaN
+   d is no sign and its pairs hold no crossing) holds a crossing: at ln p and rt value given by xp_find_intersections' two
+   expressions (pf.py:1046, 1050) with x = ln p, a = rt, b = T, ccl_pressure = exp(x) -- or, where d is exactly 0 at one end of
+   the pair, at that level itself (its p and rt as they are).  ccl_which = XP_CCL_TOP (MetPy's default)
+   takes the last crossing, XP_CCL_BOTTOM the first.  ccl_temperature = rt at the crossing; convective_temperature =
+   ccl_temperature (p0 / ccl_pressure)^kappa.  Without a crossing the three are NaN and the status carries XP_ST_NO_CCL.
+   Every output may be NULL and NULL outputs skip their work: levels are read up to the first valid level at or above 500 hPa
+   (wind levels likewise, and u, v only while they are needed), up to the first crossing for XP_CCL_BOTTOM, and to the top of
+   the column only for XP_CCL_TOP.  Values do not depend on which other outputs are asked for.  The status bits belong to
+   outputs: XP_ST_NO_LAYER is reported when one of the six indices is wanted, XP_ST_LCL_NOT_CONVERGED when showalter_index is,
+   XP_ST_NO_CCL when a CCL output is.  The outputs share the views' dtype and mem; strided device views are read in place.
+   opts NULL: XP_MOIST_EXACT, XP_CCL_TOP, depth 0.  XP_E_ARG: a NULL or mismatched view; u without v or v without u;
+   sweat_index wanted without u and v; a NULL out or one whose dtype or mem differs from the views'; an unknown moist_mode or
+   ccl_which; a ccl_mixed_layer_depth that is negative or not finite.  XP_E_NO_TABLES: XP_MOIST_TABLE without tables. */
+enum { XP_CCL_TOP = 0, XP_CCL_BOTTOM = 1 };
+typedef struct {
+    int32_t moist_mode;             /* XP_MOIST_* */
+    int32_t ccl_which;              /* XP_CCL_* */
+    double ccl_mixed_layer_depth;   /* hPa; 0 = the surface parcel */
+} xp_sounding_opts;
+typedef struct {
+    void *k_index, *total_totals, *cross_totals, *vertical_totals, *showalter_index;   /* K, ncol each */
+    void *sweat_index;                                                                 /* dimensionless */
+    void *ccl_pressure, *ccl_temperature, *convective_temperature;                     /* hPa, K, K */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_LCL_NOT_CONVERGED | XP_ST_NO_CCL */
+    int32_t dtype, mem;
+} xp_sounding_out;
+int xp_sounding_indices(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint,
+                        const xp_view *u, const xp_view *v, const xp_sounding_opts *opts,
+                        xp_sounding_out *out, void *stream);
 
 /* metpy.calc.critical_angle per point [degrees]: the angle between a = (shear_u, shear_v), the 0-500 m ln p bulk shear, and
    b = (storm_u - surface_u, storm_v - surface_v), evaluated as atan2(|a x b|, a . b) -- mathematically MetPy's

@@ -28,7 +28,7 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
            'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
-           'xp_wind_layers', 'xp_thermo_layers', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
+           'xp_wind_layers', 'xp_thermo_layers', 'xp_sounding_indices', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
            'xp_ncape', 'xp_ecape', 'xp_last_error')
 
 
@@ -189,6 +189,22 @@ class ThermoLayersOut(C.Structure):
                 [('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)])
 
 
+# xp_sounding_indices: its options and per-column outputs, the CCL choices, and the status bit of a column without a CCL
+ST_NO_CCL = 128
+CCL_WHICH = {'top': 0, 'bottom': 1}
+SOUNDING_INDEX_OUT = ('k_index', 'total_totals', 'cross_totals', 'vertical_totals', 'showalter_index', 'sweat_index')
+SOUNDING_CCL_OUT = ('ccl_pressure', 'ccl_temperature', 'convective_temperature')
+SOUNDING_OUT = SOUNDING_INDEX_OUT + SOUNDING_CCL_OUT
+
+
+class SoundingOpts(C.Structure):
+    _fields_ = [('moist_mode', C.c_int32), ('ccl_which', C.c_int32), ('ccl_mixed_layer_depth', C.c_double)]
+
+
+class SoundingOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in SOUNDING_OUT + ('status',)] + [('dtype', C.c_int32), ('mem', C.c_int32)]
+
+
 # xp_ncape: its per-column outputs; xp_ecape: its per-point inputs and outputs
 NCAPE_OUT = ('ncape', 'lfc_height', 'el_height', 'status')
 ECAPE_IN = ('cape', 'ncape', 'el_height', 'sr_u', 'sr_v')
@@ -260,6 +276,7 @@ ARGTYPES = {
     'xp_wind_layers': (_V, _V, _V, _V, _i32, C.POINTER(WindLayer), C.POINTER(WindLayersOut), _ptr),
     'xp_thermo_layers': (_V, _V, _V, _V, _i32, C.POINTER(WindLayer), C.POINTER(_ptr), C.POINTER(_ptr),
                          C.POINTER(ThermoLayersOut), _ptr),
+    'xp_sounding_indices': (_V, _V, _V, _V, _V, C.POINTER(SoundingOpts), C.POINTER(SoundingOut), _ptr),
     'xp_critical_angle': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_corfidi_storm_motion': (_i64, _i32, _i32) + (_ptr,) * 9,
     'xp_significant_tornado_effective': (_i64, _i32, _i32) + (_ptr,) * 8,
@@ -309,10 +326,12 @@ THERMO_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 # The layer CAPE / CIN kernel (csrc/xp_cape_layers.hpp): the ascent of the effective-inflow kernel, and its flag for its reason
 # (104-111 VGPRs without a spill).
 CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The sounding-indices kernel (csrc/xp_sounding.hpp) takes no flag: 59-84 VGPRs without winds, 81-105 with them, no scratch.
 UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
-         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', [])] + [
+         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),
+         ('sounding', 'xp_sounding_tu.hip', [])] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

@@ -21,13 +21,15 @@
 #include "xp_cape_layers.hpp"
 #include "xp_wind_layers.hpp"
 #include "xp_thermo_layers.hpp"
+#include "xp_sounding.hpp"
 #include "xp_ecape.hpp"
 #include "xp_per_point.hpp"
 
 static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_ST_LCL_NOT_CONVERGED &&
               xp::ST_NAN_PRESSURE == XP_ST_NAN_PRESSURE && xp::ST_BAD_PRESSURE == XP_ST_BAD_PRESSURE &&
               xp::ST_NO_LAYER == XP_ST_NO_LAYER && xp::ST_BAD_HEIGHT == XP_ST_BAD_HEIGHT &&
-              xp::ST_LAYER_OPEN == XP_ST_LAYER_OPEN, "the kernels' status bits are the ABI's");
+              xp::ST_LAYER_OPEN == XP_ST_LAYER_OPEN && xp::ST_NO_CCL == XP_ST_NO_CCL, "the kernels' status bits are the ABI's");
+static_assert(xp::CCL_TOP == XP_CCL_TOP && xp::CCL_BOTTOM == XP_CCL_BOTTOM, "the kernel's CCL choices are the ABI's");
 static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
               xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
 
@@ -1313,6 +1315,51 @@ int xp_thermo_layers(const xp_view *p, const xp_view *t, const xp_view *td, cons
     if ((rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
     a.nlev = p->nlev; a.ncol = p->ncol; a.n = nlayer;
     xp::launch_thermo_layers(a, p->dtype == XP_F64, moist, theta, colb, st.s);
+    return st.finish();
+}
+
+int xp_sounding_indices(const xp_view *p, const xp_view *t, const xp_view *td, const xp_view *u, const xp_view *v,
+                        const xp_sounding_opts *o, xp_sounding_out *out, void *stream) {
+    const char *const entry = "xp_sounding_indices";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}}))) return rc;
+    if ((u != nullptr) != (v != nullptr)) return fail(XP_E_ARG, "%s: u and v must be given together (%s is null)", entry, u ? "v" : "u");
+    if (u && (rc = check_views({{p, "pressure"}, {u, "u"}, {v, "v"}}))) return rc;
+    if ((rc = check_out(entry, out, p))) return rc;
+    if (out->sweat_index && !u) return fail(XP_E_ARG, "%s: sweat_index needs u and v", entry);
+    xp_sounding_opts opts;
+    memset(&opts, 0, sizeof(opts));
+    if (o) opts = *o;
+    if (opts.moist_mode != XP_MOIST_EXACT && opts.moist_mode != XP_MOIST_TABLE && opts.moist_mode != XP_MOIST_FAMILY)
+        return fail(XP_E_ARG, "%s: moist_mode: unknown mode %d", entry, (int)opts.moist_mode);
+    if (opts.ccl_which != XP_CCL_TOP && opts.ccl_which != XP_CCL_BOTTOM)
+        return fail(XP_E_ARG, "%s: ccl_which: unknown choice %d", entry, (int)opts.ccl_which);
+    if (!(std::isfinite(opts.ccl_mixed_layer_depth) && opts.ccl_mixed_layer_depth >= 0.0))
+        return fail(XP_E_ARG, "%s: ccl_mixed_layer_depth must be 0 or finite and positive", entry);
+    const bool want_ccl = out->ccl_pressure || out->ccl_temperature || out->convective_temperature;
+    const bool wind = out->sweat_index != nullptr;
+    const int tm = opts.moist_mode == XP_MOIST_TABLE;
+    const size_t cb = rows_bytes(p, 1);
+    TableSet ts;
+    xp::SoundingArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) ||
+        (rc = stage_view(st, td, &a.td)) || (wind && ((rc = stage_view(st, u, &a.u)) || (rc = stage_view(st, v, &a.v)))) ||
+        (rc = st.out(out->k_index, cb, out->mem, &a.k_index)) || (rc = st.out(out->total_totals, cb, out->mem, &a.total_totals)) ||
+        (rc = st.out(out->cross_totals, cb, out->mem, &a.cross_totals)) ||
+        (rc = st.out(out->vertical_totals, cb, out->mem, &a.vertical_totals)) ||
+        (rc = st.out(out->showalter_index, cb, out->mem, &a.showalter)) || (rc = st.out(out->sweat_index, cb, out->mem, &a.sweat)) ||
+        (rc = st.out(out->ccl_pressure, cb, out->mem, &a.ccl_p)) || (rc = st.out(out->ccl_temperature, cb, out->mem, &a.ccl_t)) ||
+        (rc = st.out(out->convective_temperature, cb, out->mem, &a.conv_t)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = p->nlev; a.ncol = p->ncol;
+    a.table_mode = tm; a.which = opts.ccl_which; a.ml_depth = opts.ccl_mixed_layer_depth;
+    a.want_index = a.k_index || a.total_totals || a.cross_totals || a.vertical_totals || a.showalter || a.sweat;
+    a.tb = ts.tb; a.es_tab = ts.es;
+    const int ccl = !want_ccl ? xp::CCL_NONE : opts.ccl_mixed_layer_depth > 0.0 ? xp::CCL_MIXED : xp::CCL_SURFACE;
+    xp::launch_sounding(a, p->dtype == XP_F64, wind, ccl, st.s);
     return st.finish();
 }
 

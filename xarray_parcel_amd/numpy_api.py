@@ -1167,6 +1167,80 @@ def theta_e_difference(pressure, temperature, dewpoint, height):
     return _where(~(res['theta_e_max_pressure'][0] < res['theta_e_min_pressure'][0]), diff, 0.0)
 
 
+def sounding_indices(pressure, temperature, dewpoint, u=None, v=None, *, moist=None, which='top', mixed_layer_depth=None,
+                     want=None):
+    """The classic sounding indices and the convective condensation level of every column in one pass (xp_sounding_indices;
+    include/xparcel.h has the rules): pressure [hPa], temperature, dewpoint [K] and, for the SWEAT index, u, v [m/s] on one
+    vertical, (nlev, ...).  Values at 850, 700 and 500 hPa are the level's own where a valid level lies on the isobar and
+    linear in ln p between the neighbouring valid levels otherwise.  Returns a dict of per-column 'k_index', 'total_totals',
+    'cross_totals', 'vertical_totals', 'showalter_index' [K], 'sweat_index', 'ccl_pressure' [hPa], 'ccl_temperature' and
+    'convective_temperature' [K] -- those that `want` names; by default all of them, 'sweat_index' only with winds -- and
+    'status' (XP_ST_NO_LAYER: the column does not span 850 ... 500 hPa, the indices NaN; ST_NO_CCL: no CCL, its three outputs
+    NaN; ST_LCL_NOT_CONVERGED: the Showalter parcel's LCL; each bit only where an output it belongs to is wanted).
+    moist: the Showalter parcel's moist adiabat ('exact', 'family': RK4; 'table': the lookup tables).  which: 'top' (MetPy's
+    default) or 'bottom', the CCL crossing taken.  mixed_layer_depth [hPa]: the CCL of the mixed-layer mean mixing ratio over
+    that depth instead of the lowest valid level's (None or 0)."""
+    assert (u is None) == (v is None), 'u and v must be given together'
+    assert which in L.CCL_WHICH, "which must be 'top' or 'bottom'"
+    depth = 0.0 if mixed_layer_depth is None else float(mixed_layer_depth)
+    assert np.isfinite(depth) and depth >= 0.0, 'mixed_layer_depth must be None, 0 or finite and positive'
+    if want is None:
+        keys = tuple(k for k in L.SOUNDING_OUT if k != 'sweat_index' or u is not None)
+    else:
+        keys = tuple(want)
+        assert set(keys) <= set(L.SOUNDING_OUT), 'want: unknown output'
+        assert 'sweat_index' not in keys or u is not None, 'sweat_index needs u and v'
+    c = _Call(pressure, temperature, dewpoint, *([] if u is None else [u, v]))
+    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, temperature, dewpoint, u, v must share a shape'
+    res = {k: c.out(c.hshape) for k in keys}
+    res['status'] = c.out(c.hshape, np.int32)
+    out = L.SoundingOut(dtype=c.xp_dtype, mem=c.mem)
+    for k, a in res.items():
+        setattr(out, k, _ptr(a))
+    views = [c.view(a) for a in c.ins] + [None] * (5 - len(c.ins))
+    c.run('xp_sounding_indices', *views, L.SoundingOpts(L.MOIST[moist or _DEFAULT['moist']], L.CCL_WHICH[which], depth), out)
+    return res
+
+
+def k_index(pressure, temperature, dewpoint):
+    """metpy.calc.k_index [K] of every column: (T850 - T500) + Td850[degC] - (T700 - Td700)."""
+    return sounding_indices(pressure, temperature, dewpoint, want=('k_index',))['k_index']
+
+
+def total_totals_index(pressure, temperature, dewpoint):
+    """metpy.calc.total_totals_index [K] of every column: (T850 - T500) + (Td850 - T500)."""
+    return sounding_indices(pressure, temperature, dewpoint, want=('total_totals',))['total_totals']
+
+
+def cross_totals(pressure, temperature, dewpoint):
+    """metpy.calc.cross_totals [K] of every column: Td850 - T500."""
+    return sounding_indices(pressure, temperature, dewpoint, want=('cross_totals',))['cross_totals']
+
+
+def vertical_totals(pressure, temperature, dewpoint=None):
+    """metpy.calc.vertical_totals [K] of every column: T850 - T500.  MetPy's takes no dewpoint; here a level counts only
+    where its dewpoint is valid too, so without one the temperature stands in for it."""
+    return sounding_indices(pressure, temperature, temperature if dewpoint is None else dewpoint,
+                            want=('vertical_totals',))['vertical_totals']
+
+
+def showalter_index(pressure, temperature, dewpoint, moist=None):
+    """metpy.calc.showalter_index [K] of every column: T500 minus the 500 hPa temperature of the parcel lifted from 850 hPa."""
+    return sounding_indices(pressure, temperature, dewpoint, moist=moist, want=('showalter_index',))['showalter_index']
+
+
+def sweat_index(pressure, temperature, dewpoint, u, v):
+    """metpy.calc.sweat_index of every column, from u, v [m/s] instead of MetPy's speed and direction."""
+    return sounding_indices(pressure, temperature, dewpoint, u, v, want=('sweat_index',))['sweat_index']
+
+
+def ccl(pressure, temperature, dewpoint, mixed_layer_depth=None, which='top'):
+    """metpy.calc.ccl of every column: (ccl_pressure [hPa], ccl_temperature [K], convective_temperature [K]); NaN where
+    the dewpoint line of the parcel's mixing ratio never crosses the temperature."""
+    res = sounding_indices(pressure, temperature, dewpoint, which=which, mixed_layer_depth=mixed_layer_depth, want=L.SOUNDING_CCL_OUT)
+    return tuple(res[k] for k in L.SOUNDING_CCL_OUT)
+
+
 def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure):
     """The buoyancy-dilution potential NCAPE of entraining CAPE (Peters et al. 2023) for every column (xp_ncape): the integral
     over height, between the LFC and the EL, of -(g / (cp T)) (hbar - hs) of the ENVIRONMENT -- hbar the mean moist static
