@@ -107,8 +107,10 @@ enum {
                                    below it (heights must increase strictly); every output NaN */
     XP_ST_LAYER_OPEN = 64,      /* xp_effective_inflow_layer: the last candidate of the search window passes, i.e.
                                    search_depth (or the column top) cut the layer, which might extend further */
-    XP_ST_NO_CCL = 128          /* xp_sounding_indices: the dewpoint line of the CCL's mixing ratio never crosses the
+    XP_ST_NO_CCL = 128,         /* xp_sounding_indices: the dewpoint line of the CCL's mixing ratio never crosses the
                                    environment temperature; the three CCL outputs NaN */
+    XP_ST_NOT_CONVERGED = 256   /* xp_isentropic_interpolation: the Newton iteration of some target took max_iters steps
+                                   without meeting eps; that target's outputs NaN */
 };
 
 typedef struct {
@@ -669,6 +671,57 @@ typedef struct {
 int xp_sounding_indices(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint,
                         const xp_view *u, const xp_view *v, const xp_sounding_opts *opts,
                         xp_sounding_out *out, void *stream);
+
+/* Isentropic interpolation (metpy.calc.isentropic_interpolation; the reference has no counterpart): pressure, temperature and up
+   to four further variables of every column on up to XP_ISEN_MAX_LEVELS surfaces of constant potential temperature, in ONE read
+   of pressure and temperature.  Parity with MetPy itself is UNPINNED: MetPy is not installed where this library is tested, and
+   the tests hold the kernel to a NumPy restatement of the rules below only (tests/isentropic_restatement.py).  Three deliberate
+   differences from MetPy: (1) the solver and its stopping rule -- MetPy solves the same equation with SciPy's
+   Steffensen-accelerated fixed_point and a RELATIVE test on ln p; here it is Newton with an ABSOLUTE test on ln p, under
+   MetPy's names and default values (max_iters, eps); (2) ONE bracketing pair serves the pressure and the further variables --
+   on a column whose theta does not increase strictly MetPy sorts theta for its interpolate_1d and may read other levels there
+   than it used for the pressure; (3) NaN plus a status bit instead of raising (MetPy raises only when a target exceeds the
+   whole grid's maximum theta).
+   Inputs: pressure [hPa] and temperature [K] as (nlev, ncol) views of one shape, dtype and mem, level 0 lowest, pressure
+   decreasing; nvar in 0 ... 4 further variables on the same vertical, same shape, dtype and mem; nlevel in
+   1 ... XP_ISEN_MAX_LEVELS target potential temperatures [K] as host doubles, finite and strictly increasing (64: one 64-bit
+   word holds a per-target flag).  f32 inputs are converted exactly; all arithmetic is in double, without contraction.
+   Valid levels: a level is valid when p and T are both non-NaN.  Invalid levels are dropped, as everywhere in this library;
+   nothing is interpolated through them.  A NaN in a further variable does not invalidate a level.
+   Potential temperature of a valid level: x_k = ln p_k, theta_k = T_k exp(kappa (ln 1000 - x_k)), kappa = 2 / 7.
+   Bracketing pair of a target theta* (MetPy's find_bounding_indices): a pair of consecutive valid levels (k, k + 1) holds a
+   crossing when (theta_k <= theta*) differs from (theta_k+1 <= theta*); either direction counts (an unstable layer crosses
+   downward).  from_below != 0 (the default; MetPy's bottom_up_search=True) takes the lowest such pair, from_below == 0 the
+   highest.  No such pair: every output of that target is NaN in that column and the column's status carries XP_ST_NO_LAYER.
+   Pressure on the surface: T is linear in ln p on the pair, a = (T_k+1 - T_k) / (x_k+1 - x_k), b = T_k+1 - a x_k+1.  Newton on
+   f(x) = theta* - (a x + b) exp(kappa (ln 1000 - x)) starts at the midpoint x = 0.5 (x_k + x_k+1); with
+   e = exp(kappa (ln 1000 - x)), t = a x + b, f = theta* - e t and f' = e (kappa t - a) the step is x <- x - f / f'.  The
+   iteration is converged after the step with |x_new - x| <= eps (absolute in ln p, i.e. relative in p) and the result is
+   x_new; at most max_iters steps are taken.  Without convergence the target's outputs are NaN and the status carries
+   XP_ST_NOT_CONVERGED.  pressure[j] = exp(x); temperature[j] = theta* exp(-kappa (ln 1000 - x)) (MetPy's temperature_out).
+   Further variables: linear in theta between the same two levels, v = v_k + (v_k+1 - v_k) (theta* - theta_k) / (theta_k+1 -
+   theta_k); NaN where either end is NaN.  On columns whose theta increases strictly this is MetPy's interpolate_1d over theta.
+   Outputs: pressure, temperature and vars[0 ... 3] are dense (nlevel, ncol) arrays, level-major, each nullable, of the views'
+   dtype and mem; status is int32 per column, the OR over the column's targets.  Values do not depend on which other outputs
+   are asked for.  Host views are staged; strided device views are read in place.
+   opts NULL: from_below 1, max_iters 50, eps 1e-6.  XP_E_ARG: a NULL or mismatched view; nvar outside 0 ... 4 or a NULL variable
+   below nvar; vars[i] set for i >= nvar; nlevel outside 1 ... XP_ISEN_MAX_LEVELS; levels NULL, not finite or not strictly
+   increasing; max_iters < 1; eps not finite or <= 0; a NULL out or one whose dtype or mem differs from the views'. */
+enum { XP_ISEN_MAX_LEVELS = 64 };
+typedef struct {
+    int32_t from_below;       /* != 0: the lowest bracketing pair; 0: the highest */
+    int32_t max_iters;        /* Newton steps at most, >= 1 */
+    double eps;               /* |x_new - x| <= eps in ln p */
+} xp_isentropic_opts;
+typedef struct {
+    void *pressure, *temperature;   /* hPa, K; (nlevel, ncol) each */
+    void *vars[4];                  /* the further variables on the surfaces, (nlevel, ncol) each */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_NOT_CONVERGED, ncol */
+    int32_t dtype, mem;
+} xp_isentropic_out;
+int xp_isentropic_interpolation(const xp_view *pressure, const xp_view *temperature, int32_t nvar,
+                                const xp_view *const *variables, int32_t nlevel, const double *levels,
+                                const xp_isentropic_opts *opts, xp_isentropic_out *out, void *stream);
 
 /* metpy.calc.critical_angle per point [degrees]: the angle between a = (shear_u, shear_v), the 0-500 m ln p bulk shear, and
    b = (storm_u - surface_u, storm_v - surface_v), evaluated as atan2(|a x b|, a . b) -- mathematically MetPy's

@@ -28,7 +28,7 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
            'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
-           'xp_wind_layers', 'xp_thermo_layers', 'xp_sounding_indices', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
+           'xp_wind_layers', 'xp_thermo_layers', 'xp_sounding_indices', 'xp_isentropic_interpolation', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
            'xp_ncape', 'xp_ecape', 'xp_last_error')
 
 
@@ -205,6 +205,22 @@ class SoundingOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SOUNDING_OUT + ('status',)] + [('dtype', C.c_int32), ('mem', C.c_int32)]
 
 
+# xp_isentropic_interpolation: its options and (nlevel, ncol) outputs, its limits, and the status bit of a target whose
+# Newton iteration did not converge
+ST_NOT_CONVERGED = 256
+ISEN_MAX_LEVELS = 64
+ISEN_MAX_VARS = 4
+
+
+class IsentropicOpts(C.Structure):
+    _fields_ = [('from_below', C.c_int32), ('max_iters', C.c_int32), ('eps', C.c_double)]
+
+
+class IsentropicOut(C.Structure):
+    _fields_ = [('pressure', C.c_void_p), ('temperature', C.c_void_p), ('vars', C.c_void_p * ISEN_MAX_VARS),
+                ('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)]
+
+
 # xp_ncape: its per-column outputs; xp_ecape: its per-point inputs and outputs
 NCAPE_OUT = ('ncape', 'lfc_height', 'el_height', 'status')
 ECAPE_IN = ('cape', 'ncape', 'el_height', 'sr_u', 'sr_v')
@@ -277,6 +293,8 @@ ARGTYPES = {
     'xp_thermo_layers': (_V, _V, _V, _V, _i32, C.POINTER(WindLayer), C.POINTER(_ptr), C.POINTER(_ptr),
                          C.POINTER(ThermoLayersOut), _ptr),
     'xp_sounding_indices': (_V, _V, _V, _V, _V, C.POINTER(SoundingOpts), C.POINTER(SoundingOut), _ptr),
+    'xp_isentropic_interpolation': (_V, _V, _i32, C.POINTER(_V), _i32, C.POINTER(_f64), C.POINTER(IsentropicOpts),
+                                    C.POINTER(IsentropicOut), _ptr),
     'xp_critical_angle': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_corfidi_storm_motion': (_i64, _i32, _i32) + (_ptr,) * 9,
     'xp_significant_tornado_effective': (_i64, _i32, _i32) + (_ptr,) * 8,
@@ -327,11 +345,12 @@ THERMO_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 # (104-111 VGPRs without a spill).
 CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 # The sounding-indices kernel (csrc/xp_sounding.hpp) takes no flag: 59-84 VGPRs without winds, 81-105 with them, no scratch.
+# The isentropic-interpolation kernel (csrc/xp_isentropic.hpp) takes none either: 50-52 VGPRs without extras, 86-87 with them, no scratch.
 UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
          ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),
-         ('sounding', 'xp_sounding_tu.hip', [])] + [
+         ('sounding', 'xp_sounding_tu.hip', []), ('isentropic', 'xp_isentropic_tu.hip', [])] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

@@ -1,6 +1,6 @@
 // xp_level_reader.hpp -- how the lifting kernels read a column's levels, once: LevelReader, the pointer walk with a one-level
 // look-ahead of k_cape_cin (xp_kernels.hpp) and the fused kernel (xp_multi.hpp), and LookAhead, the simpler indexed
-// look-ahead of the parcel searches and the effective inflow layer (xp_effective.hpp).
+// look-ahead of the parcel searches and the effective inflow layer (xp_effective.hpp), with LookAhead2, its two-view sibling.
 // Both keep the look-ahead values in the INPUT type until they are used: converting an fp32 value at the load makes the
 // wavefront wait for the load right there, and the prefetch hides nothing (it made every fp32 kernel run without any
 // prefetch).  None of this is arithmetic: float -> double is exact wherever it happens.
@@ -20,6 +20,20 @@ template <typename T> struct LookAhead {
     template <typename I> XP_DEV void take(I next, I nlev, double &P, double &T_, double &M_) {
         P = (double)p; T_ = (double)t; M_ = (double)m;
         if (next < nlev) request(next);
+    }
+};
+
+// The same for the kernels that read pressure and temperature alone (xp_isentropic.hpp), whose walk may also run downward:
+// the caller names the level to request next and says whether the column has it.
+template <typename T> struct LookAhead2 {
+    const View &pv, &tv;
+    const int64_t c;
+    T p, t;
+    XP_DEV LookAhead2(const View &pv_, const View &tv_, int64_t c_, int64_t k0) : pv(pv_), tv(tv_), c(c_) { request(k0); }
+    XP_DEV void request(int64_t k) { p = ldr<T>(pv, k, c); t = ldr<T>(tv, k, c); }
+    XP_DEV void take(int64_t next, bool more, double &P, double &T_) {
+        P = (double)p; T_ = (double)t;
+        if (more) request(next);
     }
 };
 

@@ -22,13 +22,17 @@
 #include "xp_wind_layers.hpp"
 #include "xp_thermo_layers.hpp"
 #include "xp_sounding.hpp"
+#include "xp_isentropic.hpp"
 #include "xp_ecape.hpp"
 #include "xp_per_point.hpp"
 
 static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_ST_LCL_NOT_CONVERGED &&
               xp::ST_NAN_PRESSURE == XP_ST_NAN_PRESSURE && xp::ST_BAD_PRESSURE == XP_ST_BAD_PRESSURE &&
               xp::ST_NO_LAYER == XP_ST_NO_LAYER && xp::ST_BAD_HEIGHT == XP_ST_BAD_HEIGHT &&
-              xp::ST_LAYER_OPEN == XP_ST_LAYER_OPEN && xp::ST_NO_CCL == XP_ST_NO_CCL, "the kernels' status bits are the ABI's");
+              xp::ST_LAYER_OPEN == XP_ST_LAYER_OPEN && xp::ST_NO_CCL == XP_ST_NO_CCL &&
+              xp::ST_NOT_CONVERGED == XP_ST_NOT_CONVERGED, "the kernels' status bits are the ABI's");
+static_assert(xp::ISEN_MAX_LEVELS == XP_ISEN_MAX_LEVELS && xp::ISEN_MAX_VARS == sizeof(xp_isentropic_out::vars) / sizeof(void *),
+              "the isentropic kernel's limits are the ABI's");
 static_assert(xp::CCL_TOP == XP_CCL_TOP && xp::CCL_BOTTOM == XP_CCL_BOTTOM, "the kernel's CCL choices are the ABI's");
 static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
               xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
@@ -1360,6 +1364,53 @@ int xp_sounding_indices(const xp_view *p, const xp_view *t, const xp_view *td, c
     a.tb = ts.tb; a.es_tab = ts.es;
     const int ccl = !want_ccl ? xp::CCL_NONE : opts.ccl_mixed_layer_depth > 0.0 ? xp::CCL_MIXED : xp::CCL_SURFACE;
     xp::launch_sounding(a, p->dtype == XP_F64, wind, ccl, st.s);
+    return st.finish();
+}
+
+int xp_isentropic_interpolation(const xp_view *p, const xp_view *t, int32_t nvar, const xp_view *const *variables, int32_t nlevel,
+                                const double *levels, const xp_isentropic_opts *o, xp_isentropic_out *out, void *stream) {
+    const char *const entry = "xp_isentropic_interpolation";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}}))) return rc;
+    if (nvar < 0 || nvar > xp::ISEN_MAX_VARS) return fail(XP_E_ARG, "%s: nvar must lie in 0 ... 4, got %d", entry, (int)nvar);
+    if (nvar > 0 && !variables) return fail(XP_E_ARG, "%s: variables: null", entry);
+    for (int i = 0; i < nvar; ++i) {
+        char name[32];
+        snprintf(name, sizeof(name), "variables[%d]", i);
+        if ((rc = check_views({{p, "pressure"}, {variables[i], name}}))) return rc;
+        if (variables[i]->mem != p->mem) return fail(XP_E_ARG, "%s: %s: mem differs from pressure's", entry, name);
+    }
+    if (t->mem != p->mem) return fail(XP_E_ARG, "%s: temperature: mem differs from pressure's", entry);
+    if ((rc = check_out(entry, out, p))) return rc;
+    for (int i = nvar; i < xp::ISEN_MAX_VARS; ++i)
+        if (out->vars[i]) return fail(XP_E_ARG, "%s: out: vars[%d] is set, but nvar is %d", entry, i, (int)nvar);
+    if (nlevel < 1 || nlevel > xp::ISEN_MAX_LEVELS)
+        return fail(XP_E_ARG, "%s: nlevel must lie in 1 ... %d, got %d", entry, xp::ISEN_MAX_LEVELS, (int)nlevel);
+    if (!levels) return fail(XP_E_ARG, "%s: levels: null", entry);
+    xp::IsentropicLevels lv;
+    memset(&lv, 0, sizeof(lv));
+    for (int j = 0; j < nlevel; ++j) {
+        if (!std::isfinite(levels[j])) return fail(XP_E_ARG, "%s: levels[%d] is not finite", entry, j);
+        if (j > 0 && !(levels[j] > levels[j - 1])) return fail(XP_E_ARG, "%s: levels must increase strictly (levels[%d])", entry, j);
+        lv.v[j] = levels[j];
+    }
+    xp_isentropic_opts opts = {1, 50, 1e-6};
+    if (o) opts = *o;
+    if (opts.max_iters < 1) return fail(XP_E_ARG, "%s: max_iters must be >= 1, got %d", entry, (int)opts.max_iters);
+    if (!(std::isfinite(opts.eps) && opts.eps > 0.0)) return fail(XP_E_ARG, "%s: eps must be finite and positive", entry);
+    const size_t lb = rows_bytes(p, nlevel);
+    xp::IsentropicArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t))) return rc;
+    for (int i = 0; i < nvar; ++i)
+        if ((rc = stage_view(st, variables[i], &a.v[i])) || (rc = st.out(out->vars[i], lb, out->mem, &a.vars[i]))) return rc;
+    if ((rc = st.out(out->pressure, lb, out->mem, &a.pressure)) || (rc = st.out(out->temperature, lb, out->mem, &a.temperature)) ||
+        (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = p->nlev; a.ncol = p->ncol; a.nlevel = nlevel;
+    a.from_below = opts.from_below != 0; a.max_iters = opts.max_iters; a.eps = opts.eps;
+    xp::launch_isentropic(a, lv, p->dtype == XP_F64, st.s);
     return st.finish();
 }
 

@@ -1241,6 +1241,63 @@ def ccl(pressure, temperature, dewpoint, mixed_layer_depth=None, which='top'):
     return tuple(res[k] for k in L.SOUNDING_CCL_OUT)
 
 
+def _on_grid(pressure, like):
+    """A 1-D pressure of nlev values (isobaric data) on the (nlev, ...) grid of `like`, in pressure's own space."""
+    shape = tuple(like.shape)
+    col = (-1,) + (1,) * (len(shape) - 1)
+    if _is_torch(pressure):
+        return pressure.reshape(col).expand(shape)
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(pressure).reshape(col), shape))
+
+
+def isentropic_interpolation(levels, pressure, temperature, *args, temperature_out=False, max_iters=50, eps=1e-6,
+                             bottom_up_search=True, status=False):
+    """metpy.calc.isentropic_interpolation of every column (xp_isentropic_interpolation; include/xparcel.h has the rules and
+    the three deliberate differences from MetPy): pressure [hPa] -- (nlev, ...) or, for isobaric data, the nlev values --
+    temperature [K] and any further variables `args` on the same vertical are put onto the surfaces of potential temperature
+    `levels` [K].  Returns MetPy's list: the pressure, the temperature if `temperature_out`, one array per arg and, with
+    status=True, the int32 per-column status (XP_ST_NO_LAYER: some target has no bracketing pair in the column;
+    ST_NOT_CONVERGED: some target's Newton iteration took max_iters steps without meeting eps; such targets are NaN).  Each
+    array is (nlevel,) + the horizontal shape, in the inputs' space.  levels are sorted ascending, as MetPy does, and the
+    outputs come in that order; duplicates are rejected.  bottom_up_search: the lowest bracketing pair (True) or the highest.
+    More than 64 levels or 4 args are served by consecutive calls of at most that many."""
+    lev = np.sort(np.asarray(levels, dtype=np.float64).reshape(-1))
+    assert lev.size >= 1 and np.all(np.isfinite(lev)), 'levels must be finite, at least one'
+    assert np.all(np.diff(lev) > 0), 'levels must not hold duplicates'
+    assert int(max_iters) >= 1, 'max_iters must be at least 1'
+    assert np.isfinite(eps) and eps > 0, 'eps must be finite and positive'
+    if len(np.shape(pressure)) == 1 and len(np.shape(temperature)) > 1:
+        assert np.shape(pressure)[0] == np.shape(temperature)[0], 'a 1-D pressure must have one value per level'
+        pressure = _on_grid(pressure, temperature)
+    c = _Call(pressure, temperature, *args)
+    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, temperature and the further variables must share a shape'
+    views, n = [c.view(a) for a in c.ins], len(lev)
+    shape = (n,) + c.hshape
+    p_out, t_out = c.out(shape), c.out(shape) if temperature_out else None
+    v_out = [c.out(shape) for _ in args]
+    st_out = None
+    opts = L.IsentropicOpts(int(bool(bottom_up_search)), int(max_iters), float(eps))
+    for i0 in range(0, max(len(args), 1), L.ISEN_MAX_VARS):
+        vs = views[2 + i0:2 + i0 + L.ISEN_MAX_VARS]
+        vptrs = (C.POINTER(L.View) * len(vs))(*[C.pointer(v) for v in vs]) if vs else None
+        for j0 in range(0, n, L.ISEN_MAX_LEVELS):
+            j1 = min(n, j0 + L.ISEN_MAX_LEVELS)
+            out = L.IsentropicOut(dtype=c.xp_dtype, mem=c.mem)
+            for q in range(len(vs)):
+                out.vars[q] = _ptr(v_out[i0 + q][j0:j1])
+            if i0 == 0:                                       # the pressure, the temperature and the status come from the first call
+                out.pressure = _ptr(p_out[j0:j1])
+                if temperature_out:
+                    out.temperature = _ptr(t_out[j0:j1])
+                part = c.out(c.hshape, np.int32)
+                out.status = _ptr(part)
+            c.run('xp_isentropic_interpolation', views[0], views[1], len(vs), vptrs, j1 - j0, (C.c_double * (j1 - j0))(*lev[j0:j1]),
+                  opts, out)
+            if i0 == 0:
+                st_out = part if st_out is None else st_out | part
+    return [p_out] + ([t_out] if temperature_out else []) + v_out + ([st_out] if status else [])
+
+
 def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure):
     """The buoyancy-dilution potential NCAPE of entraining CAPE (Peters et al. 2023) for every column (xp_ncape): the integral
     over height, between the LFC and the EL, of -(g / (cp T)) (hbar - hs) of the ENVIRONMENT -- hbar the mean moist static
