@@ -723,6 +723,64 @@ int xp_isentropic_interpolation(const xp_view *pressure, const xp_view *temperat
                                 const xp_view *const *variables, int32_t nlevel, const double *levels,
                                 const xp_isentropic_opts *opts, xp_isentropic_out *out, void *stream);
 
+/* Hydrostatic heights and layer thickness from pressure, temperature and humidity (metpy.calc.thickness_hydrostatic, accumulated
+   level by level; the reference has no counterpart): the height of every valid level of every column and the thickness of up to
+   four layers by pressure, in ONE upward pass.  Parity with MetPy itself is UNPINNED: MetPy is not installed where this library is
+   tested, and the tests hold the kernel to a NumPy restatement of the rules below only (tests/hydrostatic_restatement.py).  One
+   deliberate difference from MetPy: the moisture is given as dewpoint or as specific humidity, not as mixing ratio.
+   Inputs: pressure [hPa] and temperature [K] as (nlev, ncol) views of one shape, dtype and mem, level 0 lowest, pressure
+   decreasing; moisture on the same vertical, same shape, dtype and mem, nullable: dewpoint [K] with XP_HUM_DEWPOINT, specific
+   humidity [kg/kg] with XP_HUM_SPECIFIC (opts->humidity; opts NULL: XP_HUM_DEWPOINT); NULL: a dry atmosphere, Tv = T.
+   base_height, nullable: ncol values [m] in the views' dtype and mem, the height of each column's lowest valid level; NULL: 0,
+   i.e. heights above the lowest valid level, the convention of every height bound in this library.  A NaN element makes that
+   column's heights NaN and sets no status bit.  f32 inputs are converted exactly; all arithmetic is fp64, without contraction.
+   Valid levels: p, T and the supplied moisture are all non-NaN.  Invalid levels are dropped: their height is NaN and nothing
+   is interpolated through them.  p0: the pressure of the lowest valid level.
+   Virtual temperature of a point (p, T, moisture): Tv = T (w + eps) / (eps (1 + w)) -- MetPy's form, xp_downdraft_cape's, not the
+   reference's 0.608 form -- with w = eps e / (p - e), e = e_s(Td) by Bolton's formula (as everywhere in the library) from a
+   dewpoint, w = q / (1 - q) from a specific humidity (no dewpoint in between), w = 0 without moisture.
+   Heights: x = ln p.  The lowest valid level gets base_height; every further valid level b after the previous valid level a
+       z_b = z_a + (Rd / g) * (0.5 * (Tv_a + Tv_b)) * (x_a - x_b),      Rd = 287.04749097718457, g = 9.80665,
+   in that operation order: the trapezoid of Tv over ln p, level by level.
+   Layer thickness: nlayer in 0 ... 4 xp_wind_layer structs of kind XP_LAYER_PRESSURE or XP_LAYER_PRESSURE_DEPTH, with the
+   vocabulary and the points of xp_thermo_layers: a NaN bottom is p0; a NaN top with XP_LAYER_PRESSURE is open, to the highest
+   valid level; the points are the valid levels with pt <= p <= pb (close counting as inside) plus pb and pt themselves where no
+   selected level is close to them.  At an added bound point T and the moisture are each linear in ln p between the levels on
+   either side, and Tv is evaluated FROM THE INTERPOLATED values.  thickness[j] is the sum of the same (Rd / g) * (0.5 * (Tv_a +
+   Tv_b)) * (x_a - x_b) terms over consecutive points of the layer, from 0 at its first point: it does not depend on
+   base_height, and a layer of one point has thickness 0.  A layer with pt >= pb, with pb > p0 or with pt below the smallest
+   valid pressure gets NaN and the column XP_ST_NO_LAYER; other layers are unaffected.
+   Ordering and empty columns: the whole column is always read.  A valid level whose pressure is not below the previous valid
+   level's sets XP_ST_BAD_PRESSURE (alone: no layer is judged); heights from that level upward are NaN, and so is every thickness
+   of the column.  A column without a valid level gets all NaN and XP_ST_NO_LAYER.
+   Outputs: height is dense (nlev, ncol), level-major, nullable; thickness[j] ncol values each, nullable; status int32 per
+   column, nullable; all in the views' dtype and mem.  Values do not depend on which other outputs are asked for.  Host views
+   are staged; strided device views are read in place; a device call stages nothing and synchronises nothing.
+   XP_E_ARG: a NULL or mismatched pressure or temperature; a moisture of another shape, dtype or mem; an unknown humidity;
+   nlayer outside 0 ... 4, or layers NULL with nlayer > 0; a layer of kind XP_LAYER_HEIGHT or of an unknown kind; a depth <= 0 or
+   not finite, an infinite bound; thickness[j] set for j >= nlayer; a NULL out, or one whose dtype or mem differs from the
+   views'. */
+typedef struct {
+    int32_t humidity;         /* XP_HUM_*: what the moisture view holds */
+    int32_t reserved;         /* 0 */
+} xp_hydrostatic_opts;
+typedef struct {
+    void *height;             /* m; (nlev, ncol) */
+    void *thickness[4];       /* m; ncol each, per layer */
+    int32_t *status;          /* XP_ST_NO_LAYER | XP_ST_BAD_PRESSURE, ncol */
+    int32_t dtype, mem;
+} xp_hydrostatic_out;
+int xp_hydrostatic_height(const xp_view *pressure, const xp_view *temperature, const xp_view *moisture,
+                          const void *base_height, int32_t nlayer, const xp_wind_layer *layers,
+                          const xp_hydrostatic_opts *opts, xp_hydrostatic_out *out, void *stream);
+
+/* metpy.calc.geopotential_to_height and height_to_geopotential per point, with Re = 6371008.7714 m (metpy.constants.Re) and
+   g = 9.80665: height [m] = (geopotential * Re) / (g * Re - geopotential); geopotential [m^2 s^-2] = (g * Re * height) /
+   (Re + height), each in that operation order, without contraction.  NaN propagates.  n elements of dtype in mem each; no
+   argument may be NULL. */
+int xp_geopotential_to_height(int64_t n, int32_t dtype, int32_t mem, const void *geopotential, void *out, void *stream);
+int xp_height_to_geopotential(int64_t n, int32_t dtype, int32_t mem, const void *height, void *out, void *stream);
+
 /* metpy.calc.critical_angle per point [degrees]: the angle between a = (shear_u, shear_v), the 0-500 m ln p bulk shear, and
    b = (storm_u - surface_u, storm_v - surface_v), evaluated as atan2(|a x b|, a . b) -- mathematically MetPy's
    arccos(a . b / (|a| |b|)), but well conditioned near 0 and 180 degrees, where that form can leave [-1, 1] by rounding.

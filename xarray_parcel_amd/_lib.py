@@ -28,7 +28,8 @@ SYMBOLS = ('xp_version', 'xp_init', 'xp_set_tables', 'xp_tables_loaded', 'xp_fam
            'xp_trap_around_zeros', 'xp_bound_pressure', 'xp_get_layer', 'xp_shift_out_nans', 'xp_rebase_profile', 'xp_interp1d',
            'xp_wind_shear', 'xp_significant_hail_parameter', 'xp_storm_proxies', 'xp_bunkers_storm_motion',
            'xp_storm_relative_helicity', 'xp_storm_relative_helicity_layers', 'xp_significant_tornado', 'xp_supercell_composite',
-           'xp_wind_layers', 'xp_thermo_layers', 'xp_sounding_indices', 'xp_isentropic_interpolation', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
+           'xp_wind_layers', 'xp_thermo_layers', 'xp_sounding_indices', 'xp_isentropic_interpolation', 'xp_hydrostatic_height',
+           'xp_geopotential_to_height', 'xp_height_to_geopotential', 'xp_critical_angle', 'xp_corfidi_storm_motion', 'xp_significant_tornado_effective',
            'xp_ncape', 'xp_ecape', 'xp_last_error')
 
 
@@ -221,6 +222,21 @@ class IsentropicOut(C.Structure):
                 ('status', C.c_void_p), ('dtype', C.c_int32), ('mem', C.c_int32)]
 
 
+# xp_hydrostatic_height: what its moisture view holds (the header's XP_HUM_*), its options and outputs; the layers are
+# xp_wind_layers' by pressure (a NaN top: to the highest valid level)
+HUM_DEWPOINT, HUM_SPECIFIC = 0, 1
+HYDRO_MAX_LAYERS = 4
+
+
+class HydrostaticOpts(C.Structure):
+    _fields_ = [('humidity', C.c_int32), ('reserved', C.c_int32)]
+
+
+class HydrostaticOut(C.Structure):
+    _fields_ = [('height', C.c_void_p), ('thickness', C.c_void_p * HYDRO_MAX_LAYERS), ('status', C.c_void_p),
+                ('dtype', C.c_int32), ('mem', C.c_int32)]
+
+
 # xp_ncape: its per-column outputs; xp_ecape: its per-point inputs and outputs
 NCAPE_OUT = ('ncape', 'lfc_height', 'el_height', 'status')
 ECAPE_IN = ('cape', 'ncape', 'el_height', 'sr_u', 'sr_v')
@@ -295,6 +311,10 @@ ARGTYPES = {
     'xp_sounding_indices': (_V, _V, _V, _V, _V, C.POINTER(SoundingOpts), C.POINTER(SoundingOut), _ptr),
     'xp_isentropic_interpolation': (_V, _V, _i32, C.POINTER(_V), _i32, C.POINTER(_f64), C.POINTER(IsentropicOpts),
                                     C.POINTER(IsentropicOut), _ptr),
+    'xp_hydrostatic_height': (_V, _V, _V, _ptr, _i32, C.POINTER(WindLayer), C.POINTER(HydrostaticOpts),
+                              C.POINTER(HydrostaticOut), _ptr),
+    'xp_geopotential_to_height': (_i64, _i32, _i32) + (_ptr,) * 3,
+    'xp_height_to_geopotential': (_i64, _i32, _i32) + (_ptr,) * 3,
     'xp_critical_angle': (_i64, _i32, _i32) + (_ptr,) * 8,
     'xp_corfidi_storm_motion': (_i64, _i32, _i32) + (_ptr,) * 9,
     'xp_significant_tornado_effective': (_i64, _i32, _i32) + (_ptr,) * 8,
@@ -346,11 +366,22 @@ THERMO_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 # The sounding-indices kernel (csrc/xp_sounding.hpp) takes no flag: 59-84 VGPRs without winds, 81-105 with them, no scratch.
 # The isentropic-interpolation kernel (csrc/xp_isentropic.hpp) takes none either: 50-52 VGPRs without extras, 86-87 with them, no scratch.
+# The hydrostatic kernel (csrc/xp_hydrostatic.hpp), instantiated on dtype x {dry, dewpoint, specific humidity} x the number of
+# layers (0 ... 4): no instantiation spills with or without machine LICM, but as in the other LayerGate kernels the flag keeps the
+# fp64 constants of flog / fexp out of the level loop's registers (12 to 21 VGPRs fewer in every instantiation, a wave per SIMD
+# more in most layered ones; on 64 x 1 Mi f64 the four-layer call 0.845 ms instead of 0.968, heights alone unchanged).
+# VGPRs, waves per SIMD with the flag, by the number of layers 0 / 1 / 2 / 3 / 4:
+#   f64 dry       39, 8 / 58, 8 / 77, 6 / 85, 5 /  94, 5      f32 dry       38, 8 / 56, 8 / 75, 6 / 83, 5 /  92, 5
+#   f64 dewpoint  45, 8 / 67, 7 / 84, 5 / 92, 5 / 101, 4      f32 dewpoint  42, 8 / 64, 8 / 81, 5 / 89, 5 /  98, 4
+#   f64 specific  45, 8 / 68, 7 / 87, 5 / 95, 5 / 104, 4      f32 specific  44, 8 / 66, 7 / 85, 5 / 93, 5 / 102, 4
+# (without it 50-61 / 72-88 / 91-104 / 99-112 / 108-122); no LDS, no scratch.
+HYDROSTATIC_FLAGS = ['-mllvm', '-disable-machine-licm']
 UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
          ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),
-         ('sounding', 'xp_sounding_tu.hip', []), ('isentropic', 'xp_isentropic_tu.hip', [])] + [
+         ('sounding', 'xp_sounding_tu.hip', []), ('isentropic', 'xp_isentropic_tu.hip', []),
+         ('hydrostatic', 'xp_hydrostatic_tu.hip', HYDROSTATIC_FLAGS)] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

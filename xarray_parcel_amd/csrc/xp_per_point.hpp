@@ -1,12 +1,13 @@
 // xp_per_point.hpp -- the per-point products: ONE kernel, k_per_point, instantiated on the operation.  An operation names its
 // inputs and outputs (NIN <= 6, NOUT <= 4) and maps the values of one point, as doubles, through the product's value function,
-// which lives with the kernels it belongs to (xp_bundle.hpp, xp_kinematics.hpp, xp_wind_layers.hpp, xp_ecape.hpp) and keeps MetPy's / the
+// which lives with the kernels it belongs to (xp_bundle.hpp, xp_kinematics.hpp, xp_wind_layers.hpp, xp_ecape.hpp, xp_hydrostatic.hpp) and keeps MetPy's / the
 // reference's operation order under fp contract(off).  have[i]: input i was given (an input an entry point lets be null).
 #pragma once
 #include "xp_bundle.hpp"
 #include "xp_kinematics.hpp"
 #include "xp_wind_layers.hpp"
 #include "xp_ecape.hpp"
+#include "xp_hydrostatic.hpp"
 
 namespace xp {
 
@@ -67,6 +68,14 @@ struct StpEffectiveOp {                                  // xp_significant_torna
 struct EcapeOp {                                         // xp_ecape: cape, ncape, el_height, sr_u, sr_v -> ecape, ecape_a, psi
     static constexpr int NIN = 5, NOUT = 3;
     static XP_DEV void apply(const double *x, const bool *, double *y) { ecape_value(x[0], x[1], x[2], x[3], x[4], y); }
+};
+struct GeopotentialToHeightOp {                          // xp_geopotential_to_height
+    static constexpr int NIN = 1, NOUT = 1;
+    static XP_DEV void apply(const double *x, const bool *, double *y) { y[0] = geopotential_to_height_value(x[0]); }
+};
+struct HeightToGeopotentialOp {                          // xp_height_to_geopotential
+    static constexpr int NIN = 1, NOUT = 1;
+    static XP_DEV void apply(const double *x, const bool *, double *y) { y[0] = height_to_geopotential_value(x[0]); }
 };
 
 }  // namespace xp

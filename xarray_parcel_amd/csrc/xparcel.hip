@@ -23,6 +23,7 @@
 #include "xp_thermo_layers.hpp"
 #include "xp_sounding.hpp"
 #include "xp_isentropic.hpp"
+#include "xp_hydrostatic.hpp"
 #include "xp_ecape.hpp"
 #include "xp_per_point.hpp"
 
@@ -33,6 +34,8 @@ static_assert(xp::ST_TOP_NAN == XP_ST_TOP_NAN && xp::ST_LCL_NOT_CONVERGED == XP_
               xp::ST_NOT_CONVERGED == XP_ST_NOT_CONVERGED, "the kernels' status bits are the ABI's");
 static_assert(xp::ISEN_MAX_LEVELS == XP_ISEN_MAX_LEVELS && xp::ISEN_MAX_VARS == sizeof(xp_isentropic_out::vars) / sizeof(void *),
               "the isentropic kernel's limits are the ABI's");
+static_assert(xp::HY_MAX_LAYERS == sizeof(xp_hydrostatic_out::thickness) / sizeof(void *) && xp::HY_DEWPOINT == XP_HUM_DEWPOINT + 1 &&
+              xp::HY_SPECIFIC == XP_HUM_SPECIFIC + 1, "the hydrostatic kernel's limits and moisture kinds follow the ABI's");
 static_assert(xp::CCL_TOP == XP_CCL_TOP && xp::CCL_BOTTOM == XP_CCL_BOTTOM, "the kernel's CCL choices are the ABI's");
 static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
               xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
@@ -1412,6 +1415,52 @@ int xp_isentropic_interpolation(const xp_view *p, const xp_view *t, int32_t nvar
     a.from_below = opts.from_below != 0; a.max_iters = opts.max_iters; a.eps = opts.eps;
     xp::launch_isentropic(a, lv, p->dtype == XP_F64, st.s);
     return st.finish();
+}
+
+int xp_hydrostatic_height(const xp_view *p, const xp_view *t, const xp_view *m, const void *base_height, int32_t nlayer,
+                          const xp_wind_layer *layers, const xp_hydrostatic_opts *o, xp_hydrostatic_out *out, void *stream) {
+    const char *const entry = "xp_hydrostatic_height";
+    Entry st(stream);
+    if (st.rc) return st.rc;
+    int rc;
+    if ((rc = check_views({{p, "pressure"}, {t, "temperature"}}))) return rc;
+    if (t->mem != p->mem) return fail(XP_E_ARG, "%s: temperature: mem differs from pressure's", entry);
+    if (m && (rc = check_views({{p, "pressure"}, {m, "moisture"}}))) return rc;
+    if (m && m->mem != p->mem) return fail(XP_E_ARG, "%s: moisture: mem differs from pressure's", entry);
+    xp_hydrostatic_opts opts = {XP_HUM_DEWPOINT, 0};
+    if (o) opts = *o;
+    if (opts.humidity != XP_HUM_DEWPOINT && opts.humidity != XP_HUM_SPECIFIC)
+        return fail(XP_E_ARG, "%s: humidity must be XP_HUM_DEWPOINT or XP_HUM_SPECIFIC, got %d", entry, (int)opts.humidity);
+    if ((rc = check_out(entry, out, p))) return rc;
+    if (nlayer < 0 || nlayer > xp::HY_MAX_LAYERS) return fail(XP_E_ARG, "%s: nlayer must lie in 0 ... 4, got %d", entry, (int)nlayer);
+    if (nlayer > 0 && !layers) return fail(XP_E_ARG, "%s: layers: null", entry);
+    for (int i = nlayer; i < xp::HY_MAX_LAYERS; ++i)
+        if (out->thickness[i]) return fail(XP_E_ARG, "%s: out: thickness[%d] is set, but nlayer is %d", entry, i, (int)nlayer);
+    xp::HydrostaticArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nlayer; ++i) {
+        const xp_wind_layer &l = layers[i];
+        if (l.kind == XP_LAYER_HEIGHT) return fail(XP_E_ARG, "%s: layers[%d]: a layer by height is not served here", entry, i);
+        if ((rc = check_layer(entry, i, l, false, nullptr, nullptr, true, &a.bottom[i], &a.top[i]))) return rc;
+        a.kind[i] = l.kind; a.open[i] = l.kind == XP_LAYER_PRESSURE && std::isnan(a.top[i]);
+    }
+    const size_t cb = rows_bytes(p, 1);
+    if ((rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) || (m && (rc = stage_view(st, m, &a.m))) ||
+        (rc = st.in(base_height, cb, p->mem, &a.base)) || (rc = st.out(out->height, rows_bytes(p, p->nlev), out->mem, &a.height))) return rc;
+    for (int i = 0; i < nlayer; ++i)
+        if ((rc = st.out(out->thickness[i], cb, out->mem, &a.thickness[i]))) return rc;
+    if ((rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
+    a.nlev = p->nlev; a.ncol = p->ncol; a.n = nlayer;
+    xp::launch_hydrostatic(a, p->dtype == XP_F64, m ? opts.humidity + 1 : xp::HY_DRY, st.s);
+    return st.finish();
+}
+
+int xp_geopotential_to_height(int64_t n, int32_t dtype, int32_t mem, const void *geopotential, void *out, void *stream) {
+    return per_point<xp::GeopotentialToHeightOp>("xp_geopotential_to_height", n, dtype, mem, {geopotential}, 1, {out}, true, stream);
+}
+
+int xp_height_to_geopotential(int64_t n, int32_t dtype, int32_t mem, const void *height, void *out, void *stream) {
+    return per_point<xp::HeightToGeopotentialOp>("xp_height_to_geopotential", n, dtype, mem, {height}, 1, {out}, true, stream);
 }
 
 int xp_critical_angle(int64_t n, int32_t dtype, int32_t mem, const void *shear_u, const void *shear_v, const void *surface_u,

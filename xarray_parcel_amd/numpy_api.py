@@ -1298,6 +1298,89 @@ def isentropic_interpolation(levels, pressure, temperature, *args, temperature_o
     return [p_out] + ([t_out] if temperature_out else []) + v_out + ([st_out] if status else [])
 
 
+def _hydro_layer(spec):
+    """One layer of hydrostatic() as (kind, bottom, top) of xp_wind_layer: _wind_layer's layers by pressure, and for
+    {'bottom': ..., 'top': ...} / ('pressure', bottom, top) top=None, to the highest valid level."""
+    if isinstance(spec, dict) and 'top' in spec and spec['top'] is None:
+        spec = dict(spec, top=float('nan'))
+    elif not isinstance(spec, dict) and len(spec) == 3 and spec[0] == 'pressure' and spec[2] is None:
+        spec = (spec[0], spec[1], float('nan'))
+    kind, bottom, top = _wind_layer(spec)
+    assert kind != L.LAYER_HEIGHT, 'hydrostatic: layers are given by pressure (the heights are what the call computes)'
+    return kind, bottom, top
+
+
+def hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, base_height=None, layers=(), want=None):
+    """Hydrostatic heights and layer thickness of every column in one pass (xp_hydrostatic_height; include/xparcel.h has the
+    rules): pressure [hPa] -- (nlev, ...) or, for isobaric data, the nlev values -- temperature [K] and, for the virtual
+    temperature, EITHER dewpoint [K] OR specific_humidity [kg/kg] on the same vertical (neither: a dry atmosphere).
+    base_height [m]: the height of each column's lowest valid level, a scalar or one value per column; None: 0, heights above
+    the lowest valid level.  `layers`: up to four layers by pressure as in thermo_layers -- {'bottom': 1000, 'top': 500},
+    {'depth': 150} (the lowest 150 hPa), {'bottom': None, 'top': None} (the whole column).  Returns a dict: 'height' (nlev, ...)
+    [m], NaN at invalid levels; 'thickness', a list of one per-column array per layer [m], NaN where the column does not span
+    the layer; the per-column 'status' (XP_ST_NO_LAYER: some layer is not spanned, or the column has no valid level;
+    XP_ST_BAD_PRESSURE: a level out of order, the heights from it upward and every thickness NaN) -- or those of them that
+    `want` names.  Values do not depend on what else is asked for."""
+    assert dewpoint is None or specific_humidity is None, 'give dewpoint or specific_humidity, not both'
+    specs = [_hydro_layer(s) for s in layers]
+    n = len(specs)
+    assert n <= L.HYDRO_MAX_LAYERS, 'layers: at most four layers'
+    keys = ('height', 'thickness', 'status') if want is None else tuple(want)
+    assert set(keys) <= {'height', 'thickness', 'status'}, 'want: unknown output'
+    if len(np.shape(pressure)) == 1 and len(np.shape(temperature)) > 1:
+        assert np.shape(pressure)[0] == np.shape(temperature)[0], 'a 1-D pressure must have one value per level'
+        pressure = _on_grid(pressure, temperature)
+    moisture = dewpoint if dewpoint is not None else specific_humidity
+    c = _Call(pressure, temperature, *(() if moisture is None else (moisture,)), *([base_height] if _is_torch(base_height) else []))
+    ins = c.ins[:2 if moisture is None else 3]
+    assert all(a.shape == ins[0].shape for a in ins), 'pressure, temperature and the moisture must share a shape'
+    res = {}
+    out = L.HydrostaticOut(dtype=c.xp_dtype, mem=c.mem)
+    if 'height' in keys:
+        res['height'] = c.out((c.nlev,) + c.hshape)
+        out.height = _ptr(res['height'])
+    if 'thickness' in keys:
+        res['thickness'] = [c.out(c.hshape) for _ in range(n)]
+        for i, a in enumerate(res['thickness']):
+            out.thickness[i] = _ptr(a)
+    if 'status' in keys:
+        res['status'] = c.out(c.hshape, np.int32)
+        out.status = _ptr(res['status'])
+    base = None if base_height is None else c.per_col(base_height)
+    opts = L.HydrostaticOpts(L.HUM_SPECIFIC if specific_humidity is not None else L.HUM_DEWPOINT, 0)
+    views = [c.view(a) for a in ins] + [None]
+    c.run('xp_hydrostatic_height', *views[:3], base, n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]) if n else None,
+          opts, out)
+    return res
+
+
+def hydrostatic_height(pressure, temperature, dewpoint=None, specific_humidity=None, base_height=None, status=False):
+    """The hydrostatic height [m] of every level of every column, (nlev, ...): base_height (None: 0) at the lowest valid level,
+    then the trapezoid of the virtual temperature over ln p, level by level (MetPy's thickness_hydrostatic accumulated);
+    NaN at invalid levels.  Arguments as hydrostatic(); with status=True the int32 per-column status follows."""
+    res = hydrostatic(pressure, temperature, dewpoint, specific_humidity, base_height, want=('height', 'status') if status else ('height',))
+    return (res['height'], res['status']) if status else res['height']
+
+
+def thickness_hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, bottom=None, depth=None):
+    """metpy.calc.thickness_hydrostatic for every column [m]: the hydrostatic thickness of the layer from `bottom` [hPa; None:
+    the lowest valid level] up `depth` [hPa; None: to the highest valid level], the bounds interpolated in ln p where they lie
+    between levels (MetPy's get_layer).  One deviation from MetPy: the moisture is given as dewpoint [K] or as
+    specific_humidity [kg/kg], not as mixing_ratio; neither: a dry atmosphere.  NaN where the column does not span the layer."""
+    layer = ('pressure', bottom, None) if depth is None else ('pressure_depth', bottom, depth)
+    return hydrostatic(pressure, temperature, dewpoint, specific_humidity, layers=[layer], want=('thickness',))['thickness'][0]
+
+
+def geopotential_to_height(geopotential):
+    """metpy.calc.geopotential_to_height per point: geopotential [m^2/s^2] -> height [m] = (Phi Re) / (g Re - Phi)."""
+    return _per_point('xp_geopotential_to_height', [geopotential], (), 1)[0]
+
+
+def height_to_geopotential(height):
+    """metpy.calc.height_to_geopotential per point: height [m] -> geopotential [m^2/s^2] = (g Re z) / (Re + z)."""
+    return _per_point('xp_height_to_geopotential', [height], (), 1)[0]
+
+
 def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure):
     """The buoyancy-dilution potential NCAPE of entraining CAPE (Peters et al. 2023) for every column (xp_ncape): the integral
     over height, between the LFC and the EL, of -(g / (cp T)) (hbar - hs) of the ENVIRONMENT -- hbar the mean moist static
