@@ -601,6 +601,11 @@ struct Family {
     double s;              // the label's coordinate in psi-piece q
     int q;
     bool bad;
+    // locate() / value(): the NEXT x-piece of every lane, held while the lanes of the wavefront cross the boundary one by one
+    double c1[FAM_ND + 1]; // the column's polynomial on the piece after the one of c (valid while have1)
+    bool have1;            // wave-uniform: c1 is loaded
+    int on1;               // 1: this lane has moved on to c1 (only while have1; an int read through on(): as a bool it is
+                           // turned back into a lane mask at the top of every level, two instructions outside the rare branches)
 
     XP_DEV static int psi_piece(double psi) {
         return (int)(psi >= 245.0) + (int)(psi >= 262.0) + (int)(psi >= 275.0) + (int)(psi >= 285.0) + (int)(psi >= 293.0) +
@@ -608,7 +613,17 @@ struct Family {
     }
     XP_DEV static double x_mid(int j) { return FAM_XHI - FAM_WX * ((double)j + 0.5); }
     // c_n = sum_m A[j][n][m][q] s^m: nine reads in flight at a time
-    XP_DEV void load_piece(int j) {
+    XP_DEV void load_piece(int j) { load_piece_into(j, c, m4); }
+    // the m4 of the piece after c's (not kept: registers), as load_piece forms it; NaN on a poisoned lane
+    // (formed behind an asm barrier: left to itself the compiler computes it once per level ahead of the branches that want it)
+    XP_DEV bool on() const { int o = on1; asm volatile("" : "+v"(o)); return o != 0; }
+    XP_DEV double m4_next() const {
+        double m = m4;
+        asm volatile("" : "+v"(m));
+        const double jd = __builtin_rint(__builtin_fma(m, 0.5, FAM_XHI * (1.0 / FAM_WX) - 0.5));
+        return -(2.0 / FAM_WX) * (FAM_XHI - FAM_WX * ((jd + 1.0) + 0.5));
+    }
+    XP_DEV void load_piece_into(int j, double *cc, double &mm) const {
         const double *a = tab + (j * FAM_SJ + q);
 #pragma unroll
         for (int n = 0; n <= FAM_ND; ++n) {
@@ -621,9 +636,9 @@ struct Family {
 #pragma unroll
             for (int m = FAM_MD - 1; m >= 0; --m) v = __builtin_fma(v, s, k[m]);
             asm volatile("" : "+v"(v) : : "memory");     // this row is finished before the next row's reads are issued
-            c[n] = v;
+            cc[n] = v;
         }
-        m4 = -(2.0 / FAM_WX) * x_mid(j);
+        mm = -(2.0 / FAM_WX) * x_mid(j);
     }
     // the T with T (1 + 0.608 w_s(p, T)) = tv: five Newton steps from T0 = tv / (1 + 0.608 w_s(p, tv)) (1e-13 K wherever
     // e_s <= 0.1 p; oracle/family.py temperature_of).  Only the kernels that output or integrate the plain temperature pay it.
@@ -730,7 +745,7 @@ struct Family {
     // label of the adiabat through the LCL (x_lcl = ln p_lcl, t_lcl; tv_lcl its virtual temperature there) and the
     // coefficients of the x-piece the LCL is in
     XP_DEV void start(const double *table, const double *es, double p_lcl, double x_lcl, double t_lcl, double tv_lcl) {
-        tab = table; q = 0; s = 0.0; m4 = 0.0;
+        tab = table; q = 0; s = 0.0; m4 = 0.0; have1 = false; on1 = 0;
         bad = !(x_lcl >= FAM_XLO && x_lcl <= FAM_XHI) || isnan_(t_lcl);
         // coarse label: RK4 to ln 1000 in steps <= 0.25
         double dx = FAM_X1000 - x_lcl;
@@ -808,24 +823,82 @@ struct Family {
     // at() in two steps, for a caller that has other arithmetic to interleave with the Horner chain (eight dependent fp64 fma):
     // locate() makes sure the coefficients of X's piece are loaded and returns the piece-local coordinate; value() evaluates.
     // any_top (wave-uniform): some lane is above the table top -- only then value() looks at the per-lane `top`.
+    // A wavefront's lanes reach a piece boundary over several consecutive levels (unrelated neighbouring columns).  Reloading
+    // every lane at each of those levels -- what at() does -- costs one collapse (81 reads, 72 fma) per level in which somebody
+    // moves instead of one per piece.  So at the first such level every lane collapses the piece AFTER its own into c1
+    // (have1); while the wavefront is split a lane that has crossed (on1) takes c1 at z1 = 4 x + m4_next() and the others c at
+    // z -- value() evaluates both chains behind one wave-uniform branch and selects the RESULT per lane -- and when the last
+    // lane has crossed, c1 becomes c (nine moves).  The coefficients are a function of (piece, s, q) alone and z is formed from
+    // the piece's own m4 as in at(), so every lane gets the bits at() gives it, whatever its wave-mates do.
+    // Everything that is not "some lanes step into the next piece, the others stay" takes at()'s rule: every lane collapses the
+    // piece it is in now and the second set is given up -- a lane that skips a piece or goes back (coarse soundings, rising
+    // pressure), the table top, p > 1100 hPa, the whole wavefront moving at once (nothing to keep).  A poisoned lane (NaN in
+    // both sets) and a NaN X never move; poisoned lanes do not hold up the hand-over.
+    // Registers (these kernels sit at the 128-VGPR cap): ONE collapse in the code, always into c1, and one hand-over c1 -> c
+    // behind it -- with a second collapse straight into c the compiler kept both sets alive through it and spilled 12 VGPRs;
+    // the next piece's m4 is recomputed from m4 on the few split levels instead of being kept.
     XP_DEV double locate(double X, bool &top, bool &any_top) {
         double z = __builtin_fma(2.0 / FAM_WX, X, m4);
         top = false; any_top = false;
+        double z1 = z;
         bool move = (z <= -1.0) || (z > 1.0);
+        if (have1) {                                                                     // wave-uniform; on1 is false without it
+            z1 = __builtin_fma(2.0 / FAM_WX, X, m4_next());
+            asm volatile("" : "+v"(z1));                                                 // (stays behind the branch)
+            const double zc = on() ? z1 : z;
+            move = (zc <= -1.0) || (zc > 1.0);
+        }
         if (__builtin_amdgcn_ballot_w64(move) != 0ull) {
             double u = __builtin_fma(-(1.0 / FAM_WX), X, FAM_XHI * (1.0 / FAM_WX));
-            bool go = move;
-            if (go && u < 0.0) { bad = true; go = false; }
             int jn = (int)u;
-            top = go && jn > FAM_NPX - 1;
             int jcur = (int)__builtin_rint(__builtin_fma(m4, 0.5, FAM_XHI * (1.0 / FAM_WX) - 0.5));
-            int j = go ? (jn > FAM_NPX - 1 ? FAM_NPX - 1 : jn) : jcur;
-            load_piece(bad ? 0 : j);
-            if (bad) poison();
-            z = __builtin_fma(2.0 / FAM_WX, X, m4);
-            any_top = __builtin_amdgcn_ballot_w64(top) != 0ull;
+            // the plain step: from c's piece into the next one, inside the table
+            const bool was1 = on();
+            const bool step = move && !was1 && !(u < 0.0) && jn == jcur + 1 && jn <= FAM_NPX - 1;
+            const bool plain = __builtin_amdgcn_ballot_w64(move && !step) == 0ull;
+            bool hand;                                                                   // wave-uniform: c1 becomes c
+            double m4_new;
+            if (plain && have1) {
+                const bool now1 = was1 || move;
+                on1 = now1 ? 1 : 0;
+                hand = __builtin_amdgcn_ballot_w64(!now1 && !bad) == 0ull;                // the last lane has crossed
+                m4_new = m4_next();
+            } else {
+                // one collapse into the second set: every lane its next piece (`next`), or -- at()'s rule -- the piece it is in
+                // now, handed over at once
+                const bool next = plain && __builtin_amdgcn_ballot_w64(!move && !bad) != 0ull;
+                bool go = move && !next;
+                if (go && u < 0.0) { bad = true; go = false; }
+                top = go && jn > FAM_NPX - 1;
+                const int jhere = go ? jn : was1 ? jcur + 1 : jcur;
+                int j = next ? jcur + 1 : jhere;
+                j = j > FAM_NPX - 1 ? FAM_NPX - 1 : j;                                   // (a lane on the last piece never steps)
+                load_piece_into(bad ? 0 : j, c1, m4_new);
+                if (bad) { poison1(); m4_new = qnan(); }
+                have1 = next; on1 = (next && move) ? 1 : 0;
+                hand = !next;
+                any_top = __builtin_amdgcn_ballot_w64(top) != 0ull;
+            }
+            if (hand) {
+#pragma unroll
+                for (int n = 0; n <= FAM_ND; ++n) c[n] = c1[n];
+                m4 = m4_new;
+                z = __builtin_fma(2.0 / FAM_WX, X, m4);
+                have1 = false; on1 = 0;
+            }
         }
         return z;
+    }
+    // the value of locate()'s piece: `v` is the Horner chain of c at locate()'s z (evaluated by the caller)
+    XP_DEV double value(double v, double X) const {
+        if (have1) {                                                                     // wave-uniform
+            const double z1 = __builtin_fma(2.0 / FAM_WX, X, m4_next());
+            double w = c1[FAM_ND];
+#pragma unroll
+            for (int n = FAM_ND - 1; n >= 0; --n) w = __builtin_fma(w, z1, c1[n]);
+            v = on() ? w : v;
+        }
+        return v;
     }
     XP_DEV double top_value(double v, double X, bool top) const {           // (rare: the dry continuation above the table top)
         const double w = horner(-1.0);
@@ -855,6 +928,10 @@ struct Family {
             }
         }
         return horner(z);
+    }
+    XP_DEV void poison1() {
+#pragma unroll
+        for (int n = 0; n <= FAM_ND; ++n) c1[n] = qnan();
     }
     XP_DEV void poison() {
 #pragma unroll

@@ -365,7 +365,10 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
             tve = !need_w ? T_ : Q ? virt(T_, (m_ > 0.0 && m_ < 1.0) ? fdiv(m_, 1.0 - m_) : qnan()) : virt_env_tab(es, T_, m_, P, false);
             if (FAM_T) tpf = LAZY ? qnan() : Family::temperature_from2(es, P, tq, fam_off, fam_offp, false);
         }
-        if constexpr (TRIO) { if (f_any_top) tf = fam.top_value(tf, X, f_top); }
+        if constexpr (TRIO) {
+            tf = fam.value(tf, X);                                         // (a lane that is already on the next x-piece)
+            if (f_any_top) tf = fam.top_value(tf, X, f_top);
+        }
         double tp, tvp;
         if (FAMILY) {
             tvp = tf;
@@ -526,9 +529,13 @@ __global__ __launch_bounds__(XP_CAPE_THREADS, (XP_CAPE_THREADS >= 1024 ? 4 : MOD
             const double q = rd.peek_p();
             if (!isnan_(q)) { pm = (q < pm) ? q : pm; found = true; }
         }
+        // (the pressure view comes from the kernel arguments afresh, like the output pointers below: taken from `a`, the column's
+        // address in it is formed ahead of the level loop and occupies two registers all the way through it)
+        const auto late_in = late_kernargs<CapeArgs>();
+        const View top_p = {late_in->p.data, late_in->p.ls, late_in->p.cs};
         for (int kk = nlev - 1; kk >= (int)pc.first; --kk) {
             if (__ballot(!found) == 0ull) break;
-            const double q = ld<T>(a.p, kk, c);
+            const double q = ld<T>(top_p, kk, c);
             if (!found && !isnan_(q)) { pm = (q < pm) ? q : pm; found = true; }
         }
         sc.slot[SL_MIN_P * SLOT_STRIDE] = pm;
