@@ -8,6 +8,9 @@ of the primitives directly and run through the C ABI in tests/test_gpu_parity.py
 Tolerances: the kernels evaluate the reference's expressions in its operation order without FMA contraction, so values
 agree to the last bit of the library exp / log: 1e-12 relative here; NaN patterns, masks and integer results exactly;
 sums 1e-12 relative (NumPy's pairwise summation order differs).
+
+float32 results against the oracle, grids of one column and of one and two levels, class-by-class columns and strided
+device views: tests/test_gpu_primitive_grid.py (inputs: tests/primitive_cases.py).
 """
 import numpy as np
 import pytest

@@ -587,7 +587,9 @@ def crossing_level(x, a, value):
 
 # -- the reference's array primitives (pf.py:63-100, 164-227, 858-1064, 1200-1289, 1517-1555, 1604-1649, 1699-1720) --------
 # The CAPE / CIN kernels never build these arrays; the functions exist because the reference offers them to its callers.
-# Arrays are (nlev, ...) with the vertical first, datasets are dicts name -> array.
+# Arrays are (nlev, ...) with the vertical first, datasets are dicts name -> array.  One level is a valid column: outputs of
+# nlev - 1 rows then have zero rows (a zero-size buffer has no address: the library gets NULL for it and neither reads nor
+# writes it) -- find_intersections returns six empty arrays, trap_around_zeros one all-NaN row and a mask of ones, trapz 0.
 def insert_level(d, level, coords='pressure', fill_value=-999):
     """pf.py:933: insert `level` (dict name -> one value per column) into the dataset `d` sorted by decreasing `coords`;
     the keys of `level` define the output (pf.py:983)."""
