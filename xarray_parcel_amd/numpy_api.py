@@ -9,6 +9,12 @@ back with the horizontal shape of the input; profiles as (nlev+1, ...).  Returne
 containers are plain dicts -- the xarray-facing mirrors in parcel_functions.py
 wrap them into Datasets.
 
+With CUDA tensors for every array argument a function only enqueues work on torch's current stream and returns
+without waiting for it (tests/test_gpu_streams.py); from_most_unstable_parcel and mix_layer, whose output shape
+comes back from the device, are the exception; a Python scalar given for a per-column argument is uploaded
+with a blocking copy; and a call that takes internal scratch (moist='family') straight after another one can wait
+in the HIP runtime's hipFreeAsync while the stream is still busy, as conv_properties_composed's second parcel does.
+
 There is no CPU path here: every function ends in a kernel launch.
 """
 import ctypes as C
@@ -818,6 +824,8 @@ def _where(c, a, b):
     if _is_torch(c) or _is_torch(a) or _is_torch(b):
         dev = next(v.device for v in (c, a, b) if _is_torch(v))
         a = a if _is_torch(a) else torch.as_tensor(a, device=dev, dtype=torch.float64)
+        if np.ndim(b) == 0 and not _is_torch(b):
+            return torch.where(c, a, float(b))          # (a scalar goes in by value: uploading it would wait for the stream)
         b = b if _is_torch(b) else torch.as_tensor(b, device=dev, dtype=a.dtype)
         return torch.where(c, a, b.to(a.dtype))
     return np.where(c, a, b)
