@@ -17,7 +17,7 @@
  *     (k, c) of a view lives at data[k*lev_stride + c*col_stride] (strides in
  *     elements).  col_stride == 1 (the (lev, y, x) C-order layout) is the coalesced
  *     fast path; anything else is correct but slower;
- *   - dtype is XP_F32 or XP_F64 for data in memory; arithmetic is fp64;
+ *   - dtype is XP_F32 or XP_F64 for data in memory; arithmetic is fp64 (one exception, on request: xp_opts.compute);
  *   - mem says where a buffer lives: XP_MEM_DEVICE pointers are used in place,
  *     XP_MEM_HOST buffers are staged through internal device scratch (PCIe time
  *     is then part of the call);
@@ -136,10 +136,41 @@ typedef struct {
     int32_t pos_cape_neg_cin;               /* default 1 (pf.py:1293) */
     int32_t post_zero_cin;                  /* default 0 (pf.py:1293) */
     int32_t moist_mode;                     /* XP_MOIST_* */
-    int32_t compute;                        /* arithmetic type: XP_F64 (the only one implemented; XP_F32 is rejected with XP_E_ARG) */
+    int32_t compute;                        /* arithmetic type: XP_F64 (the default), or XP_F32 in xp_cape_cin's one case below */
     int32_t humidity;                       /* XP_HUM_*: what the `dewpoint` view of xp_cape_cin holds */
     int32_t flags;                          /* XP_OPT_* bits; 0 by default */
 } xp_opts;
+
+/* xp_opts.compute == XP_F32: fp32 arithmetic in the level walk of xp_cape_cin (csrc/xp_cape_f32.hpp).  Honoured in exactly
+   this case, and XP_E_ARG -- the message names the offending argument -- in every other one:
+     views      all three XP_F32, in host or device memory, dense or strided (staged like any other call);
+     parcel     parcel->mode == XP_PARCEL_SURFACE;
+     opts       moist_mode == XP_MOIST_FAMILY, humidity == XP_HUM_DEWPOINT, and virtual_temperature_correction, lcl_interp,
+                pos_cape_neg_cin, post_zero_cin at their defaults (1, XP_LCL_INTERP_LOG, 1, 0);
+     profile    NULL;
+     scalars    CAPE/CIN-only in the sense of xp_scalars_out below: lfc_temperature, el_temperature, lfc_index, el_index and
+                status all NULL.  Supported: cape, cin, lcl_pressure, lcl_temperature, lcl_virtual_temperature, lfc_pressure,
+                el_pressure, parcel_index, parcel_pressure, parcel_temperature, parcel_dewpoint.
+   Every other entry point that takes an xp_opts (xp_cape_cin_multi, xp_conv_properties, xp_effective_inflow_layer,
+   xp_cape_cin_layers) rejects XP_F32 with XP_E_ARG.  Nothing that passes XP_F64, or no opts, changes by a bit.
+   What fp32 arithmetic promises, against the same call with XP_F64:
+     (a) classification  the same decisions for every column: which levels are valid, where parcel minus environment
+                         changes sign, which crossing is the LFC and which the EL, whether they exist -- so cape, cin,
+                         lfc_pressure and el_pressure are NaN in the same columns.  A node whose fp32 difference is smaller
+                         than XP_F32_GUARD (4e-4 K, a derived bound on the fp32 error of that difference), the first node
+                         above the LCL where the LCL node's own difference is below 1e-5 of its (the XP_F64 path's tie
+                         window at the LCL), a node within 8e-6 (relative) of the LCL pressure, and every node at or below
+                         the LCL are evaluated in fp64 by the XP_F64 path's own code.  The bound is derived for levels with
+                         1 hPa <= p <= 1100 hPa, 150 K <= Td <= T <= 330 K, e_s(T) <= 0.1 p and a mixing ratio up to 0.04
+                         (csrc/xp_cape_f32.hpp); (a) and (b) are promised for columns whose levels lie inside that domain;
+     (b) values          cape and cin within 0.5 J/kg (measured: 0.02 J/kg); an LFC / EL that lies in the interval
+                         between the nodes a and b within 2 XP_F32_GUARD |ln p_b - ln p_a| / |y_b - y_a| + 2e-7 in ln p, y the
+                         parcel-minus-environment virtual temperature; an LFC on the LCL is the LCL bit for bit.
+   The LCL and parcel outputs are bit-identical: the column prologue (parcel, LCL, the adiabat's label) stays fp64.  Columns
+   the family table cannot serve are redone with XP_MOIST_EXACT in fp64, as for XP_F64.
+   Unlike XP_F64, the XP_F32 values of a column are NOT bitwise invariant under a permutation, a slicing or a sharding of
+   the columns: which of its nodes take the fp64 code depends on the 63 columns it shares a wavefront with.  The
+   classification (a) is invariant; cape, cin, lfc_pressure and el_pressure move within (b). */
 
 /* Per-column outputs; every pointer is nullable (not written when NULL).  Floating outputs have
    `dtype`, all buffers live in `mem`, ncol elements each.

@@ -16,6 +16,7 @@ PARCEL = {'surface': 0, 'most_unstable': 1, 'mixed_layer': 2, 'explicit': 3}
 MOIST = {'exact': 0, 'table': 1, 'family': 2}
 LCL_INTERP = {'linear': 0, 'log': 1}
 HUMIDITY = {'dewpoint': 0, 'specific': 1}
+COMPUTE = {'float32': XP_F32, 'float64': XP_F64}      # xp_opts.compute: the arithmetic type
 OPT_FUSE_PARCELS = 1
 ST_TOP_NAN, ST_LCL_NOT_CONVERGED, ST_NAN_PRESSURE, ST_BAD_PRESSURE = 1, 2, 4, 8
 
@@ -376,7 +377,11 @@ CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 #   f64 specific  45, 8 / 68, 7 / 87, 5 / 95, 5 / 104, 4      f32 specific  44, 8 / 66, 7 / 85, 5 / 93, 5 / 102, 4
 # (without it 50-61 / 72-88 / 91-104 / 99-112 / 108-122); no LDS, no scratch.
 HYDROSTATIC_FLAGS = ['-mllvm', '-disable-machine-licm']
-UNITS = [('xparcel', 'xparcel.hip', []), ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
+# The fp32-arithmetic surface CAPE / CIN kernel (csrc/xp_cape_f32.hpp, xp_opts.compute = XP_F32): the family units' workgroup
+# and flag (e_s / ln tables + the fp32 copy of the family table + the scan slots: 130.3 KB of LDS, one workgroup per CU).
+CAPE_F32_FLAGS = ['-DXP_CAPE_THREADS=1024', '-mllvm', '-disable-machine-licm']
+UNITS = [('xparcel', 'xparcel.hip', []), ('cape_f32', 'xp_cape_f32_tu.hip', CAPE_F32_FLAGS),
+         ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
          ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),

@@ -13,6 +13,7 @@
 
 #include "../../include/xparcel.h"
 #include "xp_kernels.hpp"
+#include "xp_cape_f32.hpp"
 #include "xp_multi.hpp"
 #include "xp_bundle.hpp"
 #include "xp_dcape.hpp"
@@ -432,12 +433,14 @@ xp_opts default_opts() {
     o.virtual_temperature_correction = 1; o.lcl_interp = XP_LCL_INTERP_LOG; o.pos_cape_neg_cin = 1; o.compute = XP_F64;
     return o;
 }
-int check_opts(const xp_opts &o) {
+// f32_ok: the caller implements xp_opts.compute == XP_F32 (xp_cape_cin alone, which then holds the call to check_compute32)
+int check_opts(const xp_opts &o, bool f32_ok = false) {
     if (o.lcl_interp != XP_LCL_INTERP_LINEAR && o.lcl_interp != XP_LCL_INTERP_LOG)
         return fail(XP_E_INTERP, "interpolator must be linear or log");
     if (o.moist_mode != XP_MOIST_EXACT && o.moist_mode != XP_MOIST_TABLE && o.moist_mode != XP_MOIST_FAMILY)
         return fail(XP_E_ARG, "bad moist_mode");
-    if (o.compute != XP_F64) return fail(XP_E_ARG, "xp_opts.compute: only XP_F64 arithmetic is implemented");
+    if (o.compute != XP_F64 && !(f32_ok && o.compute == XP_F32))
+        return fail(XP_E_ARG, o.compute == XP_F32 ? "xp_opts.compute: XP_F32 arithmetic is implemented by xp_cape_cin only" : "xp_opts.compute: XP_F32 or XP_F64");
     if (o.humidity != XP_HUM_DEWPOINT && o.humidity != XP_HUM_SPECIFIC) return fail(XP_E_ARG, "bad xp_opts.humidity");
     return 0;
 }
@@ -449,11 +452,11 @@ int check_parcel(const xp_parcel *parcel) {
     return 0;
 }
 // the arguments of the CAPE family: p / T / Td, each of np parcels, the options
-int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o) {
+int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o, bool f32_ok = false) {
     if (int rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) return rc;
     for (int i = 0; i < np; ++i)
         if (int rc = check_parcel(parcels + i)) return rc;
-    return check_opts(o);
+    return check_opts(o, f32_ok);
 }
 
 // the CAPE family's p / T / Td, options and tables, staged once per call however many parcels it lifts
@@ -497,9 +500,9 @@ int set_parcel(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeAr
     return 0;
 }
 int fill_common(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
-                const xp_opts &o, xp::CapeArgs *a) {
+                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false) {
     int rc;
-    if ((rc = check_cape(p, t, td, 1, parcel, o)) || (rc = stage_cape(st, p, t, td, o, a)) || (rc = set_parcel(st, *parcel, p, a)))
+    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok)) || (rc = stage_cape(st, p, t, td, o, a)) || (rc = set_parcel(st, *parcel, p, a)))
         return rc;
     return 0;
 }
@@ -542,6 +545,29 @@ void cape_pass(const Stager &st, xp::CapeArgs a, int dtype, int mode, bool profi
     a.flags = flags;
     a.persist = flags && persist(mode, a.ncol);
     by_dtype(dtype, [&](auto z) { launch_cape_pm<decltype(z)>(a, mode, profile, st.s); });
+}
+
+// xp_opts.compute == XP_F32 is honoured in exactly one case (include/xparcel.h); every other one names what it is held to
+int check_compute32(const xp_view *p, const xp_parcel *parcel, const xp_opts &o, const xp_scalars_out *s, const xp_profile_out *profile) {
+    if (p->dtype != XP_F32) return fail(XP_E_ARG, "xp_opts.compute = XP_F32: the views must be XP_F32");
+    if (parcel->mode != XP_PARCEL_SURFACE) return fail(XP_E_ARG, "xp_opts.compute = XP_F32: parcel->mode must be XP_PARCEL_SURFACE");
+    if (o.moist_mode != XP_MOIST_FAMILY) return fail(XP_E_ARG, "xp_opts.compute = XP_F32: moist_mode must be XP_MOIST_FAMILY");
+    if (o.humidity != XP_HUM_DEWPOINT) return fail(XP_E_ARG, "xp_opts.compute = XP_F32: humidity must be XP_HUM_DEWPOINT");
+    if (!o.virtual_temperature_correction || o.lcl_interp != XP_LCL_INTERP_LOG || !o.pos_cape_neg_cin || o.post_zero_cin)
+        return fail(XP_E_ARG, "xp_opts.compute = XP_F32: virtual_temperature_correction, lcl_interp, pos_cape_neg_cin and post_zero_cin must be at their defaults");
+    if (profile) return fail(XP_E_ARG, "xp_opts.compute = XP_F32: profile must be NULL");
+    if (s && (s->lfc_temperature || s->el_temperature || s->lfc_index || s->el_index || s->status))
+        return fail(XP_E_ARG, "xp_opts.compute = XP_F32: scalars->lfc_temperature, el_temperature, lfc_index, el_index and status must be NULL");
+    return 0;
+}
+// the fp32-arithmetic pass (csrc/xp_cape_f32.hpp), then RK4 for the columns the family table cannot serve, as cape_pass
+void cape_pass32(const Stager &st, xp::CapeArgs a, int32_t *flags) {
+    if (a.ncol == 0) return;
+    a.flags = flags;
+    a.persist = persist(XP_PARCEL_SURFACE, a.ncol);
+    xp::launch_cape_f32(a, st.s);
+    a.only_flagged = 1; a.persist = 0;
+    xp::launch_cape_mode<float, 0>(a, xp::PM_SURFACE, false, st.s);
 }
 
 template <typename T, int NV> void launch_interp_levels(int nt, const Stager &st, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg) {
@@ -721,9 +747,12 @@ int xp_cape_cin(const xp_view *p, const xp_view *t, const xp_view *td, const xp_
     xp::CapeArgs a;
     int32_t *flags;
     int rc;
-    if ((rc = fill_common(st, p, t, td, parcel, oo, &a)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
+    const bool f32 = oo.compute == XP_F32;                   // (held to its contract before anything is staged or looked up)
+    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
+    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
         (rc = family_flags(st, oo, a.ncol, &flags))) return rc;
-    cape_pass(st, a, p->dtype, parcel->mode, profile != nullptr, flags);
+    if (f32) cape_pass32(st, a, flags);
+    else cape_pass(st, a, p->dtype, parcel->mode, profile != nullptr, flags);
     return st.finish();
 }
 

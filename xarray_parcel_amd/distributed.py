@@ -47,9 +47,12 @@ def sharded_cape_cin(pressure, temperature, dewpoint, names=('cape', 'cin'), dst
                      **kwargs):
     """Each rank passes ITS slab (nlev, rows_local, nx) (or already flattened (nlev, ncol_local)); results for
     the whole grid arrive on `dst`.  `compute` defaults to the HIP path (numpy_api.cape_cin_columns); the CPU
-    rehearsal test injects a stand-in."""
-    if compute is None:
+    rehearsal test injects a stand-in.  A string -- 'float32' or 'float64' -- is the HIP path's own compute= keyword
+    (the arithmetic of the level walk) and is handed on to it with the other keywords."""
+    if compute is None or isinstance(compute, str):
         from . import numpy_api
+        if compute is not None:
+            kwargs['compute'] = compute
         compute = numpy_api.cape_cin_columns
     res = compute(pressure, temperature, dewpoint, want=tuple(names), **kwargs)
     local = {k: torch.as_tensor(res[k]).reshape(-1) for k in names}

@@ -134,15 +134,40 @@ class _Call:
 
 
 def _opts(virtual_temperature_correction=True, lcl_interp='log', pos_cape_neg_cin=True, post_zero_cin=False,
-          moist='exact', humidity='dewpoint'):
+          moist='exact', humidity='dewpoint', compute='float64'):
     if lcl_interp not in L.LCL_INTERP:
         raise AssertionError('interpolator must be linear or log')          # pf.py:878
     assert humidity in L.HUMIDITY, "humidity must be 'dewpoint' or 'specific'"
+    assert compute in L.COMPUTE, "compute must be 'float64' or 'float32'"
     return L.Opts(int(bool(virtual_temperature_correction)), L.LCL_INTERP[lcl_interp], int(bool(pos_cape_neg_cin)),
-                  int(bool(post_zero_cin)), L.MOIST[moist], L.XP_F64, L.HUMIDITY[humidity], 0)
+                  int(bool(post_zero_cin)), L.MOIST[moist], L.COMPUTE[compute], L.HUMIDITY[humidity], 0)
 
 
-_DEFAULT = {'moist': 'exact'}
+_DEFAULT = {'moist': 'exact', 'compute': 'float64'}
+
+# what a compute='float32' call can return (include/xparcel.h at xp_opts.compute): everything but the LFC / EL temperatures,
+# the interval indices and the status word
+COMPUTE32_WANT = ('cape', 'cin', 'lcl_pressure', 'lcl_temperature', 'lcl_virtual_temperature', 'lfc_pressure', 'el_pressure',
+                  'parcel_index', 'parcel_pressure', 'parcel_temperature', 'parcel_dewpoint')
+
+
+def set_compute(mode):
+    """The arithmetic of the CAPE / CIN level walk: 'float64' (the default) or 'float32' (fp32 arithmetic above the LCL,
+    same classification of every column, CAPE / CIN within 0.5 J/kg: include/xparcel.h at xp_opts.compute).  A preference:
+    it applies to the calls the fp32 kernel covers -- cape_cin_columns on float32 arrays, surface parcel, moist='family',
+    dewpoint input, default options, no profile, no lifted index, `want` within COMPUTE32_WANT (or None) -- and every
+    other call runs in fp64 as before.  The keyword compute='float32' of a call is strict instead: it raises XParcelError
+    where the kernel does not apply."""
+    assert mode in L.COMPUTE
+    _DEFAULT['compute'] = mode
+
+
+def _compute32_applies(c, parcel, moist, want, want_profile, lifted_index_at, kwargs):
+    return (c.xp_dtype == L.XP_F32 and parcel == 'surface' and moist == 'family' and not want_profile and
+            lifted_index_at is None and (want is None or all(k in COMPUTE32_WANT for k in want)) and
+            kwargs.get('humidity', 'dewpoint') == 'dewpoint' and bool(kwargs.get('virtual_temperature_correction', True)) and
+            kwargs.get('lcl_interp', 'log') == 'log' and bool(kwargs.get('pos_cape_neg_cin', True)) and
+            not kwargs.get('post_zero_cin', False))
 
 
 def set_moist_lapse(mode):
@@ -153,18 +178,28 @@ def set_moist_lapse(mode):
 
 
 def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=None, parcel_values=None,
-                     want_profile=False, want=None, moist=None, lifted_index_at=None, **kwargs):
+                     want_profile=False, want=None, moist=None, lifted_index_at=None, compute=None, **kwargs):
     """pf.py:1394-1475 with the three drivers.  Returns a dict of per-column arrays (and 'profile').
     want_profile: True for the six profile arrays of pf.py:806-931, or an iterable of their names for a subset (the ones
     not named are neither allocated nor written: lifted_index needs three of the six).
     lifted_index_at: a pressure [hPa] (the reference: 500): 'lifted_index' (pf.py:1722) of the lifted profile comes back
     with the scalars, computed in the same pass -- no profile array has to exist for it.
     humidity='specific' (keyword): `dewpoint` holds specific humidity [kg/kg] and is converted on load
-    (parcel_test.py:262-266 fused into the pass)."""
+    (parcel_test.py:262-266 fused into the pass).
+    compute='float32': the level walk above the LCL in fp32 arithmetic (float32 arrays, surface parcel, moist='family',
+    default options, no profile; `want` then defaults to COMPUTE32_WANT); raises where that kernel does not apply.  None:
+    the module default (set_compute), which falls back to fp64 where it does not."""
     c = _Call(pressure, temperature, dewpoint)
     p, t, td = c.ins
     assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-    o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
+    moist = moist or _DEFAULT['moist']
+    if compute is None:
+        compute = _DEFAULT['compute']
+        if compute == 'float32' and not _compute32_applies(c, parcel, moist, want, want_profile, lifted_index_at, kwargs):
+            compute = 'float64'
+    if compute == 'float32' and want is None:
+        want = COMPUTE32_WANT
+    o = _opts(moist=moist, compute=compute, **kwargs)
     if depth is None:
         depth = 300.0 if parcel == 'most_unstable' else 100.0                # pf.py:1558, 1652
     pc = L.Parcel(L.PARCEL[parcel], 0, float(depth), None, None, None)
@@ -237,7 +272,8 @@ def cape_cin(pressure, temperature, dewpoint, parcel_temperature, parcel_pressur
 
 
 def surface_based_cape_cin(pressure, temperature, dewpoint, **kwargs):
-    """pf.py:1477."""
+    """pf.py:1477.  It returns the profile, which the fp32 walk does not produce: compute='float32' always raises here, and
+    a set_compute('float32') preference leaves it in fp64 (cape_cin_columns(parcel='surface') is the call that takes it)."""
     return _split(cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', want_profile=True, **kwargs))
 
 
