@@ -173,7 +173,13 @@ typedef struct {
    classification (a) is invariant; cape, cin, lfc_pressure and el_pressure move within (b). */
 
 /* Per-column outputs; every pointer is nullable (not written when NULL).  Floating outputs have
-   `dtype`, all buffers live in `mem`, ncol elements each.
+   `dtype`, all buffers live in `mem`, ncol elements each.  `dtype` and `mem` are this struct's own: for xp_cape_cin,
+   xp_cape_cin_multi (per parcel), xp_lfc_el, xp_select_parcel and xp_rebase_profile they need not match the views' (fp32
+   grids with fp64 CAPE / CIN, device grids with host scalars, ...); a value is the fp64 result rounded once to `dtype`.
+   Anything but XP_F32 / XP_F64 and XP_MEM_HOST / XP_MEM_DEVICE is XP_E_ARG.  The other output structs below
+   (xp_dcape_out, xp_effective_layer_out, xp_cape_layers_out, xp_storm_motion_out, xp_srh_out, xp_srh_layers_out,
+   xp_wind_layers_out, xp_thermo_layers_out, xp_sounding_out, xp_isentropic_out, xp_hydrostatic_out, xp_ncape_out) must
+   match the views' dtype and mem: XP_E_ARG otherwise.
    lfc_index / el_index: index i of the interval (levels i, i+1 of the LCL-augmented profile)
    that holds the chosen crossing; -1 = none; lfc_index -2 = LFC replaced by the LCL (pf.py:1161-1185).
    parcel_index: source level of the lifted parcel (0 for surface, MU level for most-unstable, -1 otherwise).
@@ -192,7 +198,11 @@ typedef struct {
 /* Optional lifted profile with the LCL inserted as an extra level (pf.py:806-931): six
    (nlev_out, ncol) arrays, nlev_out >= nlev + 1.  For MU / ML parcels the profile is re-based
    (levels below the parcel removed, pf.py:1551-1553, 1636-1644) and padded with NaN on top.  Any of the six
-   pointers may be NULL: that array is not written (lifted_index, pf.py:1722, reads three of them). */
+   pointers may be NULL: that array is not written (lifted_index, pf.py:1722, reads three of them).  `dtype` and `mem`
+   are the profile's own: they need not match the views', nor the xp_scalars_out's of the same call.  Element (j, c) of
+   each array lives at [j*lev_stride + c*col_stride]; a device profile may have any non-negative strides (padded rows,
+   column-major, every second column: only the addressed elements are written), a host profile must be dense
+   (lev_stride == ncol, col_stride == 1); negative strides are XP_E_ARG. */
 typedef struct {
     void *pressure, *temperature, *virtual_temperature;                 /* parcel */
     void *environment_temperature, *environment_virtual_temperature, *environment_dewpoint;
@@ -940,7 +950,8 @@ int xp_shift_out_nans(const xp_view *name, const xp_view *variable, void *out, v
    mixed layer are masked, levels left without a value in every column of the grid are dropped (dropna(how='all')),
    every column is shifted onto its first remaining level and, for the mixed layer, the parcel is put underneath.
    out_*: (nlev [+ 1 for the mixed layer], ncol), rows >= *nlev_out NaN; parcel: parcel_pressure / temperature /
-   dewpoint / parcel_index of xp_scalars_out (nullable, dtype / mem of the views); level_kept (nullable, HOST, nlev
+   dewpoint / parcel_index of xp_scalars_out (nullable, in its own dtype / mem; the parcel row of out_* does not depend
+   on them); level_kept (nullable, HOST, nlev
    int32): 1 for every input level that survived the drop.  *nlev_out (HOST) = rows in use.  Synchronises the stream. */
 int xp_rebase_profile(const xp_view *pressure, const xp_view *temperature, const xp_view *dewpoint, const xp_parcel *parcel,
                       void *out_pressure, void *out_temperature, void *out_dewpoint, xp_scalars_out *parcel_out,

@@ -263,6 +263,7 @@ void k_rebase_select(CapeArgs a, double *thr, int32_t *level_any) {
     Parcel pc = choose_parcel<T, false>(a, PMODE, c, es, a.depth);
     st(a.s.par_p, a.s.f64, c, pc.p); st(a.s.par_t, a.s.f64, c, pc.t); st(a.s.par_td, a.s.f64, c, pc.td);
     sti(a.s.parcel_idx, c, pc.idx);
+    if (PMODE == PM_ML) { thr[a.ncol + c] = pc.p; thr[2 * a.ncol + c] = pc.t; thr[3 * a.ncol + c] = pc.td; }   // for pass 2
     double t = pc.p;                                                       // MU: keep p <= p_parcel (pf.py:1551)
     if (PMODE == PM_ML) {                                                  // ML: keep p < max(p) - depth (pf.py:1636)
         double pmax = qnan();
@@ -285,7 +286,7 @@ void k_rebase_write(CapeArgs a, const double *thr, const int32_t *level_any, int
     const double t = thr[c];
     int64_t j = 0;
     if (PMODE == PM_ML) {                                                  // pf.py:1641-1644
-        st(o.p, f64, c, ld1<T>(a.s.par_p, c)); st(o.t, f64, c, ld1<T>(a.s.par_t, c)); st(o.td, f64, c, ld1<T>(a.s.par_td, c));
+        st(o.p, f64, c, thr[a.ncol + c]); st(o.t, f64, c, thr[2 * a.ncol + c]); st(o.td, f64, c, thr[3 * a.ncol + c]);
         j = 1;
     }
     bool leading = true;

@@ -131,21 +131,17 @@ int xp_rebase_profile(const xp_view *p, const xp_view *t, const xp_view *td, con
     xp::CapeArgs a;
     int rc;
     if ((rc = fill_common(st, p, t, td, parcel, default_opts(), &a))) return rc;
-    if (parcel_out && (parcel_out->dtype != p->dtype || parcel_out->mem != p->mem))
-        return fail(XP_E_ARG, "xp_rebase_profile: parcel_out must have the dtype and mem of the views");
     const bool ml = parcel->mode == XP_PARCEL_MIXED_LAYER;
     const int64_t nlev = p->nlev, ncol = p->ncol, rows = nlev + (ml ? 1 : 0);
     xp_scalars_out none;
     memset(&none, 0, sizeof(none));
     none.dtype = p->dtype; none.mem = p->mem;
     if ((rc = stage_scalars(st, parcel_out ? parcel_out : &none, ncol, &a.s))) return rc;
-    // pass 2 reads the mixed-layer parcel back: give it scratch where the caller did not ask for it
-    void **need[3] = {&a.s.par_p, &a.s.par_t, &a.s.par_td};
-    for (int i = 0; i < 3; ++i)
-        if (!*need[i] && (rc = st.alloc(rows_bytes(p, 1) + 8, need[i]))) return rc;
+    // pass 2 reads the mixed-layer parcel back from scratch of its own (3 x ncol doubles behind the thresholds): the
+    // caller's parcel_out has a dtype of its own, and any of its pointers may be null
     double *thr;
     int32_t *any;
-    if ((rc = st.alloc((size_t)(ncol + 1) * 8, &thr)) || (rc = st.alloc((size_t)nlev * 4, &any))) return rc;
+    if ((rc = st.alloc((size_t)(4 * ncol + 1) * 8, &thr)) || (rc = st.alloc((size_t)nlev * 4, &any))) return rc;
     HIP_TRY(hipMemsetAsync(any, 0, (size_t)nlev * 4, st.s));
     xp::RebaseOut o;
     if ((rc = st.out(out_p, rows_bytes(p, rows), p->mem, &o.p)) || (rc = st.out(out_t, rows_bytes(p, rows), p->mem, &o.t)) ||

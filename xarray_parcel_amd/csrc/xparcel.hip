@@ -368,6 +368,7 @@ int stage_scalars(Stager &st, xp_scalars_out *s, int64_t ncol, xp::ScalarsOut *o
     memset(o, 0, sizeof(*o));
     if (!s) { o->f64 = 1; return 0; }
     if (s->dtype != XP_F32 && s->dtype != XP_F64) return fail(XP_E_ARG, "scalars: bad dtype");
+    if (s->mem != XP_MEM_HOST && s->mem != XP_MEM_DEVICE) return fail(XP_E_ARG, "scalars: mem must be XP_MEM_HOST or XP_MEM_DEVICE");
     o->f64 = s->dtype == XP_F64;
     size_t fb = (size_t)ncol * esize(s->dtype), ib = (size_t)ncol * 4;
     int rc = 0;
@@ -511,7 +512,9 @@ int stage_cape_out(Stager &st, int dtype, xp_scalars_out *scalars, xp_profile_ou
     int rc;
     if ((rc = stage_scalars(st, scalars, a->ncol, &a->s)) || !profile) return rc;
     if (profile->dtype != XP_F32 && profile->dtype != XP_F64) return fail(XP_E_ARG, "profile: bad dtype");
+    if (profile->mem != XP_MEM_HOST && profile->mem != XP_MEM_DEVICE) return fail(XP_E_ARG, "profile: mem must be XP_MEM_HOST or XP_MEM_DEVICE");
     if (profile->nlev_out < a->nlev + 1) return fail(XP_E_ARG, "profile: nlev_out must be >= nlev + 1");
+    if (profile->lev_stride < 0 || profile->col_stride < 0) return fail(XP_E_ARG, "profile: lev_stride and col_stride must not be negative");
     if (profile->mem == XP_MEM_HOST && !(profile->col_stride == 1 && profile->lev_stride == a->ncol))
         return fail(XP_E_ARG, "profile: host arrays must be dense (nlev_out, ncol)");
     void *src[6] = {profile->pressure, profile->temperature, profile->virtual_temperature,
