@@ -442,6 +442,7 @@ int xp_mixing_ratio(const xp_view *temperature, const xp_view *dewpoint, const x
    dewpoint are blanked unless ignore_nans (pf.py:2097-2098).  Everything that is not parcel lifting is one pass over the four
    grids plus one per-point kernel (csrc/xp_bundle.hpp); scratch (the dewpoint array, per-point temporaries) is stream-ordered
    and internal.  The four (nlev, ncol) views share dtype and mem; the wind views are (nwind, ncol) on their own vertical;
+   all seven views live in one mem and the options are checked on an empty grid too (XP_E_ARG / XP_E_INTERP otherwise);
    surface winds and every output are ncol values of that dtype in that mem (positive_shear: int32 0 / 1); NULL outputs are
    skipped.  opts: moist_mode and the CAPE / CIN options of xp_cape_cin (humidity is ignored: the input IS specific humidity). */
 typedef struct {

@@ -321,27 +321,28 @@ LEVEL_CLASSES = ('between', 'on_level', 'duplicate_mean', 'duplicate_one_nan', '
                  'nan_coord_next') + COMMON
 
 
-def level_cases(nlev=cc.NLEV, ncol=cc.NCOL, seed=788):
-    """Coordinates (pressure) and four variables, built around LEVEL_TARGET: the class of a column says where that
-    coordinate falls in it ('duplicate_one_nan': one of the two values is NaN, in variables 0 and 2 or in variables 1 and 3,
-    alternating along the columns of the class).  'at' is the per-column form of the target: LEVEL_TARGET itself, except in the classes
-    'between' (the exact middle of two levels) and the COMMON ones (a random coordinate)."""
+def level_cases(nlev=cc.NLEV, ncol=cc.NCOL, seed=788, target=LEVEL_TARGET):
+    """Coordinates (pressure) and four variables, built around `target` (tests/bundle_cases.py asks for 850, 700 and 500
+    hPa in turn): the class of a column says where that coordinate falls in it ('duplicate_one_nan': one of the two
+    values is NaN, in variables 0 and 2 or in variables 1 and 3, alternating along the columns of the class).  'at' is the
+    per-column form of the target: `target` itself, except in the classes 'between' (the exact middle of two levels) and
+    the COMMON ones (a random coordinate)."""
     rng, p, t, td = _sounding(nlev, ncol, seed)
     z = q64(44330.0 * (1.0 - (p / 1013.25) ** 0.19))
     w = q64(rng.normal(size=(nlev, ncol)) * 10.0)
     cls = _classes(ncol, LEVEL_CLASSES)
-    at = np.full(ncol, LEVEL_TARGET)
+    at = np.full(ncol, float(target))
     for c in range(ncol):
         name = LEVEL_CLASSES[cls[c]]
-        j = int(np.argmin(np.abs(p[:, c] - LEVEL_TARGET)))                 # the level nearest the target
+        j = int(np.argmin(np.abs(p[:, c] - target)))                       # the level nearest the target
         jn = min(j + 1, nlev - 1)
         if name == 'between':
             k = int(rng.integers(max(nlev - 1, 1)))
             at[c] = 0.5 * (p[k, c] + p[min(k + 1, nlev - 1), c])
         elif name in ('on_level', 'duplicate_mean', 'duplicate_one_nan'):
-            p[j, c] = LEVEL_TARGET
+            p[j, c] = target
             if name != 'on_level':
-                p[jn, c] = LEVEL_TARGET                                      # two levels carry the coordinate
+                p[jn, c] = target                                            # two levels carry the coordinate
             if name == 'duplicate_one_nan':                                   # in two of the four variables, so that the
                 n = c // len(LEVEL_CLASSES)                                   # variables of one call average different counts
                 for v in ((t, z) if n % 2 else (td, w)):
@@ -349,9 +350,9 @@ def level_cases(nlev=cc.NLEV, ncol=cc.NCOL, seed=788):
         elif name == 'outside_below':
             p[:, c] = q64(p[:, c] * 0.25 + 100.0)                            # every coordinate below the target
         elif name == 'outside_above':
-            p[:, c] = q64(p[:, c] * 0.25 + 600.0)                            # every coordinate above it
+            p[:, c] = q64(p[:, c] * 0.25 + (target + 100.0))                   # every coordinate above it
         elif name == 'nan_coord_next':
-            below = np.nonzero(p[:, c] > LEVEL_TARGET)[0]
+            below = np.nonzero(p[:, c] > target)[0]
             k = int(below[-1]) if below.size else 0                          # the last level below the target: its bracket
             p[max(k - 1, 0) if c % 2 else min(k + 2, nlev - 1), c] = np.nan
         else:

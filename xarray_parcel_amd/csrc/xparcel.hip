@@ -818,16 +818,20 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
     int rc;
     if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {q, "specific_humidity"}, {z, "height_asl"}})) ||
         (rc = check_views({{wu, "wind_u"}, {wv, "wind_v"}, {wh, "wind_height_above_surface"}}))) return rc;
-    if (wu->ncol != p->ncol || wu->dtype != p->dtype || wu->mem != p->mem || t->mem != p->mem || q->mem != p->mem || z->mem != p->mem)
-        return fail(XP_E_ARG, "xp_conv_properties: the views must agree in columns, dtype and mem");
+    if (wu->ncol != p->ncol || wu->dtype != p->dtype)
+        return fail(XP_E_ARG, "xp_conv_properties: pressure/wind_u: views differ in columns or dtype");
+    // all seven views are staged with pressure's mem: every one of them must live there
+    for (const Arg &x : {Arg{t, "temperature"}, Arg{q, "specific_humidity"}, Arg{z, "height_asl"}, Arg{wu, "wind_u"}, Arg{wv, "wind_v"},
+                         Arg{wh, "wind_height_above_surface"}})
+        if (x.v->mem != p->mem) return fail(XP_E_ARG, "xp_conv_properties: pressure/%s: views differ in mem", x.name);
     if (!in->surface_wind_u || !in->surface_wind_v) return fail(XP_E_ARG, "xp_conv_properties: null surface wind");
     const int64_t nlev = p->nlev, ncol = p->ncol;
     const size_t cb = rows_bytes(p, 1);
     const int mem = p->mem;
-    if (ncol == 0) return XP_OK;
     xp_opts oo = o ? *o : default_opts();
     oo.humidity = XP_HUM_DEWPOINT;
     if ((rc = check_opts(oo))) return rc;
+    if (ncol == 0) return XP_OK;
     // inputs on the device (host views are dense by contract: staged as they are)
     xp_view dv[7];
     const xp_view *src[7] = {p, t, q, z, wu, wv, wh};
