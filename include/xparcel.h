@@ -51,6 +51,28 @@ enum { XP_MEM_HOST = 0, XP_MEM_DEVICE = 1 };
 
 /* which parcel is lifted (pf.py:1477 / 1557 / 1651 / 1394) */
 enum { XP_PARCEL_SURFACE = 0, XP_PARCEL_MOST_UNSTABLE = 1, XP_PARCEL_MIXED_LAYER = 2, XP_PARCEL_EXPLICIT = 3 };
+/* XP_PARCEL_OVER_GROUND, a flag OR-ed into xp_parcel.mode: the views are ISOBARIC levels -- what reanalyses and climate
+   archives deliver, with values extrapolated below the terrain -- and the surface comes separately: xp_parcel.pressure /
+   temperature / dewpoint hold ncol surface values each (hPa, K, K; the views' dtype and mem; the third is always a dewpoint,
+   as for explicit parcels, also under XP_HUM_SPECIFIC).  Valid with XP_PARCEL_SURFACE, XP_PARCEL_MOST_UNSTABLE and
+   XP_PARCEL_MIXED_LAYER; with XP_PARCEL_EXPLICIT, with any other bit, or with one of the three pointers NULL: XP_E_ARG.
+   The RE-BASED COLUMN of column c with the surface values ps, Ts, Tds has nlev + 1 rows:
+     k0 = the first level index with p[k0] < ps (plain comparison: a NaN pressure compares false and is dropped with the
+          levels below the ground; a level with p == ps is replaced by the surface);
+     row 0 = (ps, Ts, Tds);  row 1 + j = level k0 + j;  the remaining rows NaN in all three arrays;
+     no level above the ground: row 0 alone;  ps, Ts or Tds NaN: every row NaN.
+   With the flag the call IS the same call without it on the re-based (nlev + 1, ncol) arrays, bit for bit: every scalar,
+   every status bit, every profile row.  The parcel mode is mode & 3; parcel_index, lfc_index and el_index count re-based
+   rows; a profile needs nlev_out >= nlev + 2.  XP_HUM_SPECIFIC: the kept levels are converted as
+   xp_dewpoint_from_specific_humidity converts them (stored in the views' dtype) and the call equals that function followed
+   by the dewpoint-input call.  The views are read in place whatever their strides -- col_stride == 0 is a device pressure of
+   nlev isobars shared by all columns -- by one streaming kernel (csrc/xp_ground.hpp) that writes the re-based grid to
+   internal scratch: three (nlev + 1, ncol) arrays for the duration of the call.
+   Honoured by xp_cape_cin, xp_cape_cin_multi (every parcel flagged and carrying the same three pointers, or none: XP_E_ARG
+   otherwise; the grid is re-based once per call, XP_OPT_FUSE_PARCELS works on it like on any other) and xp_select_parcel.
+   xp_rebase_profile and xp_cape_cin_layers, whose outputs would change shape, reject it with XP_E_ARG;
+   xp_opts.compute = XP_F32 rejects it by its own rule (mode must be exactly XP_PARCEL_SURFACE). */
+enum { XP_PARCEL_OVER_GROUND = 16 };
 
 /* moist adiabat: XP_MOIST_EXACT integrates MetPy's pseudo-adiabat ODE (what the reference's
    KATs are run with, unit_tests.py:114-140) by RK4 in ln p with steps <= 0.1;
@@ -123,10 +145,11 @@ typedef struct {
 } xp_view;
 
 typedef struct {
-    int32_t mode;       /* XP_PARCEL_* */
+    int32_t mode;       /* XP_PARCEL_*, optionally | XP_PARCEL_OVER_GROUND */
     int32_t reserved;
     double depth;       /* hPa: MU search depth (default 300, pf.py:1558) / ML mixing depth (100, pf.py:1652) */
-    /* XP_PARCEL_EXPLICIT only: per-column parcel, ncol elements each, same dtype/mem as the views */
+    /* XP_PARCEL_EXPLICIT: the per-column parcel; XP_PARCEL_OVER_GROUND: the surface.  ncol elements each, same dtype/mem as
+       the views; unused otherwise */
     const void *pressure, *temperature, *dewpoint;
 } xp_parcel;
 

@@ -13,6 +13,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), 'include', 'xparcel.h')
 XP_F32, XP_F64 = 0, 1
 XP_MEM_HOST, XP_MEM_DEVICE = 0, 1
 PARCEL = {'surface': 0, 'most_unstable': 1, 'mixed_layer': 2, 'explicit': 3}
+PARCEL_OVER_GROUND = 16       # XP_PARCEL_OVER_GROUND: a flag on xp_parcel.mode (isobaric levels cut at the ground)
 MOIST = {'exact': 0, 'table': 1, 'family': 2}
 LCL_INTERP = {'linear': 0, 'log': 1}
 HUMIDITY = {'dewpoint': 0, 'specific': 1}

@@ -125,6 +125,7 @@ int xp_rebase_profile(const xp_view *p, const xp_view *t, const xp_view *td, con
                       void *out_td, xp_scalars_out *parcel_out, int32_t *level_kept, int64_t *nlev_out, void *stream) {
     Entry st(stream);
     if (st.rc) return st.rc;
+    if (parcel && over_ground(*parcel)) return check_parcel(parcel);             // (names the flag: the output's shape would change)
     if (!parcel || (parcel->mode != XP_PARCEL_MOST_UNSTABLE && parcel->mode != XP_PARCEL_MIXED_LAYER))
         return fail(XP_E_ARG, "xp_rebase_profile: mode must be most-unstable or mixed-layer");
     if (!nlev_out) return fail(XP_E_ARG, "xp_rebase_profile: null nlev_out");

@@ -15,6 +15,7 @@
 #include "xp_kernels.hpp"
 #include "xp_cape_f32.hpp"
 #include "xp_multi.hpp"
+#include "xp_ground.hpp"
 #include "xp_bundle.hpp"
 #include "xp_dcape.hpp"
 #include "xp_kinematics.hpp"
@@ -445,23 +446,46 @@ int check_opts(const xp_opts &o, bool f32_ok = false) {
     if (o.humidity != XP_HUM_DEWPOINT && o.humidity != XP_HUM_SPECIFIC) return fail(XP_E_ARG, "bad xp_opts.humidity");
     return 0;
 }
-int check_parcel(const xp_parcel *parcel) {
+// XP_PARCEL_OVER_GROUND: the flag on a surface / most-unstable / mixed-layer mode, and the parcel mode under it
+bool over_ground(const xp_parcel &parcel) {
+    return parcel.mode >= XP_PARCEL_OVER_GROUND && parcel.mode < (XP_PARCEL_OVER_GROUND | XP_PARCEL_EXPLICIT);
+}
+int parcel_mode(const xp_parcel &parcel) { return over_ground(parcel) ? parcel.mode & 3 : parcel.mode; }
+// ground_ok: the caller implements XP_PARCEL_OVER_GROUND (xp_cape_cin, xp_cape_cin_multi, xp_select_parcel)
+int check_parcel(const xp_parcel *parcel, bool ground_ok = false) {
     if (!parcel) return fail(XP_E_ARG, "parcel: null");
+    if (parcel->mode == (XP_PARCEL_OVER_GROUND | XP_PARCEL_EXPLICIT))
+        return fail(XP_E_ARG, "parcel: XP_PARCEL_OVER_GROUND does not combine with XP_PARCEL_EXPLICIT");
+    if (over_ground(*parcel)) {
+        if (!ground_ok) return fail(XP_E_ARG, "parcel: XP_PARCEL_OVER_GROUND is honoured by xp_cape_cin, xp_cape_cin_multi and xp_select_parcel only");
+        if (!parcel->pressure || !parcel->temperature || !parcel->dewpoint)
+            return fail(XP_E_ARG, "parcel: XP_PARCEL_OVER_GROUND needs the surface pressure, temperature and dewpoint arrays");
+        return 0;
+    }
     if (parcel->mode < XP_PARCEL_SURFACE || parcel->mode > XP_PARCEL_EXPLICIT) return fail(XP_E_ARG, "parcel: bad mode");
     if (parcel->mode == XP_PARCEL_EXPLICIT && (!parcel->pressure || !parcel->temperature || !parcel->dewpoint))
         return fail(XP_E_ARG, "explicit parcel: null arrays");
     return 0;
 }
 // the arguments of the CAPE family: p / T / Td, each of np parcels, the options
-int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o, bool f32_ok = false) {
+int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o, bool f32_ok = false,
+               bool ground_ok = false) {
     if (int rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) return rc;
     for (int i = 0; i < np; ++i)
-        if (int rc = check_parcel(parcels + i)) return rc;
+        if (int rc = check_parcel(parcels + i, ground_ok)) return rc;
+    // the parcels of one call share its grid: over the ground all of them, over the same surface fields, or none
+    for (int i = 1; i < np; ++i) {
+        const xp_parcel &a = parcels[0], &b = parcels[i];
+        if (over_ground(a) != over_ground(b) || (over_ground(a) && (a.pressure != b.pressure || a.temperature != b.temperature || a.dewpoint != b.dewpoint)))
+            return fail(XP_E_ARG, "parcels: XP_PARCEL_OVER_GROUND must be set on every parcel, with the same surface arrays, or on none");
+    }
     return check_opts(o, f32_ok);
 }
 
-// the CAPE family's p / T / Td, options and tables, staged once per call however many parcels it lifts
-int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_opts &o, xp::CapeArgs *a) {
+// the CAPE family's p / T / Td, options and tables, staged once per call however many parcels it lifts; `ground`: a parcel
+// with XP_PARCEL_OVER_GROUND, whose surface arrays re-base the grid (csrc/xp_ground.hpp) before anything else sees it
+int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_opts &o, xp::CapeArgs *a,
+               const xp_parcel *ground = nullptr) {
     int rc;
     TableSet ts;
     memset(a, 0, sizeof(*a));
@@ -473,7 +497,23 @@ int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td
     const bool same = a->p.ls == a->t.ls && a->p.ls == a->td.ls && a->p.cs == a->t.cs && a->p.cs == a->td.cs;
     const unsigned long long row = (unsigned long long)(p->ncol > 0 ? p->ncol : 1) * esize(p->dtype);
     a->off32 = 1;
-    if (!(same && a->p.cs >= 0 && a->p.ls >= 0 && (unsigned long long)a->p.cs * row < (1ull << 32))) {
+    a->hum = o.humidity == XP_HUM_SPECIFIC;
+    if (ground) {                                            // the views are read in place; this replaces the densify step
+        if (row >= (1ull << 32)) return fail(XP_E_ARG, "more than 4 GiB per level row");
+        xp::GroundArgs ga;
+        ga.p = a->p; ga.t = a->t; ga.m = a->td; ga.nlev = p->nlev; ga.ncol = p->ncol;
+        const size_t b = rows_bytes(p, 1);
+        if ((rc = st.in(ground->pressure, b, p->mem, &ga.ps)) || (rc = st.in(ground->temperature, b, p->mem, &ga.ts)) ||
+            (rc = st.in(ground->dewpoint, b, p->mem, &ga.tds)) || (rc = st.alloc(rows_bytes(p, p->nlev + 1), &ga.op)) ||
+            (rc = st.alloc(rows_bytes(p, p->nlev + 1), &ga.ot)) || (rc = st.alloc(rows_bytes(p, p->nlev + 1), &ga.otd))) return rc;
+        by_dtype(p->dtype, [&](auto z) {
+            using T = decltype(z);
+            if (a->hum) launch(xp::k_ground_rebase<T, true>, p->ncol, st, ga);
+            else launch(xp::k_ground_rebase<T, false>, p->ncol, st, ga);
+        });
+        a->nlev = p->nlev + 1; a->hum = 0;
+        a->p = {ga.op, p->ncol, 1}; a->t = {ga.ot, p->ncol, 1}; a->td = {ga.otd, p->ncol, 1};
+    } else if (!(same && a->p.cs >= 0 && a->p.ls >= 0 && (unsigned long long)a->p.cs * row < (1ull << 32))) {
         if (row >= (1ull << 32)) return fail(XP_E_ARG, "more than 4 GiB per level row");
         const int64_t n = p->nlev * p->ncol;                 // rare: densify the three views on the device first
         for (xp::View *v : {&a->p, &a->t, &a->td}) {
@@ -486,14 +526,13 @@ int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td
     }
     a->vtc = o.virtual_temperature_correction; a->log_interp = o.lcl_interp == XP_LCL_INTERP_LOG;
     a->pos_neg = o.pos_cape_neg_cin; a->post_zero = o.post_zero_cin; a->table_mode = o.moist_mode == XP_MOIST_TABLE;
-    a->hum = o.humidity == XP_HUM_SPECIFIC;
     return 0;
 }
 // one parcel's part of the arguments: its depth, and the arrays of an explicit parcel (in the views' dtype and mem)
 int set_parcel(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeArgs *a) {
     a->depth = parcel.depth;
     a->ex_p = a->ex_t = a->ex_td = nullptr;
-    if (parcel.mode != XP_PARCEL_EXPLICIT) return 0;
+    if (parcel.mode != XP_PARCEL_EXPLICIT) return 0;         // (the surface arrays of XP_PARCEL_OVER_GROUND: stage_cape)
     const size_t b = rows_bytes(p, 1);
     int rc;
     if ((rc = st.in(parcel.pressure, b, p->mem, &a->ex_p)) || (rc = st.in(parcel.temperature, b, p->mem, &a->ex_t)) ||
@@ -501,9 +540,10 @@ int set_parcel(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeAr
     return 0;
 }
 int fill_common(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
-                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false) {
+                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false, bool ground_ok = false) {
     int rc;
-    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok)) || (rc = stage_cape(st, p, t, td, o, a)) || (rc = set_parcel(st, *parcel, p, a)))
+    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok, ground_ok)) ||
+        (rc = stage_cape(st, p, t, td, o, a, over_ground(*parcel) ? parcel : nullptr)) || (rc = set_parcel(st, *parcel, p, a)))
         return rc;
     return 0;
 }
@@ -648,7 +688,7 @@ bool multi_fused_ok(int32_t np, const xp_parcel *parcels, const xp_opts &o, cons
     if (!(o.flags & XP_OPT_FUSE_PARCELS) || o.moist_mode != XP_MOIST_FAMILY || o.humidity != XP_HUM_DEWPOINT) return false;
     if (np != 2 || profiles) return false;                                   // instantiated parcel counts (xp_multi_tu.hip)
     for (int i = 0; i < np; ++i)
-        if (parcels[i].mode != XP_PARCEL_SURFACE && parcels[i].mode != XP_PARCEL_MOST_UNSTABLE && parcels[i].mode != XP_PARCEL_MIXED_LAYER) return false;
+        if (parcel_mode(parcels[i]) == XP_PARCEL_EXPLICIT) return false;
     return true;
 }
 
@@ -751,11 +791,11 @@ int xp_cape_cin(const xp_view *p, const xp_view *t, const xp_view *td, const xp_
     int32_t *flags;
     int rc;
     const bool f32 = oo.compute == XP_F32;                   // (held to its contract before anything is staged or looked up)
-    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
-    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
+    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
+    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true, true)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
         (rc = family_flags(st, oo, a.ncol, &flags))) return rc;
     if (f32) cape_pass32(st, a, flags);
-    else cape_pass(st, a, p->dtype, parcel->mode, profile != nullptr, flags);
+    else cape_pass(st, a, p->dtype, parcel_mode(*parcel), profile != nullptr, flags);
     return st.finish();
 }
 
@@ -769,7 +809,8 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     xp::CapeArgs a, pa[xp::MULTI_MAX];
     int rc;
     // every parcel is checked, and its outputs staged, before anything runs; p / T / Td are staged once
-    if ((rc = check_cape(p, t, td, np, parcels, oo)) || (rc = stage_cape(st, p, t, td, oo, &a))) return rc;
+    if ((rc = check_cape(p, t, td, np, parcels, oo, false, true)) ||
+        (rc = stage_cape(st, p, t, td, oo, &a, over_ground(parcels[0]) ? parcels : nullptr))) return rc;   // re-based once per call
     for (int i = 0; i < np; ++i) {
         pa[i] = a;
         if ((rc = set_parcel(st, parcels[i], p, &pa[i])) ||
@@ -779,7 +820,7 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     if (!multi_fused_ok(np, parcels, oo, profiles)) {        // one pass per parcel
         int32_t *flags;
         if ((rc = family_flags(st, oo, ncol, &flags))) return rc;
-        for (int i = 0; i < np; ++i) cape_pass(st, pa[i], p->dtype, parcels[i].mode, profiles != nullptr, flags);
+        for (int i = 0; i < np; ++i) cape_pass(st, pa[i], p->dtype, parcel_mode(parcels[i]), profiles != nullptr, flags);
         return st.finish();
     }
     xp::MultiArgs m;
@@ -787,7 +828,7 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     m.base = a;
     m.np = np;
     for (int i = 0; i < np; ++i) {
-        m.mode[i] = parcels[i].mode;                                         // XP_PARCEL_* == xp::PM_*
+        m.mode[i] = parcel_mode(parcels[i]);                                 // XP_PARCEL_* == xp::PM_*
         m.depth[i] = parcels[i].depth;
         m.s[i] = pa[i].s;
     }
@@ -927,13 +968,13 @@ int xp_select_parcel(const xp_view *p, const xp_view *t, const xp_view *td, cons
     if (st.rc) return st.rc;
     xp::CapeArgs a;
     int rc;
-    if ((rc = fill_common(st, p, t, td, parcel, default_opts(), &a))) return rc;
-    if (parcel->mode != XP_PARCEL_MOST_UNSTABLE && parcel->mode != XP_PARCEL_MIXED_LAYER)
+    if ((rc = fill_common(st, p, t, td, parcel, default_opts(), &a, false, true))) return rc;
+    if (parcel_mode(*parcel) != XP_PARCEL_MOST_UNSTABLE && parcel_mode(*parcel) != XP_PARCEL_MIXED_LAYER)
         return fail(XP_E_ARG, "xp_select_parcel: mode must be most-unstable or mixed-layer");
     if ((rc = stage_scalars(st, out, a.ncol, &a.s))) return rc;
     by_dtype(p->dtype, [&](auto z) {
         using T = decltype(z);
-        if (parcel->mode == XP_PARCEL_MOST_UNSTABLE) launch(xp::k_select_parcel<T, xp::PM_MU>, a.ncol, st, a);
+        if (parcel_mode(*parcel) == XP_PARCEL_MOST_UNSTABLE) launch(xp::k_select_parcel<T, xp::PM_MU>, a.ncol, st, a);
         else launch(xp::k_select_parcel<T, xp::PM_ML>, a.ncol, st, a);
     });
     return st.finish();

@@ -177,8 +177,35 @@ def set_moist_lapse(mode):
     _DEFAULT['moist'] = mode
 
 
+def _over_ground(pressure, temperature, dewpoint, ground):
+    """A ground= call (XP_PARCEL_OVER_GROUND, include/xparcel.h): its _Call, whose grid is temperature's, the xp_views of
+    pressure, temperature and moisture, and the three per-column surface arrays.  A pressure of the nlev isobars is expanded
+    on the host (_on_grid), or, as a device tensor, passed as it is: a view whose col_stride is 0."""
+    assert len(ground) == 3, 'ground: (surface_pressure, surface_temperature, surface_dewpoint)'
+    isobars = len(np.shape(pressure)) == 1 and len(np.shape(temperature)) > 1
+    if isobars:
+        assert np.shape(pressure)[0] == np.shape(temperature)[0], 'a 1-D pressure must have one value per level'
+        if not (_is_torch(pressure) and pressure.is_cuda):
+            pressure, isobars = _on_grid(pressure, temperature), False
+    c = _Call(temperature, dewpoint, pressure, *[x for x in ground if _is_torch(x)])
+    t, td, p = c.ins[:3]
+    assert t.shape == td.shape and (isobars or p.shape == t.shape), 'pressure, temperature, dewpoint must share a shape'
+    pv = c.view(t)
+    pv.data = _ptr(p)
+    if isobars:
+        pv.lev_stride, pv.col_stride = 1, 0
+    return c, (pv, c.view(t), c.view(td)), [c.per_col(x) for x in ground]
+
+
+def _ground_parcel(pc, surface):
+    """Set XP_PARCEL_OVER_GROUND and the surface arrays on the xp_parcel `pc`."""
+    assert pc.mode != L.PARCEL['explicit'], 'ground: not with an explicit parcel'
+    pc.mode |= L.PARCEL_OVER_GROUND
+    pc.pressure, pc.temperature, pc.dewpoint = (_ptr(x) for x in surface)
+
+
 def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=None, parcel_values=None,
-                     want_profile=False, want=None, moist=None, lifted_index_at=None, compute=None, **kwargs):
+                     want_profile=False, want=None, moist=None, lifted_index_at=None, compute=None, ground=None, **kwargs):
     """pf.py:1394-1475 with the three drivers.  Returns a dict of per-column arrays (and 'profile').
     want_profile: True for the six profile arrays of pf.py:806-931, or an iterable of their names for a subset (the ones
     not named are neither allocated nor written: lifted_index needs three of the six).
@@ -188,14 +215,24 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     (parcel_test.py:262-266 fused into the pass).
     compute='float32': the level walk above the LCL in fp32 arithmetic (float32 arrays, surface parcel, moist='family',
     default options, no profile; `want` then defaults to COMPUTE32_WANT); raises where that kernel does not apply.  None:
-    the module default (set_compute), which falls back to fp64 where it does not."""
-    c = _Call(pressure, temperature, dewpoint)
-    p, t, td = c.ins
-    assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
+    the module default (set_compute), which falls back to fp64 where it does not.
+    ground=(surface_pressure, surface_temperature, surface_dewpoint): pressure-level data (XP_PARCEL_OVER_GROUND,
+    include/xparcel.h).  The arrays hold isobaric levels, `pressure` possibly just the nlev isobars, and each column is cut
+    at its surface pressure: the surface values become level 0, the levels above the ground follow, NaN fills the rest.
+    Every result is that of the call on those re-based columns: the indices count their rows, and the profile has
+    nlev + 2 rows.  Not with an explicit parcel, nor with compute='float32'."""
+    if ground is None:
+        c = _Call(pressure, temperature, dewpoint)
+        p, t, td = c.ins
+        assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
+        views = (c.view(p), c.view(t), c.view(td))
+    else:
+        c, views, surface = _over_ground(pressure, temperature, dewpoint, ground)
     moist = moist or _DEFAULT['moist']
     if compute is None:
         compute = _DEFAULT['compute']
-        if compute == 'float32' and not _compute32_applies(c, parcel, moist, want, want_profile, lifted_index_at, kwargs):
+        if compute == 'float32' and not (ground is None and
+                                         _compute32_applies(c, parcel, moist, want, want_profile, lifted_index_at, kwargs)):
             compute = 'float64'
     if compute == 'float32' and want is None:
         want = COMPUTE32_WANT
@@ -205,30 +242,38 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     pc = L.Parcel(L.PARCEL[parcel], 0, float(depth), None, None, None)
     if parcel == 'explicit':
         pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in parcel_values)
+    if ground is not None:
+        _ground_parcel(pc, surface)
     so, res = c.scalars(L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want), c.hshape)
     po = None
     if want_profile or lifted_index_at is not None:
         pvars = L.PROFILE_VARS if want_profile is True else tuple(want_profile or ())
         assert all(k in L.PROFILE_VARS for k in pvars), f'profile variables are {L.PROFILE_VARS}'
-        po, prof = c.profile(pvars, c.nlev + 1, c.hshape, lifted_index_at)
+        po, prof = c.profile(pvars, c.nlev + (1 if ground is None else 2), c.hshape, lifted_index_at)
         if lifted_index_at is not None:
             res['lifted_index'] = prof.pop('lifted_index')
-    c.run('xp_cape_cin', c.view(p), c.view(t), c.view(td), pc, o, so, po)
+    c.run('xp_cape_cin', *views, pc, o, so, po)
     if want_profile:
         res['profile'] = prof
     return res
 
 
-def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=None, lifted_index_at=None, fused=False, **kwargs):
+def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=None, lifted_index_at=None, fused=False,
+                   ground=None, **kwargs):
     """Several parcels of one grid in ONE call (xp_cape_cin_multi): `parcels` is a sequence of names or (name, depth)
     pairs out of 'surface', 'most_unstable', 'mixed_layer' -- e.g. [('most_unstable', 300), ('mixed_layer', 100)] for
     BASELINE config 5, [('most_unstable', 250), ('mixed_layer', 100), ('mixed_layer', 50)] for conv_properties
     (pf.py:1984-2006).  Returns one dict per parcel, bit-identical to what cape_cin_columns() returns for it.
     fused=True (XP_OPT_FUSE_PARCELS; moist='family', two parcels): one pass over the grid for both -- same numbers,
-    measured slower than a pass per parcel on MI355X, hence opt-in."""
-    c = _Call(pressure, temperature, dewpoint)
-    p, t, td = c.ins
-    assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
+    measured slower than a pass per parcel on MI355X, hence opt-in.
+    ground: as in cape_cin_columns; the grid is cut at the ground once for all the parcels."""
+    if ground is None:
+        c = _Call(pressure, temperature, dewpoint)
+        p, t, td = c.ins
+        assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
+        views = (c.view(p), c.view(t), c.view(td))
+    else:
+        c, views, surface = _over_ground(pressure, temperature, dewpoint, ground)
     o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
     o.flags = L.OPT_FUSE_PARCELS if fused else 0
     specs = []
@@ -240,6 +285,9 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
         specs.append((name, float(depth)))
     n = len(specs)
     pcs = (L.Parcel * n)(*[L.Parcel(L.PARCEL[nm], 0, dp, None, None, None) for nm, dp in specs])
+    if ground is not None:
+        for pc in pcs:
+            _ground_parcel(pc, surface)
     names = L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want)
     sos = (L.ScalarsOut * n)()
     pos = (L.ProfileOut * n)() if lifted_index_at is not None else None
@@ -247,10 +295,10 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
     for i in range(n):
         sos[i], out = c.scalars(names, c.hshape)
         if pos is not None:
-            pos[i], li = c.profile((), c.nlev + 1, c.hshape, lifted_index_at)
+            pos[i], li = c.profile((), c.nlev + (1 if ground is None else 2), c.hshape, lifted_index_at)
             out.update(li)
         outs.append(out)
-    c.run('xp_cape_cin_multi', c.view(p), c.view(t), c.view(td), n, pcs, o, sos, pos)
+    c.run('xp_cape_cin_multi', *views, n, pcs, o, sos, pos)
     return outs
 
 
@@ -308,22 +356,28 @@ def parcel_profile_with_lcl(pressure, temperature, dewpoint, parcel_pressure, pa
     return out
 
 
-def _select(pressure, temperature, dewpoint, mode, depth):
-    c = _Call(pressure, temperature, dewpoint)
+def _select(pressure, temperature, dewpoint, mode, depth, ground=None):
+    pc = L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None)
+    if ground is None:
+        c = _Call(pressure, temperature, dewpoint)
+        views = tuple(map(c.view, c.ins))
+    else:
+        c, views, surface = _over_ground(pressure, temperature, dewpoint, ground)
+        _ground_parcel(pc, surface)
     so, out = c.scalars(L.SCALAR_P + ('parcel_index',), c.hshape)
-    c.run('xp_select_parcel', *map(c.view, c.ins), L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None), so)
+    c.run('xp_select_parcel', *views, pc, so)
     return {'pressure': out['parcel_pressure'], 'temperature': out['parcel_temperature'],
             'dewpoint': out['parcel_dewpoint'], 'index': out['parcel_index']}
 
 
-def most_unstable_parcel(pressure, temperature, dewpoint, depth=300):
-    """pf.py:102."""
-    return _select(pressure, temperature, dewpoint, 'most_unstable', depth)
+def most_unstable_parcel(pressure, temperature, dewpoint, depth=300, ground=None):
+    """pf.py:102.  ground: as in cape_cin_columns ('index' counts the rows of the column cut at the ground)."""
+    return _select(pressure, temperature, dewpoint, 'most_unstable', depth, ground)
 
 
-def mixed_parcel(pressure, temperature, dewpoint, depth=100):
-    """pf.py:229."""
-    r = _select(pressure, temperature, dewpoint, 'mixed_layer', depth)
+def mixed_parcel(pressure, temperature, dewpoint, depth=100, ground=None):
+    """pf.py:229.  ground: as in cape_cin_columns."""
+    r = _select(pressure, temperature, dewpoint, 'mixed_layer', depth, ground)
     r.pop('index')
     return r
 
