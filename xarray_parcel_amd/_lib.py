@@ -133,6 +133,8 @@ ST_LAYER_OPEN = 64
 EFFECTIVE_F = ('base_pressure', 'top_pressure', 'base_height', 'top_height')
 EFFECTIVE_I = ('base_index', 'top_index', 'status')
 EFFECTIVE_CANDIDATES = ('candidate_cape', 'candidate_cin')
+# the named outputs of every struct that are int32_t * (indices, the status word, the shear flag); all others have the call's dtype
+INT32_OUT = frozenset(SCALAR_I + EFFECTIVE_I + ('positive_shear',))
 
 
 class EffectiveLayerOut(C.Structure):

@@ -6,8 +6,7 @@ turns the library's missing-tables error into the reference's assert, and the mo
 (parcel_functions.set_moist_lapse; None = the lookup tables).
 """
 from . import numpy_api as _api
-from ._xr import Dataset
-from .parcel_functions import VERT, _Grid, _device, _host, _moist_mode
+from .parcel_functions import VERT, _Grid, _device, _moist_mode
 
 _ATTRS = {
     'dcape': {'long_name': 'Downdraft convective available potential energy', 'units': 'J kg$^{-1}$'},
@@ -29,5 +28,5 @@ def downdraft_cape(pressure, temperature, dewpoint, vert_dim=VERT, bottom=700, d
     g = _Grid(pressure, vert_dim)
     res = _device(_api.downdraft_cape, g.values(pressure), g.values(temperature), g.values(dewpoint), bottom=bottom,
                   depth=depth, moist=moist, want_profile=True)
-    ds = Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _KEYS.items()})
-    return ds, g.vert(_host(res['parcel_temperature']), 'dcape_parcel_temperature', _ATTRS['dcape_parcel_temperature'])
+    ds = g.dataset({name: res[k] for k, name in _KEYS.items()}, attrs=_ATTRS.get)
+    return ds, g.vert(res['parcel_temperature'], 'dcape_parcel_temperature', _ATTRS['dcape_parcel_temperature'])

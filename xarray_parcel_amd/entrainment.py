@@ -4,11 +4,8 @@ column, the per-point formula, and the chain from the sounding grid to ECAPE, th
 ecape_from_ncape, ecape).  The reference has no counterparts, so this lives next to the mirror (parcel_functions.py) rather
 than in it, and is built from the mirror's plumbing, as kinematics.py and downdraft.py.
 """
-import numpy as np
-
 from . import numpy_api as _api
-from ._xr import Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 _CAPE = 'J kg$^{-1}$'
 _WIND = 'm s$^{-1}$'
@@ -30,14 +27,6 @@ _ECAPE = ('ecape', 'ecape_a', 'psi')
 _CHAIN = _ECAPE + ('ncape', 'cape', 'cin', 'lfc_height', 'el_height', 'sr_u', 'sr_v', 'status')
 
 
-def _per_col(g, x):
-    return x if x is None or np.ndim(x) == 0 else g.values(x)
-
-
-def _dataset(g, res, keys):
-    return Dataset({k: g.horiz(_host(res[k]), k, _ATTRS[k]) for k in keys})
-
-
 def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure, vert_dim=VERT):
     """NCAPE [J/kg] of every column between lfc_pressure and el_pressure [hPa; DataArrays on the horizontal dims, as the CAPE
     / CIN functions return them], from pressure [hPa], temperature, dewpoint [K] and height [m] on one vertical.  Returns a
@@ -45,8 +34,8 @@ def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure, ve
     A column without an LFC has ncape 0; one whose EL is not above its LFC is NaN."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.ncape, g.values(pressure), g.values(temperature), g.values(dewpoint), g.values(height),
-                  _per_col(g, lfc_pressure), _per_col(g, el_pressure))
-    return _dataset(g, res, _NCAPE)
+                  g.per_col(lfc_pressure), g.per_col(el_pressure))
+    return g.dataset(res, _NCAPE, _ATTRS.get)
 
 
 def ecape_from_ncape(cape, ncape, el_height, sr_u, sr_v):
@@ -54,7 +43,7 @@ def ecape_from_ncape(cape, ncape, el_height, sr_u, sr_v):
     0-1 km mean wind sr_u, sr_v [m/s].  Returns a Dataset of ecape, ecape_a (with the inflow's kinetic energy) and psi."""
     g = _Grid(cape, None)
     res = _device(_api.ecape_from_ncape, *(g.values(x) for x in (cape, ncape, el_height, sr_u, sr_v)))
-    return _dataset(g, res, _ECAPE)
+    return g.dataset(res, _ECAPE, _ATTRS.get)
 
 
 def ecape(pressure, temperature, dewpoint, height, u, v, vert_dim=VERT, parcel='most_unstable', depth=None, storm='right',
@@ -65,6 +54,6 @@ def ecape(pressure, temperature, dewpoint, height, u, v, vert_dim=VERT, parcel='
     Dataset on the horizontal dims: ecape, ecape_a, psi, ncape, cape, cin, lfc_height, el_height, sr_u, sr_v and status."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.ecape, *(g.values(x) for x in (pressure, temperature, dewpoint, height, u, v)), parcel=parcel,
-                  depth=depth, storm=storm, storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), moist=moist,
+                  depth=depth, storm=storm, storm_u=g.per_col(storm_u), storm_v=g.per_col(storm_v), moist=moist,
                   **cape_cin_options)
-    return _dataset(g, res, _CHAIN)
+    return g.dataset(res, _CHAIN, _ATTRS.get)

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import numpy_api as _api
 from ._xr import Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 _CAPE = 'J kg$^{-1}$'
 _ATTRS = {
@@ -49,7 +49,7 @@ def _inputs(pressure, temperature, dewpoint, surface, vert_dim):
 
 
 def _dataset(g, res, p, ps, suffix=''):
-    out = {k + suffix: g.horiz(_host(v), k + suffix, _ATTRS.get(k)) for k, v in res.items()}
+    out = {k + suffix: g.horiz(v, k + suffix, _ATTRS.get(k)) for k, v in res.items()}
     out['levels_below_ground'] = g.horiz(levels_below_ground(p, ps), 'levels_below_ground', _ATTRS['levels_below_ground'])
     return out
 

@@ -20,10 +20,6 @@ _ATTRS = {
 }
 
 
-def _opt(g, x):
-    return x if x is None or np.ndim(x) == 0 else g.values(x)
-
-
 def hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, base_height=None, layers=(), want=None,
                 vert_dim=VERT):
     """Hydrostatic heights and the thickness of up to four layers by pressure in one pass, as a Dataset: 'height' on the
@@ -32,18 +28,16 @@ def hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, ba
     specific_humidity (neither: dry), base_height a scalar or a DataArray on the horizontal dims (None: 0, heights above the
     lowest valid level), a pressure that has only the vertical dim is isobaric data."""
     g = _Grid(temperature, vert_dim)
-    res = _device(_api.hydrostatic, g.values(pressure), g.values(temperature), _opt(g, dewpoint), _opt(g, specific_humidity),
-                  _opt(g, base_height), layers=layers, want=want)
+    res = _device(_api.hydrostatic, g.values(pressure), g.values(temperature), g.per_col(dewpoint), g.per_col(specific_humidity),
+                  g.per_col(base_height), layers=layers, want=want)
     out = {}
     if 'height' in res:
-        out['height'] = g.vert(_host(res['height']), 'height', _ATTRS['height'])
+        out['height'] = g.vert(res['height'], 'height', _ATTRS['height'])
     if res.get('thickness'):                             # (without layers: no variable)
-        n = len(res['thickness'])
         th = np.stack([_host(x) for x in res['thickness']])
-        out['thickness'] = DataArray(th, dims=('hydrostatic_layer',) + g.dims, coords=dict(g.coords, hydrostatic_layer=np.arange(n)),
-                                     attrs=dict(_ATTRS['thickness']), name='thickness')
+        out['thickness'] = g.vert(th, 'thickness', _ATTRS['thickness'], vcoord=np.arange(len(th)), dim='hydrostatic_layer')
     if 'status' in res:
-        out['status'] = g.horiz(_host(res['status']), 'status', _ATTRS['status'])
+        out['status'] = g.horiz(res['status'], 'status', _ATTRS['status'])
     return Dataset(out)
 
 
@@ -51,18 +45,18 @@ def hydrostatic_height(pressure, temperature, dewpoint=None, specific_humidity=N
     """The hydrostatic height [m] of every level on the dims of `temperature` (vertical first), with units and a long_name:
     base_height (None: 0) at each column's lowest valid level, NaN at invalid levels."""
     g = _Grid(temperature, vert_dim)
-    res = _device(_api.hydrostatic_height, g.values(pressure), g.values(temperature), _opt(g, dewpoint), _opt(g, specific_humidity),
-                  _opt(g, base_height))
-    return g.vert(_host(res), 'height', _ATTRS['height'])
+    res = _device(_api.hydrostatic_height, g.values(pressure), g.values(temperature), g.per_col(dewpoint),
+                  g.per_col(specific_humidity), g.per_col(base_height))
+    return g.vert(res, 'height', _ATTRS['height'])
 
 
 def thickness_hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, bottom=None, depth=None, vert_dim=VERT):
     """metpy.calc.thickness_hydrostatic [m] per column: from `bottom` [hPa; None: the lowest valid level] up `depth` [hPa; None:
     to the highest valid level].  The moisture is dewpoint or specific_humidity, not MetPy's mixing_ratio."""
     g = _Grid(temperature, vert_dim)
-    res = _device(_api.thickness_hydrostatic, g.values(pressure), g.values(temperature), _opt(g, dewpoint), _opt(g, specific_humidity),
-                  bottom=bottom, depth=depth)
-    return g.horiz(_host(res), 'thickness', _ATTRS['thickness'])
+    res = _device(_api.thickness_hydrostatic, g.values(pressure), g.values(temperature), g.per_col(dewpoint),
+                  g.per_col(specific_humidity), bottom=bottom, depth=depth)
+    return g.horiz(res, 'thickness', _ATTRS['thickness'])
 
 
 def _point(fn, x, name):

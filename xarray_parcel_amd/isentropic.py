@@ -8,7 +8,7 @@ import numpy as np
 
 from . import numpy_api as _api
 from ._xr import Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 LEVEL_DIM = 'isentropic_level'
 _ATTRS = {
@@ -33,6 +33,6 @@ def isentropic_interpolation(levels, pressure, temperature, *args, temperature_o
     names += [getattr(a, 'name', None) or 'var%d' % i for i, a in enumerate(args)]
     assert len(set(names)) == len(names), 'the further variables need names of their own'
     attrs = dict(_ATTRS, **{k: dict(getattr(a, 'attrs', {})) for k, a in zip(names[len(names) - len(args):], args)})
-    out = {k: g.vert(_host(x), k, attrs[k], vcoord=lev, dim=LEVEL_DIM) for k, x in zip(names, res)}
-    out['status'] = g.horiz(_host(res[-1]), 'status', _ATTRS['status'])
+    out = {k: g.vert(x, k, attrs[k], vcoord=lev, dim=LEVEL_DIM) for k, x in zip(names, res)}
+    out['status'] = g.horiz(res[-1], 'status', _ATTRS['status'])
     return Dataset(out, attrs={'isentropic_level_units': 'K'})

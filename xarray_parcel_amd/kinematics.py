@@ -10,8 +10,7 @@ the results, _device turns library errors into the mirror's.
 import numpy as np
 
 from . import numpy_api as _api
-from ._xr import DataArray, Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 _WIND = 'm s$^{-1}$'
 _SRH = 'm$^{2}$ s$^{-2}$'
@@ -66,26 +65,13 @@ _CORFIDI = {k: 'corfidi_' + k for k in ('upwind_u', 'upwind_v', 'downwind_u', 'd
 _EFFECTIVE = ('base_pressure', 'top_pressure', 'base_height', 'top_height', 'base_index', 'top_index', 'status')
 
 
-def _per_col(g, x):
-    return x if x is None or np.ndim(x) == 0 else g.values(x)
-
-
-def _per_layer(g, res, names, dim, coord):
-    """The helicity results as a Dataset on the horizontal dims, or, with a coordinate, under the leading dim `dim`."""
-    if coord is None:
-        return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in names.items()})
-    coords = dict(g.coords, **{dim: coord})
-    return Dataset({name: DataArray(_host(res[k]), dims=(dim,) + g.dims, coords=coords, attrs=dict(_ATTRS[name]), name=name)
-                    for k, name in names.items()})
-
-
 def bunkers_storm_motion(pressure, u, v, height, vert_dim=VERT):
     """Bunkers right- and left-mover storm motion and the 0-6 km pressure-weighted mean wind of every column, from
     pressure [hPa], u, v [m/s] and height [m] on one vertical (pressure on the wind levels).  Returns a Dataset on the
     horizontal dims; columns that do not reach 6 km above their lowest level (MetPy raises) are NaN."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.bunkers_storm_motion, g.values(pressure), g.values(u), g.values(v), g.values(height))
-    return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _BUNKERS.items()})
+    return g.dataset({name: res[k] for k, name in _BUNKERS.items()}, attrs=_ATTRS.get)
 
 
 def storm_relative_helicity(height, u, v, depth, vert_dim=VERT, bottom=0.0, storm_u=0.0, storm_v=0.0, surface_u=None,
@@ -97,9 +83,10 @@ def storm_relative_helicity(height, u, v, depth, vert_dim=VERT, bottom=0.0, stor
     not span are NaN."""
     g = _Grid(height, vert_dim)
     res = _device(_api.storm_relative_helicity, g.values(height), g.values(u), g.values(v), depth, bottom=bottom,
-                  storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), surface_u=_per_col(g, surface_u),
-                  surface_v=_per_col(g, surface_v))
-    return _per_layer(g, res, _SRH_NAMES, 'srh_depth', None if np.ndim(depth) == 0 else np.asarray(depth, dtype=np.float64))
+                  storm_u=g.per_col(storm_u), storm_v=g.per_col(storm_v), surface_u=g.per_col(surface_u),
+                  surface_v=g.per_col(surface_v))
+    layered = {} if np.ndim(depth) == 0 else dict(vert=True, vcoord=np.asarray(depth, dtype=np.float64), dim='srh_depth')
+    return g.dataset({name: res[k] for k, name in _SRH_NAMES.items()}, attrs=_ATTRS.get, **layered)
 
 
 def effective_inflow_layer(pressure, temperature, dewpoint, height=None, vert_dim=VERT, cape_min=100.0, cin_min=-250.0,
@@ -111,12 +98,13 @@ def effective_inflow_layer(pressure, temperature, dewpoint, height=None, vert_di
     vertical (NaN where a level was not lifted).  Columns without a layer are NaN."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.effective_inflow_layer, g.values(pressure), g.values(temperature), g.values(dewpoint),
-                  None if height is None else g.values(height), cape_min=cape_min, cin_min=cin_min,
+                  g.per_col(height), cape_min=cape_min, cin_min=cin_min,
                   search_depth=search_depth, moist=moist, want_candidates=want_candidates, **cape_cin_options)
-    out = {name: g.horiz(_host(res[name]), name, _ATTRS[name]) for name in _EFFECTIVE}
+    out = g.dataset(res, _EFFECTIVE, _ATTRS.get)
     if want_candidates:
-        out.update({name: g.vert(_host(res[name]), name, _ATTRS[name]) for name in ('candidate_cape', 'candidate_cin')})
-    return Dataset(out)
+        for name in ('candidate_cape', 'candidate_cin'):
+            out[name] = g.vert(res[name], name, _ATTRS[name])
+    return out
 
 
 def storm_relative_helicity_layers(height, u, v, bottom, top, vert_dim=VERT, storm_u=0.0, storm_v=0.0, surface_u=None,
@@ -129,11 +117,12 @@ def storm_relative_helicity_layers(height, u, v, bottom, top, vert_dim=VERT, sto
     inverted, are NaN."""
     g = _Grid(height, vert_dim)
     many = isinstance(top, (list, tuple))
-    tops = [_per_col(g, x) for x in top] if many else _per_col(g, top)
-    res = _device(_api.storm_relative_helicity_layers, g.values(height), g.values(u), g.values(v), _per_col(g, bottom), tops,
-                  storm_u=_per_col(g, storm_u), storm_v=_per_col(g, storm_v), surface_u=_per_col(g, surface_u),
-                  surface_v=_per_col(g, surface_v))
-    return _per_layer(g, res, _LAYER_NAMES, 'srh_layer', np.arange(len(top)) if many else None)
+    tops = [g.per_col(x) for x in top] if many else g.per_col(top)
+    res = _device(_api.storm_relative_helicity_layers, g.values(height), g.values(u), g.values(v), g.per_col(bottom), tops,
+                  storm_u=g.per_col(storm_u), storm_v=g.per_col(storm_v), surface_u=g.per_col(surface_u),
+                  surface_v=g.per_col(surface_v))
+    layered = dict(vert=True, vcoord=np.arange(len(top)), dim='srh_layer') if many else {}
+    return g.dataset({name: res[k] for k, name in _LAYER_NAMES.items()}, attrs=_ATTRS.get, **layered)
 
 
 def significant_tornado(sbcape, lcl_height, storm_helicity_1km, shear_6km):
@@ -157,16 +146,11 @@ def wind_layers(pressure, u, v, height=None, layers=(), vert_dim=VERT):
     wind, the ln p bulk shear, the wind at the bottom, the strongest wind and its pressure, and the per-column status.
     Layers that a column does not span are NaN."""
     g = _Grid(pressure, vert_dim)
-    res = _device(_api.wind_layers, g.values(pressure), g.values(u), g.values(v), None if height is None else g.values(height),
-                  layers=layers)
-    ds = _per_layer(g, res, _WIND_LAYERS, 'wind_layer', np.arange(len(layers)))
-    ds['status'] = g.horiz(_host(res['status']), 'status', _ATTRS['status'])
+    res = _device(_api.wind_layers, g.values(pressure), g.values(u), g.values(v), g.per_col(height), layers=layers)
+    ds = g.dataset({name: res[k] for k, name in _WIND_LAYERS.items()}, attrs=_ATTRS.get, vert=True,
+                   vcoord=np.arange(len(layers)), dim='wind_layer')
+    ds['status'] = g.horiz(res['status'], 'status', _ATTRS['status'])
     return ds
-
-
-def _pair(g, fn, names, *args, **kw):
-    res = _device(fn, *args, **kw)
-    return Dataset({name: g.horiz(_host(x), name, _ATTRS[name]) for name, x in zip(names, res)})
 
 
 def mean_pressure_weighted(pressure, u, v, height=None, bottom=None, depth=100.0, vert_dim=VERT):
@@ -174,23 +158,24 @@ def mean_pressure_weighted(pressure, u, v, height=None, bottom=None, depth=100.0
     depth: metres (bottom above the lowest valid level) if `height` is given and `bottom` is not None, hPa otherwise
     (bottom=None: the lowest valid level) -- numpy_api.mean_pressure_weighted states the rule."""
     g = _Grid(pressure, vert_dim)
-    return _pair(g, _api.mean_pressure_weighted, ('layer_mean_wind_u', 'layer_mean_wind_v'), g.values(pressure), g.values(u),
-                 g.values(v), None if height is None else g.values(height), bottom=bottom, depth=depth)
+    res = _device(_api.mean_pressure_weighted, g.values(pressure), g.values(u), g.values(v), g.per_col(height), bottom=bottom,
+                  depth=depth)
+    return g.dataset(dict(zip(('layer_mean_wind_u', 'layer_mean_wind_v'), res)), attrs=_ATTRS.get)
 
 
 def bulk_shear(pressure, u, v, height=None, bottom=None, depth=100.0, vert_dim=VERT):
     """metpy.calc.bulk_shear for every column, as a Dataset of bulk_shear_u / _v; bottom, depth as in mean_pressure_weighted."""
     g = _Grid(pressure, vert_dim)
-    return _pair(g, _api.bulk_shear, ('bulk_shear_u', 'bulk_shear_v'), g.values(pressure), g.values(u), g.values(v),
-                 None if height is None else g.values(height), bottom=bottom, depth=depth)
+    res = _device(_api.bulk_shear, g.values(pressure), g.values(u), g.values(v), g.per_col(height), bottom=bottom, depth=depth)
+    return g.dataset(dict(zip(('bulk_shear_u', 'bulk_shear_v'), res)), attrs=_ATTRS.get)
 
 
 def critical_angle(pressure, u, v, height, storm_u, storm_v, vert_dim=VERT):
     """metpy.calc.critical_angle [degrees] for every column: the angle between the 0-500 m bulk shear and the storm-relative
     inflow at the lowest valid level; storm_u / storm_v scalars or DataArrays on the horizontal dims."""
     g = _Grid(pressure, vert_dim)
-    out = _device(_api.critical_angle, g.values(pressure), g.values(u), g.values(v), g.values(height), _per_col(g, storm_u),
-                  _per_col(g, storm_v))
+    out = _device(_api.critical_angle, g.values(pressure), g.values(u), g.values(v), g.values(height), g.per_col(storm_u),
+                  g.per_col(storm_v))
     return g.horiz(out, 'critical_angle', _ATTRS['critical_angle'])
 
 
@@ -198,9 +183,9 @@ def corfidi_storm_motion(pressure, u, v, llj_u=None, llj_v=None, vert_dim=VERT):
     """Corfidi upwind- and downwind-propagating MCS motion of every column, as a Dataset; the low-level jet (scalars or
     DataArrays on the horizontal dims, both or neither) defaults to the strongest wind at or below 850 hPa."""
     g = _Grid(pressure, vert_dim)
-    res = _device(_api.corfidi_storm_motion, g.values(pressure), g.values(u), g.values(v), llj_u=_per_col(g, llj_u),
-                  llj_v=_per_col(g, llj_v))
-    return Dataset({name: g.horiz(_host(res[k]), name, _ATTRS[name]) for k, name in _CORFIDI.items()})
+    res = _device(_api.corfidi_storm_motion, g.values(pressure), g.values(u), g.values(v), llj_u=g.per_col(llj_u),
+                  llj_v=g.per_col(llj_v))
+    return g.dataset({name: res[k] for k, name in _CORFIDI.items()}, attrs=_ATTRS.get)
 
 
 def significant_tornado_effective(mlcape, mlcin, lcl_height, esrh, ebwd, base_height=None):
@@ -208,5 +193,5 @@ def significant_tornado_effective(mlcape, mlcin, lcl_height, esrh, ebwd, base_he
     (where it is > 0 the result is 0)."""
     g = _Grid(mlcape, None)
     args = [g.values(x) for x in (mlcape, mlcin, lcl_height, esrh, ebwd)]
-    out = _device(_api.significant_tornado_effective, *args, base_height=None if base_height is None else g.values(base_height))
+    out = _device(_api.significant_tornado_effective, *args, base_height=g.per_col(base_height))
     return g.horiz(out, 'significant_tornado_effective', _ATTRS['significant_tornado_effective'])

@@ -6,8 +6,7 @@ lives next to the mirror (parcel_functions.py) rather than in it, and is built f
 import numpy as np
 
 from . import numpy_api as _api
-from ._xr import DataArray, Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 _CAPE = 'J kg$^{-1}$'
 _ATTRS = {
@@ -28,10 +27,6 @@ _PER_LAYER = ('cape', 'cin', 'bottom_pressure', 'top_pressure')
 _PER_COLUMN = ('total_cape', 'total_cin', 'lfc_pressure', 'el_pressure', 'lcl_pressure', 'status')
 
 
-def _values(g, x):
-    return x if x is None or np.ndim(x) == 0 else g.values(x)
-
-
 def cape_cin_layers(pressure, temperature, dewpoint, layers, height=None, vert_dim=VERT, parcel='surface', depth=None,
                     parcel_values=None, moist=None, **cape_cin_options):
     """CAPE and CIN [J/kg] of every column over 1 ... 4 layers of one ascent: `layers` as numpy_api.cape_cin_layers takes
@@ -40,23 +35,23 @@ def cape_cin_layers(pressure, temperature, dewpoint, layers, height=None, vert_d
     top_pressure under the leading dim 'layer', and total_cape, total_cin, lfc_pressure, el_pressure, lcl_pressure and
     status on the horizontal dims.  A layer with a NaN top or top >= bottom is NaN."""
     g = _Grid(pressure, vert_dim)
-    specs = [{k: _values(g, v) for k, v in l.items()} for l in layers]
-    pv = None if parcel_values is None else [_values(g, x) for x in parcel_values]
+    specs = [{k: g.per_col(v) for k, v in l.items()} for l in layers]
+    pv = None if parcel_values is None else [g.per_col(x) for x in parcel_values]
     res = _device(_api.cape_cin_layers, g.values(pressure), g.values(temperature), g.values(dewpoint), specs,
-                  height=None if height is None else g.values(height), parcel=parcel, depth=depth, parcel_values=pv,
+                  height=g.per_col(height), parcel=parcel, depth=depth, parcel_values=pv,
                   moist=moist, **cape_cin_options)
-    coords = dict(g.coords, layer=np.arange(len(specs)))
-    out = {k: DataArray(_host(res[k]), dims=('layer',) + g.dims, coords=coords, attrs=dict(_ATTRS[k]), name=k) for k in _PER_LAYER}
-    out.update({k: g.horiz(_host(res[k]), k, _ATTRS[k]) for k in _PER_COLUMN})
-    return Dataset(out)
+    out = g.dataset(res, _PER_LAYER, _ATTRS.get, vert=True, vcoord=np.arange(len(specs)), dim='layer')
+    for k in _PER_COLUMN:
+        out[k] = g.horiz(res[k], k, _ATTRS[k])
+    return out
 
 
 def _one(fn, name, pressure, temperature, dewpoint, height, vert_dim, kwargs):
     g = _Grid(pressure, vert_dim)
     if kwargs.get('parcel_values') is not None:
-        kwargs = dict(kwargs, parcel_values=[_values(g, x) for x in kwargs['parcel_values']])
+        kwargs = dict(kwargs, parcel_values=[g.per_col(x) for x in kwargs['parcel_values']])
     res = _device(fn, g.values(pressure), g.values(temperature), g.values(dewpoint), g.values(height), **kwargs)
-    return g.horiz(_host(res), name, _ATTRS[name])
+    return g.horiz(res, name, _ATTRS[name])
 
 
 def cape_3km(pressure, temperature, dewpoint, height, vert_dim=VERT, **kwargs):

@@ -19,6 +19,7 @@ There is no CPU path here: every function ends in a kernel launch.
 """
 import ctypes as C
 import functools
+import math
 
 import numpy as np
 
@@ -49,9 +50,11 @@ class _Call:
       live in the same space;
     - device and stream: the library runs on that device, on torch's current stream of that device (not of torch's
       current device); host calls use the NULL stream.
-    `ins` holds the inputs in that dtype and space.  Every array the call stages is kept alive as long as the call."""
+    `ins` holds the inputs in that dtype and space; an absent input (None) is left out (views() puts it back).  Every array
+    the call stages is kept alive as long as the call."""
 
     def __init__(self, *xs):
+        xs = [x for x in xs if x is not None]
         devs = [x.device for x in xs if _is_torch(x) and x.is_cuda]
         assert all(d == devs[0] for d in devs), 'all device tensors of one call must live on the same GPU'
         self.device = devs[0] if devs else None
@@ -64,7 +67,7 @@ class _Call:
         # the grid: the first input, (nlev, ...) with `hshape` the horizontal shape of its ncol columns
         shape = tuple(self.ins[0].shape)
         self.nlev, self.hshape = (shape[0], shape[1:]) if shape else (1, ())
-        self.ncol = int(np.prod(self.hshape))
+        self.ncol = math.prod(self.hshape)
 
     def array(self, x, dtype=None):
         """x as a contiguous array of `dtype` (default: the call's) in the call's memory space."""
@@ -78,14 +81,15 @@ class _Call:
         self._keep.append(a)
         return a
 
-    def per_col(self, x):
-        """Per-column argument (a scalar, broadcast, or one value per column of the grid) -> ncol elements."""
+    def per_col(self, x, n=None, msg='per-column argument does not match the grid'):
+        """Per-column argument (a scalar, broadcast, or one value per column of the grid) -> n elements (default: ncol)."""
+        n = self.ncol if n is None else n
         if not _is_torch(x):
             x = np.asarray(x, dtype=self.dtype).reshape(-1)
-            if x.size == 1 and self.ncol != 1:
-                x = np.full(self.ncol, x[0], dtype=self.dtype)
+            if x.size == 1 and n != 1:
+                x = np.full(n, x[0], dtype=self.dtype)
         a = self.array(x).reshape(-1)
-        assert int(np.prod(a.shape)) == self.ncol, 'per-column argument does not match the grid'
+        assert int(np.prod(a.shape)) == n, msg
         return a
 
     def mask(self, m, shape):
@@ -95,8 +99,13 @@ class _Call:
     def view(self, a, nlev=None, ncol=None):
         """xp_view of a staged array, (nlev, ...) as (nlev, ncol) unless given."""
         nlev = a.shape[0] if nlev is None else nlev
-        ncol = int(np.prod(a.shape[1:])) if ncol is None else ncol
+        ncol = math.prod(a.shape[1:]) if ncol is None else ncol
         return L.View(_ptr(a), self.xp_dtype, self.mem, nlev, ncol, ncol, 1)
+
+    def views(self, given):
+        """The xp_views of the call's leading inputs, laid out as the arguments `given` they were: None where one is absent."""
+        ins = iter(self.ins)
+        return [None if x is None else self.view(next(ins)) for x in given]
 
     def out(self, shape, dtype=None):
         dtype = dtype or self.dtype
@@ -104,22 +113,39 @@ class _Call:
             return np.empty(shape, dtype=dtype)
         return torch.empty(shape, dtype=_TORCH_DTYPE[dtype], device=self.device)
 
+    def struct(self, out_type, per_col=(), layered=(), n=0, per_level=(), nlev=None):
+        """An output struct of `out_type` and the outputs it points at, as (struct, dict name -> array), allocated in this
+        order: for each name in `layered` an (n, ...) array, its field holding one pointer per layer; in `per_col` one value
+        per column (int32 for the names in L.INT32_OUT, the call's dtype otherwise); in `per_level` an (nlev, ...) array
+        (nlev: the grid's unless given).  dtype and mem are set where the struct has them."""
+        out = out_type(dtype=self.xp_dtype, mem=self.mem) if hasattr(out_type, 'dtype') else out_type()
+        res = {}
+        for k in layered:
+            a = res[k] = self.out((n,) + self.hshape)
+            rows = getattr(out, k)
+            for i in range(n):
+                rows[i] = _ptr(a[i:i + 1])               # (a[i] of a grid without horizontal dims is no array)
+        for k in per_col:
+            a = res[k] = self.out(self.hshape, np.int32 if k in L.INT32_OUT else None)
+            setattr(out, k, _ptr(a))
+        if per_level:
+            shape = (self.nlev if nlev is None else nlev,) + self.hshape
+            for k in per_level:
+                a = res[k] = self.out(shape)
+                setattr(out, k, _ptr(a))
+        return out, res
+
     def scalars(self, names, shape):
-        """xp_scalars_out with an output of `shape` for each of `names` (int32 for indices and status)."""
-        so = L.ScalarsOut(dtype=self.xp_dtype, mem=self.mem)
-        out = {k: self.out(shape, np.int32 if k in L.SCALAR_I else None) for k in names}
-        for k, a in out.items():
-            setattr(so, k, _ptr(a))
-        return so, out
+        """xp_scalars_out with an output of `shape`, the grid's horizontal shape, for each of `names`."""
+        assert shape == self.hshape
+        return self.struct(L.ScalarsOut, names)
 
     def profile(self, names, nlev_out, shape, lifted_index_at=None):
         """xp_profile_out with an (nlev_out,) + shape output for each of `names` and, with lifted_index_at, the lifted index
         (one per column, under 'lifted_index')."""
-        ncol = int(np.prod(shape))
-        po = L.ProfileOut(dtype=self.xp_dtype, mem=self.mem, nlev_out=nlev_out, lev_stride=ncol, col_stride=1)
-        out = {k: self.out((nlev_out,) + shape) for k in names}
-        for k, a in out.items():
-            setattr(po, k, _ptr(a))
+        assert shape == self.hshape
+        po, out = self.struct(L.ProfileOut, per_level=names, nlev=nlev_out)
+        po.nlev_out, po.lev_stride, po.col_stride = nlev_out, self.ncol, 1
         if lifted_index_at is not None:
             out['lifted_index'] = self.out(shape)
             po.lifted_index, po.lifted_index_pressure = _ptr(out['lifted_index']), float(lifted_index_at)
@@ -177,16 +203,48 @@ def set_moist_lapse(mode):
     _DEFAULT['moist'] = mode
 
 
-def _over_ground(pressure, temperature, dewpoint, ground):
-    """A ground= call (XP_PARCEL_OVER_GROUND, include/xparcel.h): its _Call, whose grid is temperature's, the xp_views of
-    pressure, temperature and moisture, and the three per-column surface arrays.  A pressure of the nlev isobars is expanded
-    on the host (_on_grid), or, as a device tensor, passed as it is: a view whose col_stride is 0."""
+def _same_shape(arrays, msg):
+    """Assert, with the caller's message, that the arrays share the first one's shape."""
+    shape = arrays[0].shape
+    for a in arrays:
+        assert a.shape == shape, msg
+
+
+def _is_isobars(pressure, like):
+    """Whether `pressure` holds just the nlev isobars of the (nlev, ...) grid of `like` (isobaric data)."""
+    if len(np.shape(pressure)) != 1 or len(np.shape(like)) <= 1:
+        return False
+    assert np.shape(pressure)[0] == np.shape(like)[0], 'a 1-D pressure must have one value per level'
+    return True
+
+
+def _on_grid(pressure, like):
+    """A 1-D pressure of nlev values (isobaric data) on the (nlev, ...) grid of `like`, in pressure's own space."""
+    shape = tuple(like.shape)
+    col = (-1,) + (1,) * (len(shape) - 1)
+    if _is_torch(pressure):
+        return pressure.reshape(col).expand(shape)
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(pressure).reshape(col), shape))
+
+
+def _full_pressure(pressure, like):
+    """The pressure of isobaric data (_is_isobars) expanded onto the grid of `like`; any other pressure as it is."""
+    return _on_grid(pressure, like) if _is_isobars(pressure, like) else pressure
+
+
+def _sounding(pressure, temperature, dewpoint, ground=None):
+    """The sounding of a CAPE-family call: its _Call, the xp_views of pressure, temperature and moisture, and the surface:
+    None, or, for a ground= call (XP_PARCEL_OVER_GROUND, include/xparcel.h), the three per-column surface arrays.  The grid
+    of a ground= call is temperature's; its pressure may be the nlev isobars, which are expanded on the host (_full_pressure), or,
+    as a device tensor, passed as they are: a view whose col_stride is 0."""
+    if ground is None:
+        c = _Call(pressure, temperature, dewpoint)
+        _same_shape(c.ins, 'pressure, temperature, dewpoint must share a shape')
+        return c, tuple(map(c.view, c.ins)), None
     assert len(ground) == 3, 'ground: (surface_pressure, surface_temperature, surface_dewpoint)'
-    isobars = len(np.shape(pressure)) == 1 and len(np.shape(temperature)) > 1
-    if isobars:
-        assert np.shape(pressure)[0] == np.shape(temperature)[0], 'a 1-D pressure must have one value per level'
-        if not (_is_torch(pressure) and pressure.is_cuda):
-            pressure, isobars = _on_grid(pressure, temperature), False
+    isobars = _is_isobars(pressure, temperature) and _is_torch(pressure) and pressure.is_cuda
+    if not isobars:
+        pressure = _full_pressure(pressure, temperature)
     c = _Call(temperature, dewpoint, pressure, *[x for x in ground if _is_torch(x)])
     t, td, p = c.ins[:3]
     assert t.shape == td.shape and (isobars or p.shape == t.shape), 'pressure, temperature, dewpoint must share a shape'
@@ -197,11 +255,20 @@ def _over_ground(pressure, temperature, dewpoint, ground):
     return c, (pv, c.view(t), c.view(td)), [c.per_col(x) for x in ground]
 
 
-def _ground_parcel(pc, surface):
-    """Set XP_PARCEL_OVER_GROUND and the surface arrays on the xp_parcel `pc`."""
-    assert pc.mode != L.PARCEL['explicit'], 'ground: not with an explicit parcel'
-    pc.mode |= L.PARCEL_OVER_GROUND
-    pc.pressure, pc.temperature, pc.dewpoint = (_ptr(x) for x in surface)
+def _parcel(c, name, depth=None, parcel_values=None, surface=None):
+    """The xp_parcel `name` of a call: `depth` [hPa] defaults to the reference's; an explicit parcel points at its
+    (pressure, temperature, dewpoint) `parcel_values`, one per column, staged on `c`; with the `surface` arrays of a ground=
+    call (_sounding) it carries XP_PARCEL_OVER_GROUND and points at those."""
+    if depth is None:
+        depth = 300.0 if name == 'most_unstable' else 100.0                # pf.py:1558, 1652
+    pc = L.Parcel(L.PARCEL[name], 0, float(depth), None, None, None)
+    if name == 'explicit':
+        pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in parcel_values)
+    if surface is not None:
+        assert name != 'explicit', 'ground: not with an explicit parcel'
+        pc.mode |= L.PARCEL_OVER_GROUND
+        pc.pressure, pc.temperature, pc.dewpoint = (_ptr(x) for x in surface)
+    return pc
 
 
 def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=None, parcel_values=None,
@@ -221,13 +288,7 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     at its surface pressure: the surface values become level 0, the levels above the ground follow, NaN fills the rest.
     Every result is that of the call on those re-based columns: the indices count their rows, and the profile has
     nlev + 2 rows.  Not with an explicit parcel, nor with compute='float32'."""
-    if ground is None:
-        c = _Call(pressure, temperature, dewpoint)
-        p, t, td = c.ins
-        assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-        views = (c.view(p), c.view(t), c.view(td))
-    else:
-        c, views, surface = _over_ground(pressure, temperature, dewpoint, ground)
+    c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     moist = moist or _DEFAULT['moist']
     if compute is None:
         compute = _DEFAULT['compute']
@@ -237,13 +298,7 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     if compute == 'float32' and want is None:
         want = COMPUTE32_WANT
     o = _opts(moist=moist, compute=compute, **kwargs)
-    if depth is None:
-        depth = 300.0 if parcel == 'most_unstable' else 100.0                # pf.py:1558, 1652
-    pc = L.Parcel(L.PARCEL[parcel], 0, float(depth), None, None, None)
-    if parcel == 'explicit':
-        pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in parcel_values)
-    if ground is not None:
-        _ground_parcel(pc, surface)
+    pc = _parcel(c, parcel, depth, parcel_values, surface)
     so, res = c.scalars(L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want), c.hshape)
     po = None
     if want_profile or lifted_index_at is not None:
@@ -267,27 +322,16 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
     fused=True (XP_OPT_FUSE_PARCELS; moist='family', two parcels): one pass over the grid for both -- same numbers,
     measured slower than a pass per parcel on MI355X, hence opt-in.
     ground: as in cape_cin_columns; the grid is cut at the ground once for all the parcels."""
-    if ground is None:
-        c = _Call(pressure, temperature, dewpoint)
-        p, t, td = c.ins
-        assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-        views = (c.view(p), c.view(t), c.view(td))
-    else:
-        c, views, surface = _over_ground(pressure, temperature, dewpoint, ground)
+    c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
     o.flags = L.OPT_FUSE_PARCELS if fused else 0
-    specs = []
+    pcs = []
     for pc in parcels:
         name, depth = (pc, None) if isinstance(pc, str) else (pc[0], pc[1])
         assert name in ('surface', 'most_unstable', 'mixed_layer'), 'parcels: surface, most_unstable or mixed_layer'
-        if depth is None:
-            depth = 300.0 if name == 'most_unstable' else 100.0                # pf.py:1558, 1652
-        specs.append((name, float(depth)))
-    n = len(specs)
-    pcs = (L.Parcel * n)(*[L.Parcel(L.PARCEL[nm], 0, dp, None, None, None) for nm, dp in specs])
-    if ground is not None:
-        for pc in pcs:
-            _ground_parcel(pc, surface)
+        pcs.append(_parcel(c, name, depth, surface=surface))
+    n = len(pcs)
+    pcs = (L.Parcel * n)(*pcs)
     names = L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want)
     sos = (L.ScalarsOut * n)()
     pos = (L.ProfileOut * n)() if lifted_index_at is not None else None
@@ -357,15 +401,9 @@ def parcel_profile_with_lcl(pressure, temperature, dewpoint, parcel_pressure, pa
 
 
 def _select(pressure, temperature, dewpoint, mode, depth, ground=None):
-    pc = L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None)
-    if ground is None:
-        c = _Call(pressure, temperature, dewpoint)
-        views = tuple(map(c.view, c.ins))
-    else:
-        c, views, surface = _over_ground(pressure, temperature, dewpoint, ground)
-        _ground_parcel(pc, surface)
+    c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     so, out = c.scalars(L.SCALAR_P + ('parcel_index',), c.hshape)
-    c.run('xp_select_parcel', *views, pc, so)
+    c.run('xp_select_parcel', *views, _parcel(c, mode, depth, surface=surface), so)
     return {'pressure': out['parcel_pressure'], 'temperature': out['parcel_temperature'],
             'dewpoint': out['parcel_dewpoint'], 'index': out['parcel_index']}
 
@@ -469,17 +507,9 @@ def downdraft_cape(pressure, temperature, dewpoint, bottom=700.0, depth=200.0, m
     and 'status' (ST_LCL_NOT_CONVERGED, XP_ST_NO_LAYER: the column does not span the layer, everything NaN); with
     want_profile also 'parcel_temperature', the descending parcel on the levels with p >= p0 (NaN elsewhere), shaped like
     the input."""
-    c = _Call(pressure, temperature, dewpoint)
-    p, t, td = c.ins
-    assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
-    res = {k: c.out(c.hshape, np.int32 if k == 'status' else None) for k in L.DCAPE_OUT[:4]}
-    if want_profile:
-        res['parcel_temperature'] = c.out(p.shape)
-    out = L.DcapeOut(dtype=c.xp_dtype, mem=c.mem)
-    for k, a in res.items():
-        setattr(out, k, _ptr(a))
-    c.run('xp_downdraft_cape', c.view(p), c.view(t), c.view(td), float(bottom), float(depth),
-          L.MOIST[moist or _DEFAULT['moist']], out)
+    c, views, _ = _sounding(pressure, temperature, dewpoint)
+    out, res = c.struct(L.DcapeOut, L.DCAPE_OUT[:4], per_level=L.DCAPE_OUT[4:] if want_profile else ())
+    c.run('xp_downdraft_cape', *views, float(bottom), float(depth), L.MOIST[moist or _DEFAULT['moist']], out)
     return res
 
 
@@ -497,18 +527,13 @@ def effective_inflow_layer(pressure, temperature, dewpoint, height=None, cape_mi
     'candidate_cape', 'candidate_cin', shaped like the input: what was computed for every level that was lifted, NaN
     elsewhere."""
     assert 'humidity' not in cape_cin_options, 'effective_inflow_layer takes dewpoints'
-    c = _Call(*((pressure, temperature, dewpoint) + (() if height is None else (height,))))
-    p, t, td = c.ins[:3]
-    assert all(a.shape == p.shape for a in c.ins), 'pressure, temperature, dewpoint, height must share a shape'
+    c = _Call(pressure, temperature, dewpoint, height)
+    _same_shape(c.ins, 'pressure, temperature, dewpoint, height must share a shape')
     o = _opts(moist=moist or _DEFAULT['moist'], **cape_cin_options)
-    res = {k: c.out(c.hshape, np.int32 if k in L.EFFECTIVE_I else None) for k in L.EFFECTIVE_F + L.EFFECTIVE_I}
-    if want_candidates:
-        res.update({k: c.out(p.shape) for k in L.EFFECTIVE_CANDIDATES})
-    out = L.EffectiveLayerOut(dtype=c.xp_dtype, mem=c.mem)
-    for k, a in res.items():
-        setattr(out, k, _ptr(a))
-    c.run('xp_effective_inflow_layer', c.view(p), c.view(t), c.view(td), None if height is None else c.view(c.ins[3]),
-          float(cape_min), float(cin_min), float(search_depth), o, out)
+    out, res = c.struct(L.EffectiveLayerOut, L.EFFECTIVE_F + L.EFFECTIVE_I,
+                        per_level=L.EFFECTIVE_CANDIDATES if want_candidates else ())
+    c.run('xp_effective_inflow_layer', *c.views((pressure, temperature, dewpoint, height)), float(cape_min), float(cin_min),
+          float(search_depth), o, out)
     return res
 
 
@@ -572,30 +597,17 @@ def cape_cin_layers(pressure, temperature, dewpoint, layers, height=None, parcel
     assert all(set(l) <= {s + k for s in ('bottom', 'top') for k in _LAYER_BOUND_KEYS} for l in layers), 'layers: unknown key'
     bound_arrays = [v for l in layers for v in l.values() if _is_torch(v)]
     pv = list(parcel_values) if parcel == 'explicit' else []
-    c = _Call(*((pressure, temperature, dewpoint) + (() if height is None else (height,))), *[x for x in pv + bound_arrays if _is_torch(x)])
+    c = _Call(pressure, temperature, dewpoint, height, *[x for x in pv + bound_arrays if _is_torch(x)])
     p, t, td = c.ins[:3]
     z = None if height is None else c.ins[3]
-    assert p.shape == t.shape == td.shape and (z is None or z.shape == p.shape), 'pressure, temperature, dewpoint, height must share a shape'
+    _same_shape(c.ins[:3 if z is None else 4], 'pressure, temperature, dewpoint, height must share a shape')
     o = _opts(moist=moist or _DEFAULT['moist'], **cape_cin_options)
-    if depth is None:
-        depth = 300.0 if parcel == 'most_unstable' else 100.0                # pf.py:1558, 1652
-    pc = L.Parcel(L.PARCEL[parcel], 0, float(depth), None, None, None)
-    if parcel == 'explicit':
-        pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in pv)
+    pc = _parcel(c, parcel, depth, pv)
     by_height = any(l.get(s + '_height') is not None for l in layers for s in ('bottom', 'top'))
     z0 = _lowest_valid_height(p, z) if by_height and z is not None else None
     bottoms = [_layer_bound(c, l, 'bottom', p, t, z, z0) for l in layers]
     tops = [_layer_bound(c, l, 'top', p, t, z, z0) for l in layers]
-    res = {k: c.out((n,) + c.hshape) for k in L.CAPE_LAYERS_OUT}
-    res.update({k: c.out(c.hshape) for k in L.CAPE_LAYERS_TOTAL})
-    res['status'] = c.out(c.hshape, np.int32)
-    out = L.CapeLayersOut(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in L.CAPE_LAYERS_OUT:
-        arr = getattr(out, k)
-        for i in range(n):
-            arr[i] = _ptr(res[k][i])
-    for k in L.CAPE_LAYERS_TOTAL:
-        setattr(out, k, _ptr(res[k]))
+    out, res = c.struct(L.CapeLayersOut, L.CAPE_LAYERS_TOTAL + ('status',), L.CAPE_LAYERS_OUT, n)
     c.run('xp_cape_cin_layers', c.view(p), c.view(t), c.view(td), pc, o, n,
           (C.c_void_p * n)(*[None if b is None else _ptr(b) for b in bottoms]), (C.c_void_p * n)(*map(_ptr, tops)), out)
     nan = c.out(c.hshape)
@@ -636,7 +648,7 @@ def interp_levels(coords, variables, ats, log=False):
     c = _Call(coords, *variables)
     cds, xs = c.ins[0], c.ins[1:]
     assert 1 <= len(xs) <= 4 and 1 <= len(ats) <= 4, 'one to four variables, one to four coordinates'
-    assert all(x.shape == cds.shape for x in xs), 'coords and variables must share a shape'
+    _same_shape(c.ins, 'coords and variables must share a shape')
     vptrs = (C.POINTER(L.View) * len(xs))(*[C.pointer(c.view(x)) for x in xs])
     outs = [[c.out(c.hshape) for _ in ats] for _ in xs]
     optrs = (C.c_void_p * (len(xs) * len(ats)))(*[_ptr(o) for row in outs for o in row])
@@ -648,9 +660,8 @@ def interp_levels(coords, variables, ats, log=False):
 def dewpoint_from_specific_humidity(pressure, temperature, specific_humidity):
     """metpy.calc.dewpoint_from_specific_humidity, MetPy 1.4.1 chain (parcel_test.py:262-266, pf.py:1889), K."""
     c = _Call(pressure, temperature, specific_humidity)
-    p, t, q = c.ins
-    assert p.shape == t.shape == q.shape, 'pressure, temperature, specific_humidity must share a shape'
-    out = c.out(p.shape)
+    _same_shape(c.ins, 'pressure, temperature, specific_humidity must share a shape')
+    out = c.out(c.ins[0].shape)
     c.run('xp_dewpoint_from_specific_humidity', *map(c.view, c.ins), out)
     return out
 
@@ -658,10 +669,10 @@ def dewpoint_from_specific_humidity(pressure, temperature, specific_humidity):
 def mixing_ratio(temperature, dewpoint, pressure):
     """pf.py:684: RH(T, Td) x saturation mixing ratio at (p, T) [kg/kg]."""
     c = _Call(temperature, dewpoint, pressure)
-    t, td, p = c.ins
-    assert t.shape == td.shape == p.shape, 'temperature, dewpoint, pressure must share a shape'
-    n = int(np.prod(t.shape))
-    out = c.out(t.shape)
+    _same_shape(c.ins, 'temperature, dewpoint, pressure must share a shape')
+    shape = c.ins[0].shape
+    n = int(np.prod(shape))
+    out = c.out(shape)
     c.run('xp_mixing_ratio', *[c.view(a, 1, n) for a in c.ins], out)
     return out
 
@@ -692,10 +703,9 @@ def insert_level(d, level, coords='pressure', fill_value=-999):
     out = {}
     for k in level.keys():
         c = _Call(d[coords], d[k])
-        cds, v = c.ins
-        assert cds.shape == v.shape, 'variables of a dataset must share a shape'
+        _same_shape(c.ins, 'variables of a dataset must share a shape')
         out[k] = c.out((c.nlev + 1,) + c.hshape)
-        c.run('xp_insert_level', c.view(cds), c.view(v), c.per_col(level[coords]), c.per_col(level[k]), float(fill_value),
+        c.run('xp_insert_level', *map(c.view, c.ins), c.per_col(level[coords]), c.per_col(level[k]), float(fill_value),
               out[k])
     return out
 
@@ -705,11 +715,10 @@ INTERSECTION_KEYS = ('all_intersect_x', 'all_intersect_y', 'increasing_x', 'incr
 
 def find_intersections(x, a, b=None, log_x=False):
     """pf.py:992: dict of six (nlev - 1, ...) arrays; entry i belongs to the interval between levels i and i + 1."""
-    c = _Call(*((x, a) if b is None else (x, a, b)))
-    assert all(h.shape == c.ins[0].shape for h in c.ins), 'x, a, b must share a shape'
+    c = _Call(x, a, b)
+    _same_shape(c.ins, 'x, a, b must share a shape')
     out = {k: c.out((c.nlev - 1,) + c.hshape) for k in INTERSECTION_KEYS}
-    c.run('xp_find_intersections', c.view(c.ins[0]), c.view(c.ins[1]), c.view(c.ins[2]) if b is not None else None,
-          int(bool(log_x)), (C.c_void_p * 6)(*map(_ptr, out.values())))
+    c.run('xp_find_intersections', *c.views((x, a, b)), int(bool(log_x)), (C.c_void_p * 6)(*map(_ptr, out.values())))
     return out
 
 
@@ -719,10 +728,9 @@ def trapz(dat, x, mask=None, only_positive=False, only_negative=False):
     if isinstance(dat, dict):
         return {k: trapz(v, x, mask=mask, only_positive=only_positive, only_negative=only_negative) for k, v in dat.items()}
     c = _Call(dat, x)
-    d, xh = c.ins
-    assert d.shape == xh.shape, 'dat and x must share a shape'
+    _same_shape(c.ins, 'dat and x must share a shape')
     out = c.out(c.hshape)
-    c.run('xp_trapz', c.view(d), c.view(xh), None if mask is None else c.mask(mask, (max(c.nlev - 1, 0), c.ncol)),
+    c.run('xp_trapz', *map(c.view, c.ins), None if mask is None else c.mask(mask, (max(c.nlev - 1, 0), c.ncol)),
           int(bool(only_positive)), int(bool(only_negative)), out)
     return out
 
@@ -736,11 +744,10 @@ def trap_around_zeros(x, y, log_x=True, start=0):
     True where no area was taken out of an interval."""
     assert start == 0, 'only start=0 is implemented (the reference never passes anything else)'
     c = _Call(x, y)
-    xh, yh = c.ins
-    assert xh.shape == yh.shape, 'x and y must share a shape'
+    _same_shape(c.ins, 'x and y must share a shape')
     areas = {k: c.out((2 * c.nlev - 1,) + c.hshape) for k in AREA_KEYS}
-    mask = c.out(xh.shape, np.uint8)
-    c.run('xp_trap_around_zeros', c.view(xh), c.view(yh), int(bool(log_x)), (C.c_void_p * 5)(*map(_ptr, areas.values())),
+    mask = c.out(c.ins[0].shape, np.uint8)
+    c.run('xp_trap_around_zeros', *map(c.view, c.ins), int(bool(log_x)), (C.c_void_p * 5)(*map(_ptr, areas.values())),
           mask)
     return areas, mask != 0
 
@@ -759,10 +766,9 @@ def get_layer(dat, depth=100, interpolate=True):
     out = {}
     for k, v in dat.items():
         c = _Call(dat['pressure'], v)
-        p, x = c.ins
-        assert p.shape == x.shape, 'variables of a dataset must share a shape'
+        _same_shape(c.ins, 'variables of a dataset must share a shape')
         out[k] = c.out((c.nlev + (1 if interpolate else 0),) + c.hshape)
-        c.run('xp_get_layer', c.view(p), c.view(x), float(depth), int(bool(interpolate)), int(k == 'pressure'), out[k])
+        c.run('xp_get_layer', *map(c.view, c.ins), float(depth), int(bool(interpolate)), int(k == 'pressure'), out[k])
     return out
 
 
@@ -772,23 +778,19 @@ def shift_out_nans(x, name):
     out = {}
     for k, v in x.items():
         c = _Call(x[name], v)
-        nh, vh = c.ins
-        assert nh.shape == vh.shape, 'variables of a dataset must share a shape'
-        out[k] = c.out(nh.shape)
-        c.run('xp_shift_out_nans', c.view(nh), c.view(vh), out[k])
+        _same_shape(c.ins, 'variables of a dataset must share a shape')
+        out[k] = c.out(c.ins[0].shape)
+        c.run('xp_shift_out_nans', *map(c.view, c.ins), out[k])
     return out
 
 
 def _rebase(pressure, temperature, dewpoint, mode, depth):
-    c = _Call(pressure, temperature, dewpoint)
-    p, t, td = c.ins
-    assert p.shape == t.shape == td.shape, 'pressure, temperature, dewpoint must share a shape'
+    c, views, _ = _sounding(pressure, temperature, dewpoint)
     so, par = c.scalars(L.SCALAR_P + ('parcel_index',), c.hshape)
     outs = [c.out((c.nlev + (1 if mode == 'mixed_layer' else 0),) + c.hshape) for _ in range(3)]
     kept = np.zeros(c.nlev, dtype=np.int32)
     nout = C.c_int64(0)
-    c.run('xp_rebase_profile', c.view(p), c.view(t), c.view(td), L.Parcel(L.PARCEL[mode], 0, float(depth), None, None, None),
-          *outs, so, kept, C.byref(nout))
+    c.run('xp_rebase_profile', *views, _parcel(c, mode, depth), *outs, so, kept, C.byref(nout))
     n = nout.value
     parcel = {'pressure': par['parcel_pressure'], 'temperature': par['parcel_temperature'],
               'dewpoint': par['parcel_dewpoint'], 'index': par['parcel_index']}
@@ -930,8 +932,7 @@ def _flat(hs):
 def wind_shear(surface_wind_u, surface_wind_v, wind_u, wind_v, height, shear_height=6000):
     """pf.py:2216: wind at `shear_height` (linear interpolation in height) minus the surface wind (xp_wind_shear)."""
     c = _Call(wind_u, wind_v, height)
-    wu, wv, hh = c.ins
-    assert wu.shape == wv.shape == hh.shape, 'wind_u, wind_v, height must share a shape'
+    _same_shape(c.ins, 'wind_u, wind_v, height must share a shape')
     res = {k: c.out(c.hshape) for k in ('shear_u', 'shear_v', 'shear_magnitude')}
     pos = c.out(c.hshape, np.int32)
     c.run('xp_wind_shear', *map(c.view, c.ins), c.per_col(surface_wind_u), c.per_col(surface_wind_v), float(shear_height),
@@ -951,35 +952,25 @@ def bunkers_storm_motion(pressure, u, v, height):
     'mean_v' [m/s] and 'status' (XP_ST_NO_LAYER: the column does not reach 6 km above its lowest level; ST_BAD_HEIGHT /
     ST_BAD_PRESSURE: the levels are out of order; everything NaN)."""
     c = _Call(pressure, u, v, height)
-    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, u, v, height must share a shape'
-    res = {k: c.out(c.hshape, np.int32 if k == 'status' else None) for k in L.STORM_MOTION_OUT}
-    out = L.StormMotionOut(dtype=c.xp_dtype, mem=c.mem)
-    for k, a in res.items():
-        setattr(out, k, _ptr(a))
+    _same_shape(c.ins, 'pressure, u, v, height must share a shape')
+    out, res = c.struct(L.StormMotionOut, L.STORM_MOTION_OUT)
     c.run('xp_bunkers_storm_motion', *map(c.view, c.ins), out)
     return res
 
 
 def _helicity(entry, height, u, v, per_col, storm, surface, n, many, keys, out_type, bounds):
     """What the two helicity calls share: the _Call (CUDA tensors among the per-column arguments decide the device), the
-    storm and surface wind per column, one output per key and layer (with a leading axis if `many`) and the status.
+    storm and surface wind per column, one output per key with a leading axis of the n layers (if `many`) and the status.
     bounds(cols), cols being per_col as per-column arrays: the entry point's own arguments between the storm motion and the
     output struct."""
     assert (surface[0] is None) == (surface[1] is None), 'surface_u, surface_v: give both or neither'
     c = _Call(height, u, v, *[x for x in (*per_col, *storm, *surface) if _is_torch(x)])
-    z, wu, wv = c.ins[:3]
-    assert z.shape == wu.shape == wv.shape, 'height, u, v must share a shape'
+    _same_shape(c.ins[:3], 'height, u, v must share a shape')
     sfc = [None, None] if surface[0] is None else [c.per_col(x) for x in surface]
-    res = {k: c.out(((n,) if many else ()) + c.hshape) for k in keys}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = out_type(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in keys:
-        arr = getattr(out, k)
-        for i in range(n):
-            arr[i] = _ptr(res[k][i] if many else res[k])
+    out, res = c.struct(out_type, ('status',), keys, n)
     cols = [c.per_col(x) for x in per_col]
-    c.run(entry, c.view(z), c.view(wu), c.view(wv), *sfc, *[c.per_col(x) for x in storm], *bounds(cols), out)
-    return res
+    c.run(entry, *map(c.view, c.ins[:3]), *sfc, *[c.per_col(x) for x in storm], *bounds(cols), out)
+    return res if many else {k: a.reshape(c.hshape) for k, a in res.items()}
 
 
 def storm_relative_helicity(height, u, v, depth, bottom=0.0, storm_u=0.0, storm_v=0.0, surface_u=None, surface_v=None):
@@ -1047,19 +1038,6 @@ def _wind_layer(spec):
     return kinds[kind], float('nan') if bottom is None else float(bottom), float(top)
 
 
-def _layers_out(c, out_type, keys, n):
-    """What wind_layers and thermo_layers return, and the entry point's output struct pointing into it: one array per key with
-    a leading axis of the n layers, and the per-column 'status'."""
-    res = {k: c.out((n,) + c.hshape) for k in keys}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = out_type(dtype=c.xp_dtype, mem=c.mem, status=_ptr(res['status']))
-    for k in keys:
-        arr = getattr(out, k)
-        for i in range(n):
-            arr[i] = _ptr(res[k][i:i + 1])
-    return res, out
-
-
 def wind_layers(pressure, u, v, height=None, layers=(), want=None):
     """The wind over up to four layers of every column in one pass (xp_wind_layers): pressure [hPa], u, v [m/s] and, for
     layers given by height, height [m] on one vertical, (nlev, ...).  `layers`: a sequence of layers, each a dict or a tuple
@@ -1074,12 +1052,11 @@ def wind_layers(pressure, u, v, height=None, layers=(), want=None):
     assert height is not None or all(k != L.LAYER_HEIGHT for k, _, _ in specs), 'a layer given by height needs height'
     keys = L.WIND_LAYERS_OUT if want is None else tuple(want)
     assert set(keys) <= set(L.WIND_LAYERS_OUT), 'want: unknown output'
-    c = _Call(pressure, u, v, *(() if height is None else (height,)))
-    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, u, v, height must share a shape'
+    c = _Call(pressure, u, v, height)
+    _same_shape(c.ins, 'pressure, u, v, height must share a shape')
     n = len(specs)
-    res, out = _layers_out(c, L.WindLayersOut, keys, n)
-    views = [c.view(a) for a in c.ins] + [None]
-    c.run('xp_wind_layers', *views[:4], n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]), out)
+    out, res = c.struct(L.WindLayersOut, ('status',), keys, n)
+    c.run('xp_wind_layers', *c.views((pressure, u, v, height)), n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]), out)
     return res
 
 
@@ -1114,15 +1091,10 @@ def _per_point(entry, ins, per_col, nout, extra=()):
     """A per-point entry point on the arrays `ins` (one shape) and the per-column arguments `per_col` (scalars broadcast;
     CUDA tensors among them take part in deciding the device): `nout` outputs of that shape."""
     c = _Call(*ins, *[x for x in per_col if _is_torch(x)])
-    assert all(a.shape == c.ins[0].shape for a in c.ins[:len(ins)]), 'per-point arguments must share a shape'
+    _same_shape(c.ins[:len(ins)], 'per-point arguments must share a shape')
     shape = tuple(c.ins[0].shape)
     n = int(np.prod(shape))
-    cols = []
-    for x in per_col:
-        if x is not None and not _is_torch(x) and np.ndim(x) == 0:
-            x = np.full(n, x, dtype=c.dtype)
-        cols.append(None if x is None else c.array(x).reshape(-1))
-    assert all(a is None or int(np.prod(a.shape)) == n for a in cols), 'per-point arguments must share a shape'
+    cols = [None if x is None else c.per_col(x, n, 'per-point arguments must share a shape') for x in per_col]
     outs = [c.out(shape) for _ in range(nout)]
     c.run(entry, n, c.xp_dtype, c.mem, *c.ins[:len(ins)], *cols, *extra, *outs)
     return outs
@@ -1206,17 +1178,15 @@ def thermo_layers(pressure, temperature=None, dewpoint=None, height=None, layers
         assert set(keys) <= set(L.THERMO_LAYERS_OUT), 'want: unknown output'
         for k in keys:
             assert all(given[v] is not None for v in L.THERMO_LAYERS_NEEDS[k]), '%s needs %s' % (k, ' and '.join(L.THERMO_LAYERS_NEEDS[k]))
-    names = ['pressure'] + [v for v in ('temperature', 'dewpoint', 'height') if given[v] is not None]
+    soundings = (pressure, temperature, dewpoint, height)
     bounds = [x for s in specs for x in s[3:] if _is_torch(x)]
-    c = _Call(pressure, *[given[v] for v in names[1:]], *bounds)
-    ins = dict(zip(names, c.ins))
-    assert all(a.shape == ins['pressure'].shape for a in ins.values()), 'pressure, temperature, dewpoint, height must share a shape'
-    res, out = _layers_out(c, L.ThermoLayersOut, keys, n)
+    c = _Call(*soundings, *bounds)
+    _same_shape(c.ins[:len(c.ins) - len(bounds)], 'pressure, temperature, dewpoint, height must share a shape')
+    out, res = c.struct(L.ThermoLayersOut, ('status',), keys, n)
     cols = [[None if s[j] is None else c.per_col(s[j]) for s in specs] for j in (3, 4)]
     bcols, tcols = (None if all(x is None for x in col) else (C.c_void_p * n)(*[None if x is None else _ptr(x) for x in col])
                     for col in cols)
-    views = [c.view(ins[v]) if v in ins else None for v in ('pressure', 'temperature', 'dewpoint', 'height')]
-    c.run('xp_thermo_layers', *views, n, (L.WindLayer * n)(*[L.WindLayer(s[0], 0, s[1], s[2]) for s in specs]), bcols, tcols, out)
+    c.run('xp_thermo_layers', *c.views(soundings), n, (L.WindLayer * n)(*[L.WindLayer(s[0], 0, s[1], s[2]) for s in specs]), bcols, tcols, out)
     return res
 
 
@@ -1249,7 +1219,7 @@ def hail_growth_zone_thickness(pressure, temperature, height):
     -30 degC crossing or the two come in the wrong order; from the lowest valid level where it has no -10 degC crossing."""
     c = _Call(pressure, temperature, height)
     p, t, z = c.ins
-    assert p.shape == t.shape == z.shape, 'pressure, temperature, height must share a shape'
+    _same_shape(c.ins, 'pressure, temperature, height must share a shape')
     spec = {'bottom_temperature': 263.15, 'top_temperature': 243.15}
     bottom, top = (_layer_bound(c, spec, side, p, t, z, None).reshape(c.hshape or (1,)) for side in ('bottom', 'top'))
     res = thermo_layers(p, t, None, z, layers=[{'bottom': bottom, 'top': top}], want=('thickness', 'lapse_rate'))
@@ -1290,15 +1260,10 @@ def sounding_indices(pressure, temperature, dewpoint, u=None, v=None, *, moist=N
         keys = tuple(want)
         assert set(keys) <= set(L.SOUNDING_OUT), 'want: unknown output'
         assert 'sweat_index' not in keys or u is not None, 'sweat_index needs u and v'
-    c = _Call(pressure, temperature, dewpoint, *([] if u is None else [u, v]))
-    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, temperature, dewpoint, u, v must share a shape'
-    res = {k: c.out(c.hshape) for k in keys}
-    res['status'] = c.out(c.hshape, np.int32)
-    out = L.SoundingOut(dtype=c.xp_dtype, mem=c.mem)
-    for k, a in res.items():
-        setattr(out, k, _ptr(a))
-    views = [c.view(a) for a in c.ins] + [None] * (5 - len(c.ins))
-    c.run('xp_sounding_indices', *views, L.SoundingOpts(L.MOIST[moist or _DEFAULT['moist']], L.CCL_WHICH[which], depth), out)
+    c = _Call(pressure, temperature, dewpoint, u, v)
+    _same_shape(c.ins, 'pressure, temperature, dewpoint, u, v must share a shape')
+    out, res = c.struct(L.SoundingOut, keys + ('status',))
+    c.run('xp_sounding_indices', *c.views((pressure, temperature, dewpoint, u, v)), L.SoundingOpts(L.MOIST[moist or _DEFAULT['moist']], L.CCL_WHICH[which], depth), out)
     return res
 
 
@@ -1341,15 +1306,6 @@ def ccl(pressure, temperature, dewpoint, mixed_layer_depth=None, which='top'):
     return tuple(res[k] for k in L.SOUNDING_CCL_OUT)
 
 
-def _on_grid(pressure, like):
-    """A 1-D pressure of nlev values (isobaric data) on the (nlev, ...) grid of `like`, in pressure's own space."""
-    shape = tuple(like.shape)
-    col = (-1,) + (1,) * (len(shape) - 1)
-    if _is_torch(pressure):
-        return pressure.reshape(col).expand(shape)
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(pressure).reshape(col), shape))
-
-
 def isentropic_interpolation(levels, pressure, temperature, *args, temperature_out=False, max_iters=50, eps=1e-6,
                              bottom_up_search=True, status=False):
     """metpy.calc.isentropic_interpolation of every column (xp_isentropic_interpolation; include/xparcel.h has the rules and
@@ -1366,11 +1322,8 @@ def isentropic_interpolation(levels, pressure, temperature, *args, temperature_o
     assert np.all(np.diff(lev) > 0), 'levels must not hold duplicates'
     assert int(max_iters) >= 1, 'max_iters must be at least 1'
     assert np.isfinite(eps) and eps > 0, 'eps must be finite and positive'
-    if len(np.shape(pressure)) == 1 and len(np.shape(temperature)) > 1:
-        assert np.shape(pressure)[0] == np.shape(temperature)[0], 'a 1-D pressure must have one value per level'
-        pressure = _on_grid(pressure, temperature)
-    c = _Call(pressure, temperature, *args)
-    assert all(a.shape == c.ins[0].shape for a in c.ins), 'pressure, temperature and the further variables must share a shape'
+    c = _Call(_full_pressure(pressure, temperature), temperature, *args)
+    _same_shape(c.ins, 'pressure, temperature and the further variables must share a shape')
     views, n = [c.view(a) for a in c.ins], len(lev)
     shape = (n,) + c.hshape
     p_out, t_out = c.out(shape), c.out(shape) if temperature_out else None
@@ -1427,13 +1380,9 @@ def hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, ba
     assert n <= L.HYDRO_MAX_LAYERS, 'layers: at most four layers'
     keys = ('height', 'thickness', 'status') if want is None else tuple(want)
     assert set(keys) <= {'height', 'thickness', 'status'}, 'want: unknown output'
-    if len(np.shape(pressure)) == 1 and len(np.shape(temperature)) > 1:
-        assert np.shape(pressure)[0] == np.shape(temperature)[0], 'a 1-D pressure must have one value per level'
-        pressure = _on_grid(pressure, temperature)
     moisture = dewpoint if dewpoint is not None else specific_humidity
-    c = _Call(pressure, temperature, *(() if moisture is None else (moisture,)), *([base_height] if _is_torch(base_height) else []))
-    ins = c.ins[:2 if moisture is None else 3]
-    assert all(a.shape == ins[0].shape for a in ins), 'pressure, temperature and the moisture must share a shape'
+    c = _Call(_full_pressure(pressure, temperature), temperature, moisture, base_height if _is_torch(base_height) else None)
+    _same_shape(c.ins[:2 if moisture is None else 3], 'pressure, temperature and the moisture must share a shape')
     res = {}
     out = L.HydrostaticOut(dtype=c.xp_dtype, mem=c.mem)
     if 'height' in keys:
@@ -1448,8 +1397,7 @@ def hydrostatic(pressure, temperature, dewpoint=None, specific_humidity=None, ba
         out.status = _ptr(res['status'])
     base = None if base_height is None else c.per_col(base_height)
     opts = L.HydrostaticOpts(L.HUM_SPECIFIC if specific_humidity is not None else L.HUM_DEWPOINT, 0)
-    views = [c.view(a) for a in ins] + [None]
-    c.run('xp_hydrostatic_height', *views[:3], base, n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]) if n else None,
+    c.run('xp_hydrostatic_height', *c.views((pressure, temperature, moisture)), base, n, (L.WindLayer * n)(*[L.WindLayer(k, 0, b, t) for k, b, t in specs]) if n else None,
           opts, out)
     return res
 
@@ -1491,11 +1439,8 @@ def ncape(pressure, temperature, dewpoint, height, lfc_pressure, el_pressure):
     'status' (XP_ST_NO_LAYER: EL not above the LFC or fewer than two valid levels; ST_BAD_HEIGHT / ST_BAD_PRESSURE: levels out
     of order; everything NaN)."""
     c = _Call(pressure, temperature, dewpoint, height, *[x for x in (lfc_pressure, el_pressure) if _is_torch(x)])
-    assert all(a.shape == c.ins[0].shape for a in c.ins[:4]), 'pressure, temperature, dewpoint, height must share a shape'
-    res = {k: c.out(c.hshape, np.int32 if k == 'status' else None) for k in L.NCAPE_OUT}
-    out = L.NcapeOut(dtype=c.xp_dtype, mem=c.mem)
-    for k, a in res.items():
-        setattr(out, k, _ptr(a))
+    _same_shape(c.ins[:4], 'pressure, temperature, dewpoint, height must share a shape')
+    out, res = c.struct(L.NcapeOut, L.NCAPE_OUT)
     c.run('xp_ncape', *map(c.view, c.ins[:4]), c.per_col(lfc_pressure), c.per_col(el_pressure), out)
     return res
 
@@ -1562,16 +1507,13 @@ def conv_properties(dat, ignore_nans=False, moist=None):
     order = L.CONV_IN_VIEWS + ('surface_wind_u', 'surface_wind_v')
     c = _Call(*[dat[k] for k in order])
     h = dict(zip(order, c.ins))
-    p = h['pressure']
-    assert all(h[k].shape == p.shape for k in ('temperature', 'specific_humidity', 'height_asl')), 'pressure, temperature, specific_humidity, height_asl must share a shape'
+    _same_shape(c.ins[:4], 'pressure, temperature, specific_humidity, height_asl must share a shape')
     wu = h['wind_u']
     assert wu.shape == h['wind_v'].shape == h['wind_height_above_surface'].shape and tuple(wu.shape[1:]) == c.hshape, 'wind arrays must be (nwind, ...) over the same points'
     views = [C.pointer(c.view(h[k])) for k in L.CONV_IN_VIEWS]
     assert int(np.prod(h['surface_wind_u'].shape)) == c.ncol and int(np.prod(h['surface_wind_v'].shape)) == c.ncol
     ci = L.ConvIn(*views, _ptr(h['surface_wind_u']), _ptr(h['surface_wind_v']))
-    co, res = L.ConvOut(), {k: c.out(c.hshape, np.int32 if k == 'positive_shear' else None) for k in L.CONV_OUT}
-    for k, a in res.items():
-        setattr(co, k, _ptr(a))
+    co, res = c.struct(L.ConvOut, L.CONV_OUT)
     c.run('xp_conv_properties', ci, _opts(moist=moist or _DEFAULT['moist']), int(bool(ignore_nans)), co)
     res['positive_shear'] = res['positive_shear'] != 0
     return res

@@ -58,6 +58,10 @@ class _Grid:
             x = x.transpose(dim, *(d for d in x.dims if d != dim))
         return np.asarray(x.values)
 
+    def per_col(self, x):
+        """An argument that may be absent, a scalar or a field: None and 0-d values as they are, anything else as values(x)."""
+        return x if x is None or np.ndim(x) == 0 else self.values(x)
+
     def split(self, ds):
         """Dataset -> name -> values with the vertical first; variables without it are broadcast along it
         (xarray.broadcast)."""

@@ -7,7 +7,7 @@ from the mirror's plumbing, as kinematics.py and thermo_layers.py.
 """
 from . import numpy_api as _api
 from ._xr import Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 _ATTRS = {
     'k_index': {'long_name': 'K index', 'units': 'K'},
@@ -23,10 +23,6 @@ _ATTRS = {
 }
 
 
-def _opt(g, x):
-    return None if x is None else g.values(x)
-
-
 def sounding_indices(pressure, temperature, dewpoint, u=None, v=None, moist=None, which='top', mixed_layer_depth=None,
                      want=None, vert_dim=VERT):
     """Every index and the CCL of every column in one pass, as a Dataset on the horizontal dims: k_index, total_totals,
@@ -34,9 +30,9 @@ def sounding_indices(pressure, temperature, dewpoint, u=None, v=None, moist=None
     convective_temperature [K] -- those that `want` names, by default all the inputs allow -- and the per-column status.
     Arguments as numpy_api.sounding_indices."""
     g = _Grid(pressure, vert_dim)
-    res = _device(_api.sounding_indices, g.values(pressure), g.values(temperature), g.values(dewpoint), _opt(g, u), _opt(g, v),
+    res = _device(_api.sounding_indices, g.values(pressure), g.values(temperature), g.values(dewpoint), g.per_col(u), g.per_col(v),
                   moist=moist, which=which, mixed_layer_depth=mixed_layer_depth, want=want)
-    return Dataset({k: g.horiz(_host(x), k, _ATTRS[k]) for k, x in res.items()})
+    return g.dataset(res, attrs=_ATTRS.get)
 
 
 def _one(key, pressure, temperature, dewpoint, vert_dim, u=None, v=None, **kwargs):

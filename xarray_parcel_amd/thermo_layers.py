@@ -8,8 +8,7 @@ kinematics.py and layer_cape.py.
 import numpy as np
 
 from . import numpy_api as _api
-from ._xr import DataArray, Dataset
-from .parcel_functions import VERT, _Grid, _device, _host
+from .parcel_functions import VERT, _Grid, _device
 
 _ATTRS = {
     'precipitable_water': {'long_name': 'Precipitable water of the layer', 'units': 'mm'},
@@ -28,19 +27,11 @@ _ATTRS = {
 }
 
 
-def _values(g, x):
-    return x if x is None or np.ndim(x) == 0 else g.values(x)
-
-
 def _layer(g, spec):
     """A layer as numpy_api.thermo_layers takes it, per-column bounds (DataArrays on the horizontal dims) as their values."""
     if isinstance(spec, dict):
-        return {k: _values(g, v) for k, v in spec.items()}
-    return tuple(spec[:1]) + tuple(_values(g, v) for v in spec[1:])
-
-
-def _opt(g, x):
-    return None if x is None else g.values(x)
+        return {k: g.per_col(v) for k, v in spec.items()}
+    return tuple(spec[:1]) + tuple(g.per_col(v) for v in spec[1:])
 
 
 def thermo_layers(pressure, temperature=None, dewpoint=None, height=None, layers=(), want=None, vert_dim=VERT):
@@ -52,33 +43,28 @@ def thermo_layers(pressure, temperature=None, dewpoint=None, height=None, layers
     allow -- and the per-column status.  Layers that a column does not span are NaN."""
     g = _Grid(pressure, vert_dim)
     specs = [_layer(g, s) for s in layers]
-    res = _device(_api.thermo_layers, g.values(pressure), _opt(g, temperature), _opt(g, dewpoint), _opt(g, height),
+    res = _device(_api.thermo_layers, g.values(pressure), g.per_col(temperature), g.per_col(dewpoint), g.per_col(height),
                   layers=specs, want=want)
-    coords = dict(g.coords, thermo_layer=np.arange(len(specs)))
-    out = {k: DataArray(_host(v), dims=('thermo_layer',) + g.dims, coords=coords, attrs=dict(_ATTRS[k]), name=k)
-           for k, v in res.items() if k != 'status'}
-    out['status'] = g.horiz(_host(res['status']), 'status', _ATTRS['status'])
-    return Dataset(out)
+    out = g.dataset(res, [k for k in res if k != 'status'], _ATTRS.get, vert=True, vcoord=np.arange(len(specs)),
+                    dim='thermo_layer')
+    out['status'] = g.horiz(res['status'], 'status', _ATTRS['status'])
+    return out
 
 
 def precipitable_water(pressure, dewpoint, bottom=None, top=None, vert_dim=VERT):
     """metpy.calc.precipitable_water [mm] of every column between `bottom` and `top` [hPa; scalars or DataArrays on the
     horizontal dims; None: the lowest / the highest valid level]."""
     g = _Grid(pressure, vert_dim)
-    res = _device(_api.precipitable_water, g.values(pressure), g.values(dewpoint), bottom=_values(g, bottom), top=_values(g, top))
-    return g.horiz(_host(res), 'precipitable_water', _ATTRS['precipitable_water'])
+    res = _device(_api.precipitable_water, g.values(pressure), g.values(dewpoint), bottom=g.per_col(bottom), top=g.per_col(top))
+    return g.horiz(res, 'precipitable_water', _ATTRS['precipitable_water'])
 
 
 def mean_relative_humidity(pressure, temperature, dewpoint, height=None, layer=('pressure', 700.0, 500.0), vert_dim=VERT):
     """The pressure-weighted mean relative humidity [0 ... 1] of one layer (default 700-500 hPa) of every column."""
     g = _Grid(pressure, vert_dim)
-    res = _device(_api.mean_relative_humidity, g.values(pressure), g.values(temperature), g.values(dewpoint), _opt(g, height),
+    res = _device(_api.mean_relative_humidity, g.values(pressure), g.values(temperature), g.values(dewpoint), g.per_col(height),
                   layer=_layer(g, layer))
-    return g.horiz(_host(res), 'mean_relative_humidity', _ATTRS['mean_relative_humidity'])
-
-
-def _pair(g, res, names):
-    return Dataset({name: g.horiz(_host(x), name, _ATTRS[name]) for name, x in zip(names, res)})
+    return g.horiz(res, 'mean_relative_humidity', _ATTRS['mean_relative_humidity'])
 
 
 def layer_lapse_rate(pressure, temperature, height, layer=('pressure', 700.0, 500.0), vert_dim=VERT):
@@ -86,7 +72,7 @@ def layer_lapse_rate(pressure, temperature, height, layer=('pressure', 700.0, 50
     hPa) of every column, as a Dataset of lapse_rate and thickness."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.layer_lapse_rate, g.values(pressure), g.values(temperature), g.values(height), layer=_layer(g, layer))
-    return _pair(g, res, ('lapse_rate', 'thickness'))
+    return g.dataset(dict(zip(('lapse_rate', 'thickness'), res)), attrs=_ATTRS.get)
 
 
 def hail_growth_zone_thickness(pressure, temperature, height, vert_dim=VERT):
@@ -95,7 +81,7 @@ def hail_growth_zone_thickness(pressure, temperature, height, vert_dim=VERT):
     crossing or the two come in the wrong order."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.hail_growth_zone_thickness, g.values(pressure), g.values(temperature), g.values(height))
-    return _pair(g, res, ('hail_growth_zone_thickness', 'hail_growth_zone_lapse_rate'))
+    return g.dataset(dict(zip(('hail_growth_zone_thickness', 'hail_growth_zone_lapse_rate'), res)), attrs=_ATTRS.get)
 
 
 def theta_e_difference(pressure, temperature, dewpoint, height, vert_dim=VERT):
@@ -103,4 +89,4 @@ def theta_e_difference(pressure, temperature, dewpoint, height, vert_dim=VERT):
     the lowest 3 km, 0 where the largest lies above the smallest; NaN where the column does not reach 3 km."""
     g = _Grid(pressure, vert_dim)
     res = _device(_api.theta_e_difference, g.values(pressure), g.values(temperature), g.values(dewpoint), g.values(height))
-    return g.horiz(_host(res), 'theta_e_difference', _ATTRS['theta_e_difference'])
+    return g.horiz(res, 'theta_e_difference', _ATTRS['theta_e_difference'])
