@@ -73,6 +73,32 @@ enum { XP_PARCEL_SURFACE = 0, XP_PARCEL_MOST_UNSTABLE = 1, XP_PARCEL_MIXED_LAYER
    xp_rebase_profile and xp_cape_cin_layers, whose outputs would change shape, reject it with XP_E_ARG;
    xp_opts.compute = XP_F32 rejects it by its own rule (mode must be exactly XP_PARCEL_SURFACE). */
 enum { XP_PARCEL_OVER_GROUND = 16 };
+/* XP_PARCEL_MAX_CAPE, a fifth parcel kind: the departure level with the LARGEST CAPE in the lowest xp_parcel.depth hPa --
+   the "most unstable" of the archives that lift a parcel from every level of the window, where XP_PARCEL_MOST_UNSTABLE is
+   the reference's rule, the level of highest theta-e.  The two usually agree and part on elevated convection.
+   CANDIDATES, those of xp_effective_inflow_layer: a level is valid when p, T and Td are all non-NaN; p0 is the pressure of
+     the lowest valid level; the candidates are the valid levels with p >= p0 - depth (plain comparison), in level order.
+     depth [hPa] not finite or not > 0: XP_E_ARG.
+   CANDIDATE CAPE: CAPE_k = what xp_cape_cin(XP_PARCEL_SURFACE) writes as cape for the views p[k:], T[k:], Td[k:] with the
+     call's four CAPE / CIN options; the moist adiabat by the lookup tables under XP_MOIST_TABLE and by the RK4 stepper
+     otherwise -- XP_MOIST_FAMILY is treated as exact FOR THE SELECTION ONLY.  Every candidate is lifted: no early stop.
+   SELECTION: k* = the lowest candidate whose CAPE_k is the largest.  Walking the candidates upward the first one is taken
+     and then replaced only when CAPE_k > best, so a NaN CAPE_k never wins, and when every CAPE is 0 the lowest valid level
+     wins: the surface parcel.  A column without candidates has k* = 0.
+   The RE-BASED COLUMN has nlev rows: row j = level k* + j for j < nlev - k*, the remaining rows NaN in all three arrays.
+   With this mode the call IS the call with XP_PARCEL_SURFACE on the re-based arrays, with the caller's own options --
+   XP_MOIST_FAMILY and its transparent exact redo included -- bit for bit: every scalar, every status bit, every profile row
+   (nlev_out >= nlev + 1, as for any call).  The one exception: parcel_index = k*, the convention of the most-unstable
+   parcel; parcel_pressure / temperature / dewpoint are level k*'s values, lfc_index / el_index count re-based rows, as
+   they do for XP_PARCEL_MOST_UNSTABLE.
+   Honoured by xp_cape_cin, xp_cape_cin_multi (in any mix with the other kinds, one selection per such parcel; with
+   XP_OPT_FUSE_PARCELS the call takes the per-parcel path, as for explicit parcels) and xp_select_parcel (no options: the
+   selection runs with the default options and RK4; it writes parcel_index and the three parcel values).  XP_HUM_SPECIFIC
+   with this kind: XP_E_ARG; xp_opts.compute = XP_F32 rejects it by its own rule; it does not combine with
+   XP_PARCEL_OVER_GROUND (4 | 16 is a bad mode); every other entry point that takes an xp_parcel rejects it.
+   COST: one ascent per candidate and column (csrc/xp_max_cape.hpp; ~the open-threshold xp_effective_inflow_layer call)
+   plus three (nlev, ncol) scratch arrays for the duration of the call, per such parcel. */
+enum { XP_PARCEL_MAX_CAPE = 4 };
 
 /* moist adiabat: XP_MOIST_EXACT integrates MetPy's pseudo-adiabat ODE (what the reference's
    KATs are run with, unit_tests.py:114-140) by RK4 in ln p with steps <= 0.1;
@@ -145,7 +171,7 @@ typedef struct {
 } xp_view;
 
 typedef struct {
-    int32_t mode;       /* XP_PARCEL_*, optionally | XP_PARCEL_OVER_GROUND */
+    int32_t mode;       /* XP_PARCEL_* (XP_PARCEL_MAX_CAPE included), the first three optionally | XP_PARCEL_OVER_GROUND */
     int32_t reserved;
     double depth;       /* hPa: MU search depth (default 300, pf.py:1558) / ML mixing depth (100, pf.py:1652) */
     /* XP_PARCEL_EXPLICIT: the per-column parcel; XP_PARCEL_OVER_GROUND: the surface.  ncol elements each, same dtype/mem as

@@ -12,7 +12,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), 'include', 'xparcel.h')
 
 XP_F32, XP_F64 = 0, 1
 XP_MEM_HOST, XP_MEM_DEVICE = 0, 1
-PARCEL = {'surface': 0, 'most_unstable': 1, 'mixed_layer': 2, 'explicit': 3}
+PARCEL = {'surface': 0, 'most_unstable': 1, 'mixed_layer': 2, 'explicit': 3, 'max_cape': 4}
 PARCEL_OVER_GROUND = 16       # XP_PARCEL_OVER_GROUND: a flag on xp_parcel.mode (isobaric levels cut at the ground)
 MOIST = {'exact': 0, 'table': 1, 'family': 2}
 LCL_INTERP = {'linear': 0, 'log': 1}
@@ -359,6 +359,9 @@ for _m in list(MULTI_FLAGS):
 # The effective-inflow-layer kernel (csrc/xp_effective.hpp): its LCL iteration sits inside the candidate loop, and with
 # machine LICM the fp64 constants of both loops are kept in registers through every ascent (160+ VGPRs instead of 106-112).
 EFFECTIVE_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The maximum-CAPE parcel's kernels (csrc/xp_max_cape.hpp) are that sweep with another bookkeeping, in a unit of their own
+# with the same flag.  VGPRs, waves per SIMD: k_max_cape_select f64 RK4 108, 4 / f64 tables 112, 4 / f32 RK4 105, 4 /
+# f32 tables 110, 4 (38448 B of LDS: four workgroups per CU); k_rebase_from f64 43, 8 / f32 40, 8 (no LDS); no scratch.
 # The wind-layers kernel (csrc/xp_wind_layers.hpp): each layer can add two bound points, each with three logarithms, and
 # with machine LICM their fp64 constants are carried through the level loop (14 VGPRs more in every instantiation: three
 # layers without the strongest wind 131 instead of 119, two with it 143 instead of 128 -- a wave per SIMD each).
@@ -384,7 +387,7 @@ HYDROSTATIC_FLAGS = ['-mllvm', '-disable-machine-licm']
 # and flag (e_s / ln tables + the fp32 copy of the family table + the scan slots: 130.3 KB of LDS, one workgroup per CU).
 CAPE_F32_FLAGS = ['-DXP_CAPE_THREADS=1024', '-mllvm', '-disable-machine-licm']
 UNITS = [('xparcel', 'xparcel.hip', []), ('cape_f32', 'xp_cape_f32_tu.hip', CAPE_F32_FLAGS),
-         ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS),
+         ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS), ('max_cape', 'xp_max_cape_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
          ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),

@@ -20,6 +20,7 @@
 #include "xp_dcape.hpp"
 #include "xp_kinematics.hpp"
 #include "xp_effective.hpp"
+#include "xp_max_cape.hpp"
 #include "xp_cape_layers.hpp"
 #include "xp_wind_layers.hpp"
 #include "xp_thermo_layers.hpp"
@@ -451,8 +452,9 @@ bool over_ground(const xp_parcel &parcel) {
     return parcel.mode >= XP_PARCEL_OVER_GROUND && parcel.mode < (XP_PARCEL_OVER_GROUND | XP_PARCEL_EXPLICIT);
 }
 int parcel_mode(const xp_parcel &parcel) { return over_ground(parcel) ? parcel.mode & 3 : parcel.mode; }
-// ground_ok: the caller implements XP_PARCEL_OVER_GROUND (xp_cape_cin, xp_cape_cin_multi, xp_select_parcel)
-int check_parcel(const xp_parcel *parcel, bool ground_ok = false) {
+// ground_ok: the caller implements XP_PARCEL_OVER_GROUND (xp_cape_cin, xp_cape_cin_multi, xp_select_parcel);
+// max_cape_ok: it implements XP_PARCEL_MAX_CAPE (the same three)
+int check_parcel(const xp_parcel *parcel, bool ground_ok = false, bool max_cape_ok = false) {
     if (!parcel) return fail(XP_E_ARG, "parcel: null");
     if (parcel->mode == (XP_PARCEL_OVER_GROUND | XP_PARCEL_EXPLICIT))
         return fail(XP_E_ARG, "parcel: XP_PARCEL_OVER_GROUND does not combine with XP_PARCEL_EXPLICIT");
@@ -462,6 +464,10 @@ int check_parcel(const xp_parcel *parcel, bool ground_ok = false) {
             return fail(XP_E_ARG, "parcel: XP_PARCEL_OVER_GROUND needs the surface pressure, temperature and dewpoint arrays");
         return 0;
     }
+    if (max_cape_ok && parcel->mode == XP_PARCEL_MAX_CAPE) {
+        if (!(std::isfinite(parcel->depth) && parcel->depth > 0.0)) return fail(XP_E_ARG, "parcel: XP_PARCEL_MAX_CAPE: depth must be finite and positive");
+        return 0;
+    }
     if (parcel->mode < XP_PARCEL_SURFACE || parcel->mode > XP_PARCEL_EXPLICIT) return fail(XP_E_ARG, "parcel: bad mode");
     if (parcel->mode == XP_PARCEL_EXPLICIT && (!parcel->pressure || !parcel->temperature || !parcel->dewpoint))
         return fail(XP_E_ARG, "explicit parcel: null arrays");
@@ -469,10 +475,13 @@ int check_parcel(const xp_parcel *parcel, bool ground_ok = false) {
 }
 // the arguments of the CAPE family: p / T / Td, each of np parcels, the options
 int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o, bool f32_ok = false,
-               bool ground_ok = false) {
+               bool ground_ok = false, bool max_cape_ok = false) {
     if (int rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) return rc;
-    for (int i = 0; i < np; ++i)
-        if (int rc = check_parcel(parcels + i, ground_ok)) return rc;
+    for (int i = 0; i < np; ++i) {
+        if (int rc = check_parcel(parcels + i, ground_ok, max_cape_ok)) return rc;
+        if (parcels[i].mode == XP_PARCEL_MAX_CAPE && o.humidity == XP_HUM_SPECIFIC)
+            return fail(XP_E_ARG, "parcel: XP_PARCEL_MAX_CAPE: humidity must be XP_HUM_DEWPOINT");
+    }
     // the parcels of one call share its grid: over the ground all of them, over the same surface fields, or none
     for (int i = 1; i < np; ++i) {
         const xp_parcel &a = parcels[0], &b = parcels[i];
@@ -540,9 +549,9 @@ int set_parcel(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeAr
     return 0;
 }
 int fill_common(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
-                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false, bool ground_ok = false) {
+                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false, bool ground_ok = false, bool max_cape_ok = false) {
     int rc;
-    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok, ground_ok)) ||
+    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok, ground_ok, max_cape_ok)) ||
         (rc = stage_cape(st, p, t, td, o, a, over_ground(*parcel) ? parcel : nullptr)) || (rc = set_parcel(st, *parcel, p, a)))
         return rc;
     return 0;
@@ -588,6 +597,41 @@ void cape_pass(const Stager &st, xp::CapeArgs a, int dtype, int mode, bool profi
     a.flags = flags;
     a.persist = flags && persist(mode, a.ncol);
     by_dtype(dtype, [&](auto z) { launch_cape_pm<decltype(z)>(a, mode, profile, st.s); });
+}
+
+// XP_PARCEL_MAX_CAPE (csrc/xp_max_cape.hpp), the selection on a call's staged views: k* per column into scratch of the call
+// (kstar), or, for xp_select_parcel, the parcel it names into `sel`.  Lifted with the call's four options, by the tables in
+// table mode and by RK4 otherwise.
+int max_cape_select(Stager &st, const xp_parcel &parcel, const xp::CapeArgs &a, const xp_view *p, const xp::ScalarsOut *sel, int32_t **kstar) {
+    xp::MaxCapeArgs m;
+    memset(&m, 0, sizeof(m));
+    m.e.p = a.p; m.e.t = a.t; m.e.td = a.td;
+    m.e.nlev = a.nlev; m.e.ncol = a.ncol; m.e.depth = parcel.depth;
+    m.e.vtc = a.vtc; m.e.log_interp = a.log_interp; m.e.pos_neg = a.pos_neg; m.e.post_zero = a.post_zero;
+    m.e.tb = a.tb; m.e.es_tab = a.es_tab;
+    if (sel) m.s = *sel;
+    else if (int rc = st.alloc(sizeof(int32_t) * (size_t)a.ncol, &m.kstar)) return rc;
+    if (kstar) *kstar = m.kstar;
+    xp::launch_max_cape_select(m, p->dtype == XP_F64, a.table_mode != 0, st.s);
+    return 0;
+}
+// ... and the front of a CAPE / CIN call with that parcel: the selection, then the columns from k* on as three dense scratch
+// arrays in place of the views.  What follows is the call with XP_PARCEL_SURFACE on those; copy_kstar ends it.
+int max_cape_front(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeArgs *a, int32_t **kstar) {
+    int rc;
+    xp::RebaseFromArgs r;
+    if ((rc = max_cape_select(st, parcel, *a, p, nullptr, kstar)) || (rc = st.alloc(rows_bytes(p, p->nlev), &r.op)) ||
+        (rc = st.alloc(rows_bytes(p, p->nlev), &r.ot)) || (rc = st.alloc(rows_bytes(p, p->nlev), &r.otd))) return rc;
+    r.p = a->p; r.t = a->t; r.td = a->td; r.kstar = *kstar; r.nlev = a->nlev; r.ncol = a->ncol;
+    xp::launch_rebase_from(r, p->dtype == XP_F64, st.s);
+    a->p = {r.op, a->ncol, 1}; a->t = {r.ot, a->ncol, 1}; a->td = {r.otd, a->ncol, 1};
+    return 0;
+}
+// parcel_index = k*, the most-unstable parcel's convention, over the 0 the surface pass stored (same stream: after it)
+int copy_kstar(const Stager &st, const int32_t *kstar, const xp::CapeArgs &a) {
+    if (kstar && a.s.parcel_idx && a.ncol > 0)
+        HIP_TRY(hipMemcpyAsync(a.s.parcel_idx, kstar, sizeof(int32_t) * (size_t)a.ncol, hipMemcpyDeviceToDevice, st.s));
+    return 0;
 }
 
 // xp_opts.compute == XP_F32 is honoured in exactly one case (include/xparcel.h); every other one names what it is held to
@@ -688,7 +732,7 @@ bool multi_fused_ok(int32_t np, const xp_parcel *parcels, const xp_opts &o, cons
     if (!(o.flags & XP_OPT_FUSE_PARCELS) || o.moist_mode != XP_MOIST_FAMILY || o.humidity != XP_HUM_DEWPOINT) return false;
     if (np != 2 || profiles) return false;                                   // instantiated parcel counts (xp_multi_tu.hip)
     for (int i = 0; i < np; ++i)
-        if (parcel_mode(parcels[i]) == XP_PARCEL_EXPLICIT) return false;
+        if (parcel_mode(parcels[i]) == XP_PARCEL_EXPLICIT || parcel_mode(parcels[i]) == XP_PARCEL_MAX_CAPE) return false;
     return true;
 }
 
@@ -791,11 +835,16 @@ int xp_cape_cin(const xp_view *p, const xp_view *t, const xp_view *td, const xp_
     int32_t *flags;
     int rc;
     const bool f32 = oo.compute == XP_F32;                   // (held to its contract before anything is staged or looked up)
-    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
-    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true, true)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
+    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true, true, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
+    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true, true, true)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
         (rc = family_flags(st, oo, a.ncol, &flags))) return rc;
     if (f32) cape_pass32(st, a, flags);
-    else cape_pass(st, a, p->dtype, parcel_mode(*parcel), profile != nullptr, flags);
+    else if (parcel->mode == XP_PARCEL_MAX_CAPE) {           // the surface call on the columns from k* on
+        int32_t *kstar;
+        if ((rc = max_cape_front(st, *parcel, p, &a, &kstar))) return rc;
+        cape_pass(st, a, p->dtype, XP_PARCEL_SURFACE, profile != nullptr, flags);
+        if ((rc = copy_kstar(st, kstar, a))) return rc;
+    } else cape_pass(st, a, p->dtype, parcel_mode(*parcel), profile != nullptr, flags);
     return st.finish();
 }
 
@@ -809,7 +858,7 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     xp::CapeArgs a, pa[xp::MULTI_MAX];
     int rc;
     // every parcel is checked, and its outputs staged, before anything runs; p / T / Td are staged once
-    if ((rc = check_cape(p, t, td, np, parcels, oo, false, true)) ||
+    if ((rc = check_cape(p, t, td, np, parcels, oo, false, true, true)) ||
         (rc = stage_cape(st, p, t, td, oo, &a, over_ground(parcels[0]) ? parcels : nullptr))) return rc;   // re-based once per call
     for (int i = 0; i < np; ++i) {
         pa[i] = a;
@@ -820,7 +869,13 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     if (!multi_fused_ok(np, parcels, oo, profiles)) {        // one pass per parcel
         int32_t *flags;
         if ((rc = family_flags(st, oo, ncol, &flags))) return rc;
-        for (int i = 0; i < np; ++i) cape_pass(st, pa[i], p->dtype, parcel_mode(parcels[i]), profiles != nullptr, flags);
+        for (int i = 0; i < np; ++i) {
+            const bool mc = parcels[i].mode == XP_PARCEL_MAX_CAPE;           // its own selection and re-based views of the shared grid
+            int32_t *kstar = nullptr;
+            if (mc && (rc = max_cape_front(st, parcels[i], p, &pa[i], &kstar))) return rc;
+            cape_pass(st, pa[i], p->dtype, mc ? XP_PARCEL_SURFACE : parcel_mode(parcels[i]), profiles != nullptr, flags);
+            if ((rc = copy_kstar(st, kstar, pa[i]))) return rc;
+        }
         return st.finish();
     }
     xp::MultiArgs m;
@@ -968,7 +1023,11 @@ int xp_select_parcel(const xp_view *p, const xp_view *t, const xp_view *td, cons
     if (st.rc) return st.rc;
     xp::CapeArgs a;
     int rc;
-    if ((rc = fill_common(st, p, t, td, parcel, default_opts(), &a, false, true))) return rc;
+    if ((rc = fill_common(st, p, t, td, parcel, default_opts(), &a, false, true, true))) return rc;
+    if (parcel->mode == XP_PARCEL_MAX_CAPE) {                // the selection alone, with the default options and RK4
+        if ((rc = stage_scalars(st, out, a.ncol, &a.s)) || (rc = max_cape_select(st, *parcel, a, p, &a.s, nullptr))) return rc;
+        return st.finish();
+    }
     if (parcel_mode(*parcel) != XP_PARCEL_MOST_UNSTABLE && parcel_mode(*parcel) != XP_PARCEL_MIXED_LAYER)
         return fail(XP_E_ARG, "xp_select_parcel: mode must be most-unstable or mixed-layer");
     if ((rc = stage_scalars(st, out, a.ncol, &a.s))) return rc;

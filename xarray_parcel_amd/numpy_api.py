@@ -258,14 +258,15 @@ def _sounding(pressure, temperature, dewpoint, ground=None):
 def _parcel(c, name, depth=None, parcel_values=None, surface=None):
     """The xp_parcel `name` of a call: `depth` [hPa] defaults to the reference's; an explicit parcel points at its
     (pressure, temperature, dewpoint) `parcel_values`, one per column, staged on `c`; with the `surface` arrays of a ground=
-    call (_sounding) it carries XP_PARCEL_OVER_GROUND and points at those."""
+    call (_sounding) it carries XP_PARCEL_OVER_GROUND and points at those ('max_cape' does not combine with it)."""
     if depth is None:
-        depth = 300.0 if name == 'most_unstable' else 100.0                # pf.py:1558, 1652
+        depth = 300.0 if name in ('most_unstable', 'max_cape') else 100.0  # pf.py:1558, 1652
     pc = L.Parcel(L.PARCEL[name], 0, float(depth), None, None, None)
     if name == 'explicit':
         pc.pressure, pc.temperature, pc.dewpoint = (_ptr(c.per_col(x)) for x in parcel_values)
     if surface is not None:
         assert name != 'explicit', 'ground: not with an explicit parcel'
+        assert name != 'max_cape', 'ground: not with the max_cape parcel'
         pc.mode |= L.PARCEL_OVER_GROUND
         pc.pressure, pc.temperature, pc.dewpoint = (_ptr(x) for x in surface)
     return pc
@@ -287,7 +288,10 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     include/xparcel.h).  The arrays hold isobaric levels, `pressure` possibly just the nlev isobars, and each column is cut
     at its surface pressure: the surface values become level 0, the levels above the ground follow, NaN fills the rest.
     Every result is that of the call on those re-based columns: the indices count their rows, and the profile has
-    nlev + 2 rows.  Not with an explicit parcel, nor with compute='float32'."""
+    nlev + 2 rows.  Not with an explicit parcel, nor with compute='float32'.
+    parcel='max_cape' (XP_PARCEL_MAX_CAPE, include/xparcel.h): the departure level of the lowest `depth` hPa (default 300)
+    whose parcel has the largest CAPE -- every level of the window is lifted.  The results are those of the surface call on
+    the column from that level on, 'parcel_index' the level.  Not with ground=, humidity='specific' or compute='float32'."""
     c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     moist = moist or _DEFAULT['moist']
     if compute is None:
@@ -316,7 +320,7 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
 def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=None, lifted_index_at=None, fused=False,
                    ground=None, **kwargs):
     """Several parcels of one grid in ONE call (xp_cape_cin_multi): `parcels` is a sequence of names or (name, depth)
-    pairs out of 'surface', 'most_unstable', 'mixed_layer' -- e.g. [('most_unstable', 300), ('mixed_layer', 100)] for
+    pairs out of 'surface', 'most_unstable', 'mixed_layer', 'max_cape' -- e.g. [('most_unstable', 300), ('mixed_layer', 100)] for
     BASELINE config 5, [('most_unstable', 250), ('mixed_layer', 100), ('mixed_layer', 50)] for conv_properties
     (pf.py:1984-2006).  Returns one dict per parcel, bit-identical to what cape_cin_columns() returns for it.
     fused=True (XP_OPT_FUSE_PARCELS; moist='family', two parcels): one pass over the grid for both -- same numbers,
@@ -328,7 +332,7 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
     pcs = []
     for pc in parcels:
         name, depth = (pc, None) if isinstance(pc, str) else (pc[0], pc[1])
-        assert name in ('surface', 'most_unstable', 'mixed_layer'), 'parcels: surface, most_unstable or mixed_layer'
+        assert name in ('surface', 'most_unstable', 'mixed_layer', 'max_cape'), 'parcels: surface, most_unstable or mixed_layer, or max_cape'
         pcs.append(_parcel(c, name, depth, surface=surface))
     n = len(pcs)
     pcs = (L.Parcel * n)(*pcs)
@@ -378,6 +382,14 @@ def most_unstable_cape_cin(pressure, temperature, dewpoint, depth=300, **kwargs)
                       'dewpoint': res['parcel_dewpoint'], 'index': res['parcel_index']}
 
 
+def max_cape_cape_cin(pressure, temperature, dewpoint, depth=300, **kwargs):
+    """As most_unstable_cape_cin for the parcel with the largest CAPE of the lowest `depth` hPa (parcel='max_cape')."""
+    res = cape_cin_columns(pressure, temperature, dewpoint, parcel='max_cape', depth=depth, want_profile=True, **kwargs)
+    cc, prof = _split(res)
+    return cc, prof, {'pressure': res['parcel_pressure'], 'temperature': res['parcel_temperature'],
+                      'dewpoint': res['parcel_dewpoint'], 'index': res['parcel_index']}
+
+
 def mixed_layer_cape_cin(pressure, temperature, dewpoint, depth=100, **kwargs):
     """pf.py:1651."""
     res = cape_cin_columns(pressure, temperature, dewpoint, parcel='mixed_layer', depth=depth, want_profile=True,
@@ -411,6 +423,12 @@ def _select(pressure, temperature, dewpoint, mode, depth, ground=None):
 def most_unstable_parcel(pressure, temperature, dewpoint, depth=300, ground=None):
     """pf.py:102.  ground: as in cape_cin_columns ('index' counts the rows of the column cut at the ground)."""
     return _select(pressure, temperature, dewpoint, 'most_unstable', depth, ground)
+
+
+def max_cape_parcel(pressure, temperature, dewpoint, depth=300):
+    """The departure level of the lowest `depth` hPa whose parcel has the largest CAPE (XP_PARCEL_MAX_CAPE, include/xparcel.h;
+    default options, exact moist adiabat): what most_unstable_parcel returns."""
+    return _select(pressure, temperature, dewpoint, 'max_cape', depth)
 
 
 def mixed_parcel(pressure, temperature, dewpoint, depth=100, ground=None):
