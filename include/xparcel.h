@@ -107,8 +107,28 @@ enum { XP_PARCEL_MAX_CAPE = 4 };
 enum { XP_MOIST_EXACT = 0, XP_MOIST_TABLE = 1, XP_MOIST_FAMILY = 2 };
 /* XP_HUM_SPECIFIC: the moisture view holds specific humidity [kg/kg] (what the reference's data files provide) and is
    converted to dewpoint on load with the xp_dewpoint_from_specific_humidity chain (parcel_test.py:262-266), saving the
-   separate pass and the (nlev, ncol) dewpoint array.  Explicit parcels (xp_parcel.dewpoint) stay dewpoints. */
-enum { XP_HUM_DEWPOINT = 0, XP_HUM_SPECIFIC = 1 };
+   separate pass and the (nlev, ncol) dewpoint array.  Explicit parcels (xp_parcel.dewpoint) stay dewpoints.
+   XP_HUM_RELATIVE and XP_HUM_MIXING_RATIO: the moisture m as the archives without a dewpoint deliver it.
+     XP_HUM_RELATIVE: the view holds relative humidity over liquid water as a FRACTION (1 = saturated; not percent):
+       e = m * e_s(T), e_s Bolton's formula as everywhere in the library.
+     XP_HUM_MIXING_RATIO: the view holds the water-vapour mixing ratio [kg/kg]: e = p * m / (eps + m).
+     Both: D = 273.15 + 243.5 v / (17.67 - v) with v = ln(e / 6.112) -- MetPy's dewpoint -- evaluated in double.
+     VALIDITY: D is NaN unless m > 0 by plain comparison, so a NaN, zero or negative moisture gives NaN.  There is no upper
+       bound: rh > 1 gives D > T, exactly as a dewpoint view may hold it.  The IEEE arithmetic of the formula decides
+       everything else (infinities, a NaN T or p); the relative kind needs T and not p, the mixing-ratio kind p and not T.
+     D is stored in the views' dtype, rounded once, and with either kind the call IS the XP_HUM_DEWPOINT call on D, bit for
+     bit: every scalar, every status bit, every profile row, environment_dewpoint included.  Explicit parcels stay
+     dewpoints, and so does the surface dewpoint of XP_PARCEL_OVER_GROUND: the levels are converted first and the ground
+     cut runs on the result.
+     Honoured by xp_cape_cin, xp_cape_cin_multi (converted once per call; XP_OPT_FUSE_PARCELS works on D like on any
+     dewpoint grid), xp_cape_cin_layers and xp_effective_inflow_layer.  XP_PARCEL_MAX_CAPE accepts both (its selection
+     sees a dewpoint grid); xp_opts.compute = XP_F32 rejects them by its own rule; xp_conv_properties (specific humidity
+     by construction) and xp_hydrostatic_height (its own two kinds) do not take them.
+     COST: one streaming pass over the moisture and T or p in front of the call (csrc/xp_humidity.hpp; the views are read
+     in place whatever their strides, the caller's moisture view is never written) plus one dense (nlev, ncol) scratch
+     array for the duration of the call.  Measured on 64 x 1 Mi columns, surface parcel, XP_MOIST_FAMILY:
+     the call costs 1.6 x the dewpoint call in fp64 and 1.5 x in fp32. */
+enum { XP_HUM_DEWPOINT = 0, XP_HUM_SPECIFIC = 1, XP_HUM_RELATIVE = 2, XP_HUM_MIXING_RATIO = 3 };
 /* XP_MOIST_FAMILY: the same pseudo-adiabat ODE, served from a piecewise-polynomial table of its solutions: the parcel's
    VIRTUAL temperature along the adiabat, Tv(ln p ; psi) = T (1 + 0.608 w_s(p, T)) (what pf.py:760-775 feed the CAPE / CIN
    integration), psi = the adiabat's temperature at 1000 hPa (8 pieces of 0.5 in ln p from 1100 hPa to ~20 hPa x 9 pieces
@@ -399,9 +419,9 @@ int xp_downdraft_cape(const xp_view *pressure, const xp_view *temperature, const
    status: XP_ST_NO_LAYER when no candidate passes (floats NaN, indices -1); XP_ST_LAYER_OPEN when the last candidate of the
    window passes; XP_ST_LCL_NOT_CONVERGED ORed over the candidates lifted; XP_ST_BAD_PRESSURE as in xp_cape_cin (ORed likewise).
    opts: the four CAPE / CIN options and moist_mode (XP_MOIST_EXACT, XP_MOIST_TABLE; XP_MOIST_FAMILY is treated as exact);
-   humidity must be XP_HUM_DEWPOINT.  Non-finite thresholds, search_depth <= 0 or not finite, mismatched views and
-   XP_HUM_SPECIFIC return XP_E_ARG.  Every output may be NULL; the outputs share the views' dtype and mem.  Strided device
-   views are read in place. */
+   humidity XP_HUM_DEWPOINT, XP_HUM_RELATIVE or XP_HUM_MIXING_RATIO.  Non-finite thresholds, search_depth <= 0 or not finite,
+   mismatched views and XP_HUM_SPECIFIC return XP_E_ARG.  Every output may be NULL; the outputs share the views' dtype and
+   mem.  Strided device views are read in place. */
 typedef struct {
     void *base_pressure, *top_pressure;   /* hPa, ncol: the pressures of the levels base_index / top_index */
     void *base_height, *top_height;       /* m above the lowest valid level, ncol */
@@ -439,8 +459,8 @@ int xp_effective_inflow_layer(const xp_view *pressure, const xp_view *temperatur
    promised there).
    total_cape, total_cin, lfc_pressure, el_pressure, lcl_pressure and the other status bits are what xp_cape_cin writes
    for the same arguments.  opts: pos_cape_neg_cin must be set (cin[i] <= 0 by construction, so post_zero_cin changes
-   nothing); moist_mode XP_MOIST_EXACT or XP_MOIST_TABLE (XP_MOIST_FAMILY is treated as exact); humidity must be
-   XP_HUM_DEWPOINT.  nlayer outside 1 ... 4, a NULL top or top[i], mismatched views, XP_HUM_SPECIFIC,
+   nothing); moist_mode XP_MOIST_EXACT or XP_MOIST_TABLE (XP_MOIST_FAMILY is treated as exact); humidity XP_HUM_DEWPOINT,
+   XP_HUM_RELATIVE or XP_HUM_MIXING_RATIO.  nlayer outside 1 ... 4, a NULL top or top[i], mismatched views, XP_HUM_SPECIFIC,
    pos_cape_neg_cin == 0 and an unknown moist_mode return XP_E_ARG; a bad lcl_interp XP_E_INTERP.  Every output may be
    NULL; the outputs share the views' dtype and mem. */
 typedef struct {

@@ -16,7 +16,7 @@ PARCEL = {'surface': 0, 'most_unstable': 1, 'mixed_layer': 2, 'explicit': 3, 'ma
 PARCEL_OVER_GROUND = 16       # XP_PARCEL_OVER_GROUND: a flag on xp_parcel.mode (isobaric levels cut at the ground)
 MOIST = {'exact': 0, 'table': 1, 'family': 2}
 LCL_INTERP = {'linear': 0, 'log': 1}
-HUMIDITY = {'dewpoint': 0, 'specific': 1}
+HUMIDITY = {'dewpoint': 0, 'specific': 1, 'relative': 2, 'mixing_ratio': 3}     # xp_opts.humidity: what the moisture view holds
 COMPUTE = {'float32': XP_F32, 'float64': XP_F64}      # xp_opts.compute: the arithmetic type
 OPT_FUSE_PARCELS = 1
 ST_TOP_NAN, ST_LCL_NOT_CONVERGED, ST_NAN_PRESSURE, ST_BAD_PRESSURE = 1, 2, 4, 8
@@ -383,6 +383,12 @@ CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 #   f64 specific  45, 8 / 68, 7 / 87, 5 / 95, 5 / 104, 4      f32 specific  44, 8 / 66, 7 / 85, 5 / 93, 5 / 102, 4
 # (without it 50-61 / 72-88 / 91-104 / 99-112 / 108-122); no LDS, no scratch.
 HYDROSTATIC_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The humidity conversion in front of the CAPE / CIN calls (csrc/xp_humidity.hpp, XP_HUM_RELATIVE / XP_HUM_MIXING_RATIO) takes no
+# flag either: a streaming kernel without a level loop to keep constants out of.  No LDS, no scratch; as cross-compiled,
+# k_dewpoint_from<T, KIND, VEC> by (T: 'd' / 'f', KIND: XP_HUM_*, VEC: 16-byte runs or one column per lane) -> (VGPRs, waves
+# per SIMD), which tests/test_humidity_cpu.py holds the unit to:
+HUMIDITY_RESOURCES = {('d', 2, 1): (52, 8), ('d', 2, 0): (41, 8), ('d', 3, 1): (44, 8), ('d', 3, 0): (38, 8),
+                      ('f', 2, 1): (52, 8), ('f', 2, 0): (43, 8), ('f', 3, 1): (46, 8), ('f', 3, 0): (40, 8)}
 # The fp32-arithmetic surface CAPE / CIN kernel (csrc/xp_cape_f32.hpp, xp_opts.compute = XP_F32): the family units' workgroup
 # and flag (e_s / ln tables + the fp32 copy of the family table + the scan slots: 130.3 KB of LDS, one workgroup per CU).
 CAPE_F32_FLAGS = ['-DXP_CAPE_THREADS=1024', '-mllvm', '-disable-machine-licm']
@@ -392,7 +398,7 @@ UNITS = [('xparcel', 'xparcel.hip', []), ('cape_f32', 'xp_cape_f32_tu.hip', CAPE
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
          ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),
          ('sounding', 'xp_sounding_tu.hip', []), ('isentropic', 'xp_isentropic_tu.hip', []),
-         ('hydrostatic', 'xp_hydrostatic_tu.hip', HYDROSTATIC_FLAGS)] + [
+         ('hydrostatic', 'xp_hydrostatic_tu.hip', HYDROSTATIC_FLAGS), ('humidity', 'xp_humidity_tu.hip', [])] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])
     for t in ('double', 'float') for m in (0, 1, 2)] + [
     (f'multi_{t[0]}{n}', 'xp_multi_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_MULTI_NP={n}'] + MULTI_FLAGS[n])

@@ -27,6 +27,7 @@
 #include "xp_sounding.hpp"
 #include "xp_isentropic.hpp"
 #include "xp_hydrostatic.hpp"
+#include "xp_humidity.hpp"
 #include "xp_ecape.hpp"
 #include "xp_per_point.hpp"
 
@@ -39,6 +40,7 @@ static_assert(xp::ISEN_MAX_LEVELS == XP_ISEN_MAX_LEVELS && xp::ISEN_MAX_VARS == 
               "the isentropic kernel's limits are the ABI's");
 static_assert(xp::HY_MAX_LAYERS == sizeof(xp_hydrostatic_out::thickness) / sizeof(void *) && xp::HY_DEWPOINT == XP_HUM_DEWPOINT + 1 &&
               xp::HY_SPECIFIC == XP_HUM_SPECIFIC + 1, "the hydrostatic kernel's limits and moisture kinds follow the ABI's");
+static_assert(xp::HUM_RELATIVE == XP_HUM_RELATIVE && xp::HUM_MIXING_RATIO == XP_HUM_MIXING_RATIO, "the conversion kernel's moisture kinds are the ABI's");
 static_assert(xp::CCL_TOP == XP_CCL_TOP && xp::CCL_BOTTOM == XP_CCL_BOTTOM, "the kernel's CCL choices are the ABI's");
 static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
               xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
@@ -444,7 +446,7 @@ int check_opts(const xp_opts &o, bool f32_ok = false) {
         return fail(XP_E_ARG, "bad moist_mode");
     if (o.compute != XP_F64 && !(f32_ok && o.compute == XP_F32))
         return fail(XP_E_ARG, o.compute == XP_F32 ? "xp_opts.compute: XP_F32 arithmetic is implemented by xp_cape_cin only" : "xp_opts.compute: XP_F32 or XP_F64");
-    if (o.humidity != XP_HUM_DEWPOINT && o.humidity != XP_HUM_SPECIFIC) return fail(XP_E_ARG, "bad xp_opts.humidity");
+    if (o.humidity < XP_HUM_DEWPOINT || o.humidity > XP_HUM_MIXING_RATIO) return fail(XP_E_ARG, "bad xp_opts.humidity");
     return 0;
 }
 // XP_PARCEL_OVER_GROUND: the flag on a surface / most-unstable / mixed-layer mode, and the parcel mode under it
@@ -491,6 +493,18 @@ int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, co
     return check_opts(o, f32_ok);
 }
 
+// XP_HUM_RELATIVE / XP_HUM_MIXING_RATIO (csrc/xp_humidity.hpp): the staged moisture view *m becomes the dewpoint D of the
+// header, a dense (nlev, ncol) array in the call's scratch, written on the call's stream; the other kinds leave *m alone.
+// What follows is the dewpoint-input call on D.
+int dewpoint_front(Stager &st, const xp_view *p, const xp_opts &o, const xp::View &pv, const xp::View &tv, xp::View *m) {
+    if (o.humidity != XP_HUM_RELATIVE && o.humidity != XP_HUM_MIXING_RATIO) return 0;
+    xp::HumidityArgs h = {pv, tv, *m, p->nlev, p->ncol, nullptr};
+    if (int rc = st.alloc(rows_bytes(p, p->nlev), &h.out)) return rc;
+    xp::launch_dewpoint_from(h, p->dtype == XP_F64, o.humidity, st.s);
+    *m = {h.out, p->ncol, 1};
+    return 0;
+}
+
 // the CAPE family's p / T / Td, options and tables, staged once per call however many parcels it lifts; `ground`: a parcel
 // with XP_PARCEL_OVER_GROUND, whose surface arrays re-base the grid (csrc/xp_ground.hpp) before anything else sees it
 int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_opts &o, xp::CapeArgs *a,
@@ -499,7 +513,8 @@ int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td
     TableSet ts;
     memset(a, 0, sizeof(*a));
     if ((rc = snapshot_tables(o.moist_mode == XP_MOIST_TABLE, &ts)) || (rc = stage_view(st, p, &a->p)) ||
-        (rc = stage_view(st, t, &a->t)) || (rc = stage_view(st, td, &a->td))) return rc;
+        (rc = stage_view(st, t, &a->t)) || (rc = stage_view(st, td, &a->td)) ||
+        (rc = dewpoint_front(st, p, o, a->p, a->t, &a->td))) return rc;       // (before the ground cut and the densify step)
     a->nlev = p->nlev; a->ncol = p->ncol;
     a->tb = ts.tb; a->es_tab = ts.es; a->fam_tab = ts.fam;
     // fast level addressing (xp_kernels.hpp load3): common strides, non-negative, column offsets below 4 GiB
@@ -729,7 +744,7 @@ int helicity(const char *entry, const xp_view *z, const xp_view *u, const xp_vie
 }
 
 bool multi_fused_ok(int32_t np, const xp_parcel *parcels, const xp_opts &o, const xp_profile_out *profiles) {
-    if (!(o.flags & XP_OPT_FUSE_PARCELS) || o.moist_mode != XP_MOIST_FAMILY || o.humidity != XP_HUM_DEWPOINT) return false;
+    if (!(o.flags & XP_OPT_FUSE_PARCELS) || o.moist_mode != XP_MOIST_FAMILY || o.humidity == XP_HUM_SPECIFIC) return false;
     if (np != 2 || profiles) return false;                                   // instantiated parcel counts (xp_multi_tu.hip)
     for (int i = 0; i < np; ++i)
         if (parcel_mode(parcels[i]) == XP_PARCEL_EXPLICIT || parcel_mode(parcels[i]) == XP_PARCEL_MAX_CAPE) return false;
@@ -1225,7 +1240,7 @@ int xp_effective_inflow_layer(const xp_view *p, const xp_view *t, const xp_view 
     if ((rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) || (rc = check_opts(opts))) return rc;
     if (z && (rc = check_views({{p, "pressure"}, {z, "height"}}))) return rc;
     if ((rc = check_out("xp_effective_inflow_layer", out, p))) return rc;
-    if (opts.humidity != XP_HUM_DEWPOINT) return fail(XP_E_ARG, "xp_effective_inflow_layer: humidity must be XP_HUM_DEWPOINT");
+    if (opts.humidity == XP_HUM_SPECIFIC) return fail(XP_E_ARG, "xp_effective_inflow_layer: humidity must be XP_HUM_DEWPOINT");
     if (!(std::isfinite(cape_min) && std::isfinite(cin_min))) return fail(XP_E_ARG, "xp_effective_inflow_layer: cape_min and cin_min must be finite");
     if (!(std::isfinite(search_depth) && search_depth > 0.0)) return fail(XP_E_ARG, "xp_effective_inflow_layer: search_depth must be finite and positive");
     const int tm = opts.moist_mode == XP_MOIST_TABLE;
@@ -1234,7 +1249,7 @@ int xp_effective_inflow_layer(const xp_view *p, const xp_view *t, const xp_view 
     xp::EffectiveArgs a;
     memset(&a, 0, sizeof(a));
     if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &a.p)) || (rc = stage_view(st, t, &a.t)) ||
-        (rc = stage_view(st, td, &a.td)) || (z && (rc = stage_view(st, z, &a.z))) ||
+        (rc = stage_view(st, td, &a.td)) || (rc = dewpoint_front(st, p, opts, a.p, a.t, &a.td)) || (z && (rc = stage_view(st, z, &a.z))) ||
         (rc = st.out(out->base_pressure, cb, out->mem, &a.base_p)) || (rc = st.out(out->top_pressure, cb, out->mem, &a.top_p)) ||
         (rc = st.out(out->base_height, cb, out->mem, &a.base_z)) || (rc = st.out(out->top_height, cb, out->mem, &a.top_z)) ||
         (rc = st.out(out->base_index, ib, out->mem, &a.base_idx)) || (rc = st.out(out->top_index, ib, out->mem, &a.top_idx)) ||
@@ -1260,7 +1275,7 @@ int xp_cape_cin_layers(const xp_view *p, const xp_view *t, const xp_view *td, co
     xp::CapeLayersArgs a;
     memset(&a, 0, sizeof(a));
     if ((rc = check_cape(p, t, td, 1, parcel, opts)) || (rc = check_out(entry, out, p))) return rc;
-    if (opts.humidity != XP_HUM_DEWPOINT) return fail(XP_E_ARG, "%s: humidity must be XP_HUM_DEWPOINT", entry);
+    if (opts.humidity == XP_HUM_SPECIFIC) return fail(XP_E_ARG, "%s: humidity must be XP_HUM_DEWPOINT", entry);
     if (!opts.pos_cape_neg_cin) return fail(XP_E_ARG, "%s: layers are defined for pos_cape_neg_cin only", entry);
     if (nlayer < 1 || nlayer > xp::CL_MAX_LAYERS) return fail(XP_E_ARG, "%s: nlayer must lie in 1 ... 4, got %d", entry, (int)nlayer);
     if (!top) return fail(XP_E_ARG, "%s: top: null", entry);

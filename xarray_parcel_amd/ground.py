@@ -9,7 +9,7 @@ import numpy as np
 
 from . import numpy_api as _api
 from ._xr import Dataset
-from .parcel_functions import VERT, _Grid, _device
+from .parcel_functions import VERT, _Grid, _device, _moisture
 
 _CAPE = 'J kg$^{-1}$'
 _ATTRS = {
@@ -43,9 +43,9 @@ def levels_below_ground(pressure, surface_pressure):
     return np.where(above.any(axis=0), above.argmax(axis=0), p.shape[0]).astype(np.int32).reshape(ps.shape)
 
 
-def _inputs(pressure, temperature, dewpoint, surface, vert_dim):
+def _inputs(pressure, temperature, dewpoint, surface, vert_dim, kwargs):
     g = _Grid(temperature, vert_dim)
-    return g, g.values(pressure), g.values(temperature), g.values(dewpoint), tuple(g.values(x) for x in surface)
+    return g, g.values(pressure), g.values(temperature), _moisture(g, dewpoint, kwargs), tuple(g.values(x) for x in surface)
 
 
 def _dataset(g, res, p, ps, suffix=''):
@@ -55,7 +55,7 @@ def _dataset(g, res, p, ps, suffix=''):
 
 
 def _cape_cin(parcel, depth, pressure, temperature, dewpoint, surface, vert_dim, kwargs):
-    g, p, t, td, sfc = _inputs(pressure, temperature, dewpoint, surface, vert_dim)
+    g, p, t, td, sfc = _inputs(pressure, temperature, dewpoint, surface, vert_dim, kwargs)
     res = _device(_api.cape_cin_columns, p, t, td, parcel=parcel, depth=depth, ground=sfc, **kwargs)
     return Dataset(_dataset(g, res, p, sfc[0]))
 
@@ -64,7 +64,9 @@ def surface_based_cape_cin(pressure, temperature, dewpoint, surface_pressure, su
                            vert_dim=VERT, **kwargs):
     """CAPE / CIN of the parcel at the surface (ps, 2 m temperature, 2 m dewpoint) lifted through the isobaric levels above
     it.  pressure [hPa]: on the dims of `temperature`, or the isobars on `vert_dim` alone; temperature, dewpoint [K] on the
-    levels (humidity='specific': specific humidity on the levels, the surface stays a dewpoint); the surface fields on the
+    levels (humidity='specific' / 'relative' / 'mixing_ratio': specific humidity [kg/kg], relative humidity as a fraction or
+    the mixing ratio [kg/kg] on the levels, the surface stays a dewpoint; relative humidity in percent is refused); the
+    surface fields on the
     horizontal dims.  Returns a Dataset of the per-column scalars (cape, cin, the LCL, LFC and EL, status, the parcel; indices
     count the rows of the column cut at the ground) and levels_below_ground; no profile.  kwargs: want, moist and the CAPE /
     CIN options of numpy_api.cape_cin_columns."""
@@ -93,7 +95,7 @@ def cape_cin_multi(pressure, temperature, dewpoint, surface_pressure, surface_te
     them, e.g. ['surface', ('most_unstable', 300), ('mixed_layer', 100)].  Returns one Dataset: the scalars of parcel i
     carry the suffix '_<i>', levels_below_ground none."""
     g, p, t, td, sfc = _inputs(pressure, temperature, dewpoint,
-                               (surface_pressure, surface_temperature, surface_dewpoint), vert_dim)
+                               (surface_pressure, surface_temperature, surface_dewpoint), vert_dim, kwargs)
     outs = _device(_api.cape_cin_multi, p, t, td, parcels, ground=sfc, **kwargs)
     out = {}
     for i, res in enumerate(outs):

@@ -10,7 +10,7 @@ the results, _device turns library errors into the mirror's.
 import numpy as np
 
 from . import numpy_api as _api
-from .parcel_functions import VERT, _Grid, _device
+from .parcel_functions import VERT, _Grid, _device, _moisture
 
 _WIND = 'm s$^{-1}$'
 _SRH = 'm$^{2}$ s$^{-2}$'
@@ -95,9 +95,11 @@ def effective_inflow_layer(pressure, temperature, dewpoint, height=None, vert_di
     parcels have CAPE >= cape_min and CIN >= cin_min, searched over the lowest search_depth hPa.  Returns a Dataset on
     the horizontal dims: base / top pressure [hPa], height [m above the lowest valid level; NaN without `height`] and
     level index (-1: none), and the status bits; with want_candidates also candidate_cape / candidate_cin on the
-    vertical (NaN where a level was not lifted).  Columns without a layer are NaN."""
+    vertical (NaN where a level was not lifted).  Columns without a layer are NaN.  humidity='relative' (a fraction; percent
+    is refused) or 'mixing_ratio' [kg/kg] among the options: what `dewpoint` holds."""
     g = _Grid(pressure, vert_dim)
-    res = _device(_api.effective_inflow_layer, g.values(pressure), g.values(temperature), g.values(dewpoint),
+    res = _device(_api.effective_inflow_layer, g.values(pressure), g.values(temperature),
+                  _moisture(g, dewpoint, cape_cin_options),
                   g.per_col(height), cape_min=cape_min, cin_min=cin_min,
                   search_depth=search_depth, moist=moist, want_candidates=want_candidates, **cape_cin_options)
     out = g.dataset(res, _EFFECTIVE, _ATTRS.get)

@@ -6,7 +6,7 @@ lives next to the mirror (parcel_functions.py) rather than in it, and is built f
 import numpy as np
 
 from . import numpy_api as _api
-from .parcel_functions import VERT, _Grid, _device
+from .parcel_functions import VERT, _Grid, _device, _moisture
 
 _CAPE = 'J kg$^{-1}$'
 _ATTRS = {
@@ -33,13 +33,13 @@ def cape_cin_layers(pressure, temperature, dewpoint, layers, height=None, vert_d
     them (dicts of 'bottom' / 'top' [hPa], '..._height' [m above the lowest valid level], '..._temperature' [K]; per-column
     bounds as DataArrays on the horizontal dims).  Returns a Dataset: cape, cin and the resolved bottom_pressure /
     top_pressure under the leading dim 'layer', and total_cape, total_cin, lfc_pressure, el_pressure, lcl_pressure and
-    status on the horizontal dims.  A layer with a NaN top or top >= bottom is NaN."""
+    status on the horizontal dims.  A layer with a NaN top or top >= bottom is NaN.  humidity='relative' (a fraction; percent is
+    refused) or 'mixing_ratio' [kg/kg] among the options: what `dewpoint` holds."""
     g = _Grid(pressure, vert_dim)
     specs = [{k: g.per_col(v) for k, v in l.items()} for l in layers]
     pv = None if parcel_values is None else [g.per_col(x) for x in parcel_values]
-    res = _device(_api.cape_cin_layers, g.values(pressure), g.values(temperature), g.values(dewpoint), specs,
-                  height=g.per_col(height), parcel=parcel, depth=depth, parcel_values=pv,
-                  moist=moist, **cape_cin_options)
+    res = _device(_api.cape_cin_layers, g.values(pressure), g.values(temperature), _moisture(g, dewpoint, cape_cin_options),
+                  specs, height=g.per_col(height), parcel=parcel, depth=depth, parcel_values=pv, moist=moist, **cape_cin_options)
     out = g.dataset(res, _PER_LAYER, _ATTRS.get, vert=True, vcoord=np.arange(len(specs)), dim='layer')
     for k in _PER_COLUMN:
         out[k] = g.horiz(res[k], k, _ATTRS[k])
@@ -50,7 +50,7 @@ def _one(fn, name, pressure, temperature, dewpoint, height, vert_dim, kwargs):
     g = _Grid(pressure, vert_dim)
     if kwargs.get('parcel_values') is not None:
         kwargs = dict(kwargs, parcel_values=[g.per_col(x) for x in kwargs['parcel_values']])
-    res = _device(fn, g.values(pressure), g.values(temperature), g.values(dewpoint), g.values(height), **kwargs)
+    res = _device(fn, g.values(pressure), g.values(temperature), _moisture(g, dewpoint, kwargs), g.values(height), **kwargs)
     return g.horiz(res, name, _ATTRS[name])
 
 

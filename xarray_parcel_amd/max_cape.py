@@ -6,7 +6,7 @@ highest theta-e.  The reference has no counterpart, so this lives next to the mi
 it, and is built from the mirror's plumbing, as ground.py.
 """
 from . import numpy_api as _api
-from .parcel_functions import VERT, _Grid, _device
+from .parcel_functions import VERT, _Grid, _device, _moisture
 
 _CAPE = 'J kg$^{-1}$'
 _ATTRS = {
@@ -34,10 +34,11 @@ def max_cape_cape_cin(pressure, temperature, dewpoint, vert_dim=VERT, depth=300,
     """CAPE / CIN of the parcel with the largest CAPE among the levels of the lowest `depth` hPa.  pressure [hPa],
     temperature, dewpoint [K] on the same dims with `vert_dim` among them.  Returns a Dataset of the per-column scalars
     (cape, cin, the LCL, LFC and EL, status, the parcel; parcel_index is the level, lfc_index / el_index count from it); no
-    profile.  kwargs: want, moist and the CAPE / CIN options of numpy_api.cape_cin_columns."""
+    profile.  kwargs: want, moist and the CAPE / CIN options of numpy_api.cape_cin_columns; among them humidity='relative'
+    (`dewpoint` holds relative humidity as a fraction; percent is refused) or 'mixing_ratio' [kg/kg], not 'specific'."""
     g = _Grid(temperature, vert_dim)
-    res = _device(_api.cape_cin_columns, g.values(pressure), g.values(temperature), g.values(dewpoint), parcel='max_cape',
-                  depth=depth, **kwargs)
+    res = _device(_api.cape_cin_columns, g.values(pressure), g.values(temperature), _moisture(g, dewpoint, kwargs),
+                  parcel='max_cape', depth=depth, **kwargs)
     return g.dataset(res, attrs=_ATTRS.get)
 
 

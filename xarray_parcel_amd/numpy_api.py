@@ -163,7 +163,7 @@ def _opts(virtual_temperature_correction=True, lcl_interp='log', pos_cape_neg_ci
           moist='exact', humidity='dewpoint', compute='float64'):
     if lcl_interp not in L.LCL_INTERP:
         raise AssertionError('interpolator must be linear or log')          # pf.py:878
-    assert humidity in L.HUMIDITY, "humidity must be 'dewpoint' or 'specific'"
+    assert humidity in L.HUMIDITY, "humidity must be 'dewpoint', 'specific', 'relative' or 'mixing_ratio'"
     assert compute in L.COMPUTE, "compute must be 'float64' or 'float32'"
     return L.Opts(int(bool(virtual_temperature_correction)), L.LCL_INTERP[lcl_interp], int(bool(pos_cape_neg_cin)),
                   int(bool(post_zero_cin)), L.MOIST[moist], L.COMPUTE[compute], L.HUMIDITY[humidity], 0)
@@ -281,6 +281,11 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     with the scalars, computed in the same pass -- no profile array has to exist for it.
     humidity='specific' (keyword): `dewpoint` holds specific humidity [kg/kg] and is converted on load
     (parcel_test.py:262-266 fused into the pass).
+    humidity='relative' / 'mixing_ratio' (XP_HUM_RELATIVE / XP_HUM_MIXING_RATIO, include/xparcel.h): `dewpoint` holds relative
+    humidity over liquid water as a FRACTION (1 = saturated, not percent) or the water-vapour mixing ratio [kg/kg].  One
+    streaming pass in front of the call turns it into a dewpoint (NaN unless the value is > 0), and every result is that of
+    the dewpoint call on it.  They combine with every parcel (an explicit parcel's and ground='s surface dewpoint stay
+    dewpoints), with ground= and with parcel='max_cape'; not with compute='float32'.
     compute='float32': the level walk above the LCL in fp32 arithmetic (float32 arrays, surface parcel, moist='family',
     default options, no profile; `want` then defaults to COMPUTE32_WANT); raises where that kernel does not apply.  None:
     the module default (set_compute), which falls back to fp64 where it does not.
@@ -291,7 +296,8 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     nlev + 2 rows.  Not with an explicit parcel, nor with compute='float32'.
     parcel='max_cape' (XP_PARCEL_MAX_CAPE, include/xparcel.h): the departure level of the lowest `depth` hPa (default 300)
     whose parcel has the largest CAPE -- every level of the window is lifted.  The results are those of the surface call on
-    the column from that level on, 'parcel_index' the level.  Not with ground=, humidity='specific' or compute='float32'."""
+    the column from that level on, 'parcel_index' the level.  Not with ground=, humidity='specific' or compute='float32'
+    (humidity='relative' and 'mixing_ratio' are fine)."""
     c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     moist = moist or _DEFAULT['moist']
     if compute is None:
@@ -325,6 +331,7 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
     (pf.py:1984-2006).  Returns one dict per parcel, bit-identical to what cape_cin_columns() returns for it.
     fused=True (XP_OPT_FUSE_PARCELS; moist='family', two parcels): one pass over the grid for both -- same numbers,
     measured slower than a pass per parcel on MI355X, hence opt-in.
+    humidity (keyword): as in cape_cin_columns; 'relative' and 'mixing_ratio' are converted once for all the parcels.
     ground: as in cape_cin_columns; the grid is cut at the ground once for all the parcels."""
     c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
@@ -537,14 +544,15 @@ def effective_inflow_layer(pressure, temperature, dewpoint, height=None, cape_mi
     contiguous run of levels whose parcels, each lifted as the surface parcel of the column cut off below it, have
     CAPE >= cape_min [J/kg] and CIN >= cin_min (CIN is <= 0 here).  Levels with a NaN in p, T or Td are skipped; the search
     covers the levels with p >= p_lowest - search_depth [hPa].  cape_cin_options: the CAPE / CIN options of
-    cape_cin_columns (virtual_temperature_correction, lcl_interp, pos_cape_neg_cin, post_zero_cin); moist: 'exact' or
-    'table' ('family' runs as 'exact').  Returns a dict of per-column 'base_pressure', 'top_pressure' [hPa],
+    cape_cin_columns (virtual_temperature_correction, lcl_interp, pos_cape_neg_cin, post_zero_cin, and humidity='relative' /
+    'mixing_ratio' for what `dewpoint` holds -- not 'specific'); moist: 'exact' or 'table' ('family' runs as 'exact').
+    Returns a dict of per-column 'base_pressure', 'top_pressure' [hPa],
     'base_height', 'top_height' [m above the lowest valid level: the bounds storm_relative_helicity_layers takes; NaN
     without `height`], 'base_index', 'top_index' (level indices, -1 = none) and 'status' (XP_ST_NO_LAYER: no level
     passes; ST_LAYER_OPEN: the window cut the layer; ST_LCL_NOT_CONVERGED, ST_BAD_PRESSURE); with want_candidates also
     'candidate_cape', 'candidate_cin', shaped like the input: what was computed for every level that was lifted, NaN
     elsewhere."""
-    assert 'humidity' not in cape_cin_options, 'effective_inflow_layer takes dewpoints'
+    assert cape_cin_options.get('humidity') != 'specific', 'effective_inflow_layer does not take specific humidity'
     c = _Call(pressure, temperature, dewpoint, height)
     _same_shape(c.ins, 'pressure, temperature, dewpoint, height must share a shape')
     o = _opts(moist=moist or _DEFAULT['moist'], **cape_cin_options)
@@ -603,12 +611,13 @@ def cape_cin_layers(pressure, temperature, dewpoint, layers, height=None, parcel
                                                 crossing (freezing_level_height's rule), turned into a pressure likewise.
     No bottom: from the first node of the ascent.  Bounds by height or temperature need `height`; they are resolved with
     the library's own entry points in the inputs' memory space.  parcel, depth, parcel_values, moist and the options as in
-    cape_cin_columns (pos_cape_neg_cin must stay True; 'family' runs as 'exact'; dewpoints only).
+    cape_cin_columns (pos_cape_neg_cin must stay True; 'family' runs as 'exact'; humidity 'dewpoint', 'relative' or
+    'mixing_ratio', not 'specific').
     Returns a dict: 'cape', 'cin' [J/kg] of shape (nlayer,) + columns, 'bottom_pressure', 'top_pressure' (the resolved
     bounds; NaN bottom = from the first node), and per column 'total_cape', 'total_cin', 'lfc_pressure', 'el_pressure',
     'lcl_pressure', 'status' (cape_cin_columns' bits, and XP_ST_NO_LAYER where a layer has a NaN top or top >= bottom: that
     layer is NaN)."""
-    assert 'humidity' not in cape_cin_options, 'cape_cin_layers takes dewpoints'
+    assert cape_cin_options.get('humidity') != 'specific', 'cape_cin_layers does not take specific humidity'
     layers = list(layers)
     n = len(layers)
     assert 1 <= n <= L.CAPE_MAX_LAYERS, 'layers: one to four layers'

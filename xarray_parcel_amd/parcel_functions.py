@@ -90,6 +90,16 @@ class _Grid:
         return Dataset({k: wrap(arrs[k], k, attrs(k) if attrs else None, **kw) for k in (keys or arrs)})
 
 
+def _moisture(g, x, options):
+    """g.values(x) for the moisture argument of a CAPE-family call with the keyword `options`.  humidity='relative' takes a
+    fraction: a DataArray that says it holds percent is refused rather than read a hundred times too moist."""
+    units = str(getattr(x, 'attrs', {}).get('units', '')).strip().lower()
+    if options.get('humidity') == 'relative' and units in ('%', 'percent', 'percentage'):
+        raise ValueError("humidity='relative' takes relative humidity as a fraction (1 = saturated), not in %r: "
+                         "divide by 100 first" % x.attrs['units'])
+    return g.values(x)
+
+
 def _attrs_of(ds):
     """attrs(name) of the variables of an input Dataset."""
     return lambda k: getattr(ds[k], 'attrs', {}) if k in ds else {}
@@ -216,7 +226,7 @@ def _run(pressure, temperature, dewpoint, vert_dim, parcel, depth=None, parcel_v
     """The drivers: (cape / cin Dataset, profile Dataset, the parcel as a Dataset with attrs parcel_attrs(name))."""
     kwargs['moist'] = _moist_mode(kwargs.get('moist'))
     g = _Grid(pressure, vert_dim)
-    p, t, td = g.values(pressure), g.values(temperature), g.values(dewpoint)
+    p, t, td = g.values(pressure), g.values(temperature), _moisture(g, dewpoint, kwargs)
     g.check_index('Vert_dim index increments must all be 1.')                          # pf.py:957
     res = _device(_api.cape_cin_columns, p, t, td, parcel=parcel, depth=depth, parcel_values=parcel_values,
                   want_profile=True, **kwargs)
