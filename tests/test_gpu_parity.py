@@ -47,13 +47,17 @@ FKEYS = ('cape', 'cin', 'lcl_pressure', 'lcl_temperature', 'lcl_virtual_temperat
 IKEYS = ('lfc_index', 'el_index', 'status', 'parcel_index')
 
 
-def _log_ties(n_excluded, n_label, n_saturated, n):
+def _log_counts(text):
     # evidence for the bounds below: every classification is appended to gpurun_out/ties.log when that directory exists
     import os
     d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     if os.path.isdir(d):
         with open(os.path.join(d, 'ties.log'), 'a') as fh:
-            fh.write('%s excluded=%d label_only=%d saturated=%d n=%d\n' % (os.environ.get('PYTEST_CURRENT_TEST', '?').split(' ')[0], n_excluded, n_label, n_saturated, n))
+            fh.write('%s %s\n' % (os.environ.get('PYTEST_CURRENT_TEST', '?').split(' ')[0], text))
+
+
+def _log_ties(n_excluded, n_label, n_saturated, n):
+    _log_counts('excluded=%d label_only=%d saturated=%d n=%d' % (n_excluded, n_label, n_saturated, n))
 
 
 def _saturated_tie_columns(got, ref):
@@ -300,25 +304,30 @@ def test_explicit_parcel_and_ragged_shapes(moist):
     assert got['cape'].shape == (0,)
 
 
-@pytest.mark.parametrize('moist', ['exact', 'family'])
-def test_truncated_columns_lcl_at_and_above_the_top(moist):
+OMODE = {'exact': 'rk4', 'family': 'family', 'table': 'table'}       # numpy_api's name of a moist mode -> the C oracle's
+
+
+@pytest.mark.parametrize('moist', ['exact', 'family', 'table'])
+def test_truncated_columns_lcl_at_and_above_the_top(moist, request):
     """Phase A's edge cases: only the lowest 1 ... 8 levels of a 64-level grid, so that for many columns the LCL lies above
     the top level (its node is fed in the iteration past the top, with no upper bracket: NaN environment), is bracketed
     by the last two levels (the crossing level is the last one and waits for the flush iteration), or is the parcel's
     own level (saturated).  Scalars for every parcel, and the profile rows (count, order, NaN pattern) for the surface
     and the mixed-layer parcel."""
+    if moist == 'table':
+        request.getfixturevalue('oracle_tables')                              # both sides look up the same arrays
     full = synth.columns(nlev=64, ncol=6000, seed=41, nan_fraction=0.08, dtype=np.float64)
     for nlev in (1, 2, 3, 5, 8):
         p, t, td = (np.ascontiguousarray(v[:nlev]) for v in full)
         for parcel in ('surface', 'most_unstable', 'mixed_layer'):
             got = xa.cape_cin_columns(p, t, td, parcel=parcel, moist=moist)
-            ref = co.cape_cin_grid(p, t, td, parcel=parcel, moist='rk4' if moist == 'exact' else 'family')
+            ref = co.cape_cin_grid(p, t, td, parcel=parcel, moist=OMODE[moist])
             above = np.nansum(ref['lcl_pressure'] < np.nanmin(p, axis=0))
             assert parcel != 'surface' or above > 100                         # the case this test is about is in the sample
             _compare(got, ref, np.float64, 1e-6)
         for parcel in ('surface', 'mixed_layer'):
             got = xa.cape_cin_columns(p, t, td, parcel=parcel, moist=moist, want_profile=True)
-            ref = co.cape_cin_grid(p, t, td, parcel=parcel, moist='rk4' if moist == 'exact' else 'family', want_profile=True)
+            ref = co.cape_cin_grid(p, t, td, parcel=parcel, moist=OMODE[moist], want_profile=True)
             for k in ref['profile']:
                 a, b = got['profile'][k], ref['profile'][k]
                 assert a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)), (nlev, parcel, k)
@@ -326,8 +335,8 @@ def test_truncated_columns_lcl_at_and_above_the_top(moist):
                 assert not ok.any() or np.max(np.abs(a[ok] - b[ok])) <= 1e-8, (nlev, parcel, k)
 
 
-@pytest.mark.parametrize('moist', ['exact', 'family'])
-def test_nan_pressure_levels(moist):
+@pytest.mark.parametrize('moist', ['exact', 'family', 'table'])
+def test_nan_pressure_levels(moist, request):
     """A NaN PRESSURE inside a column (outside the reference's input contract, README.md:9).
     Above the LCL the kernel follows the reference (the level is an all-NaN node).  Below the LCL the reference's
     insert_level puts a copy of the LCL into the NaN slot (its fill-value trick, pf.py:962-966) and integrates over the
@@ -337,7 +346,9 @@ def test_nan_pressure_levels(moist):
     the contract."""
     nlev, ncol = 30, 4000
     p, t, td = synth.columns(nlev=nlev, ncol=ncol, seed=9, dtype=np.float64)
-    omode = ('rk4' if moist == 'exact' else 'family')
+    omode = OMODE[moist]
+    if moist == 'table':
+        request.getfixturevalue('oracle_tables')
     base = co.cape_cin_grid(p, t, td, moist=omode)
     first_above = np.argmax(p < base['lcl_pressure'][None, :], axis=0)         # first level above the LCL
     q, t2, td2 = p.copy(), t.copy(), td.copy()
