@@ -13,8 +13,9 @@ import re
 from tests import stream_cases as S
 from xarray_parcel_amd import _lib as L
 
-# the asynchronous calls and the (zero-based) position of their stream argument
-STREAM_ARG = {'hipLaunchKernelGGL': 4, 'hipMemcpyAsync': 4, 'hipMemsetAsync': 3, 'hipMallocAsync': 2, 'hipFreeAsync': 1}
+# the asynchronous calls (launch_columns: csrc/xp_launch.hpp, the launch of all but five kernels) and the (zero-based)
+# position of their stream argument
+STREAM_ARG = {'launch_columns': 2, 'hipLaunchKernelGGL': 4, 'hipMemcpyAsync': 4, 'hipMemsetAsync': 3, 'hipMallocAsync': 2, 'hipFreeAsync': 1}
 DEFAULT_STREAM = re.compile(r'^(\(\s*hipStream_t\s*\)\s*)?\(?\s*(0|NULL|nullptr|hipStreamLegacy|hipStreamPerThread)\s*\)?$')
 # the calls that wait for the device, and the only functions that may hold them
 BLOCKING = ('hipMemcpy', 'hipMemset', 'hipMalloc', 'hipFree', 'hipDeviceSynchronize')
@@ -81,6 +82,17 @@ def call_arguments(text, start):
     raise AssertionError('unbalanced call')
 
 
+def join_template_arguments(args):
+    """call_arguments' pieces with the commas of a kernel's template arguments put back: launch_columns(k<T, N>, n, s, ...)."""
+    out = []
+    for a in args:
+        if out and out[-1].count('<') > out[-1].count('>'):
+            out[-1] += ', ' + a
+        else:
+            out.append(a)
+    return out
+
+
 HEADER = re.compile(r'(~?\w[\w]*)\s*\([^;{}]*\)\s*(?:const\s*)?(?:noexcept\s*)?(?::[^;{}]*)?$', re.S)
 RECORD = re.compile(r'\b(?:struct|class)\s+(\w+)[^;{}()]*$', re.S)
 
@@ -120,10 +132,12 @@ def scan_sources(sources):
         text = strip_comments_and_strings(raw)
         owner = enclosing_functions(text)
         where = lambda pos: '%s:%d' % (path, text.count('\n', 0, pos) + 1)
-        for m in re.finditer(r'\b(hip\w+)\s*\(', text):
+        for m in re.finditer(r'\b(hip\w+|launch_columns)\s*\(', text):
             name, pos = m.group(1), m.start()
             if name in STREAM_ARG:
                 args = call_arguments(text, m.end() - 1)
+                if name == 'launch_columns':
+                    args = join_template_arguments(args)
                 if len(args) <= STREAM_ARG[name]:
                     bad.append('%s: %s names no stream (%d arguments)' % (where(pos), name, len(args)))
                 elif DEFAULT_STREAM.match(args[STREAM_ARG[name]]):
@@ -148,7 +162,7 @@ def test_source_rule():
     sources = csrc_sources()
     text = '\n'.join(strip_comments_and_strings(s) for s in sources.values())
     # the scan sees what it is meant to see: the launch sites and the allowed waits are all there
-    assert len(re.findall(r'\bhipLaunchKernelGGL\s*\(', text)) >= 38 and len(re.findall(r"\blaunch\s*\(", text)) >= 30
+    assert len(re.findall(r'\bhipLaunchKernelGGL\s*\(', text)) >= 5 and len(re.findall(r"\blaunch_columns\s*\(", text)) >= 44
     assert len(re.findall(r'\bhipStreamSynchronize\s*\(', text)) == 3 and len(re.findall(r'\bhipDeviceSynchronize\s*\(', text)) == 3
     bad = scan_sources(sources)
     assert not bad, '\n' + '\n'.join(bad)
@@ -164,10 +178,11 @@ def test_source_rule_sees_violations():
         assert src.count(old) == 1, old
         return scan_sources({path: src.replace(old, new)})          # (the other files: test_source_rule)
     line = lambda old: src[:src.index(old)].count('\n') + 1
-    old = 'hipLaunchKernelGGL(k, dim3(blocks(n)), dim3(256), 0, st.s, args...)'
+    old = 'launch_columns(xp::k_per_point<decltype(z), Op>, n, st.s, a)'
     for zero in ('0', 'nullptr', '(hipStream_t)0', 'NULL'):
         bad = doctored(old, old.replace('st.s', zero))
-        assert bad == ['%s:%d: hipLaunchKernelGGL on the default stream (%r)' % (path, line(old), zero)], bad
+        assert bad == ['%s:%d: launch_columns on the default stream (%r)' % (path, line(old), zero)], bad
+    assert doctored(old, old.replace(', st.s, a', '')) == ['%s:%d: launch_columns names no stream (2 arguments)' % (path, line(old))]
     old = 'hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s)'
     assert doctored(old, 'hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice)') == \
         ['%s:%d: hipMemcpyAsync names no stream (4 arguments)' % (path, line(old))]
@@ -182,5 +197,11 @@ def test_source_rule_sees_violations():
     assert doctored(old, old + ' (void)hipStreamSynchronize(st.s);') == ['%s:%d: hipStreamSynchronize in cape_pass' % (path, line(old))]
     # an entry point of its own translation unit
     path, src = 'xarray_parcel_amd/csrc/xp_ecape_tu.hip', sources['xarray_parcel_amd/csrc/xp_ecape_tu.hip']
-    old = 'hipLaunchKernelGGL(k_ncape<float>, gr, bl, 0, s, a)'
-    assert doctored(old, old.replace(', s, a', ', 0, a')) == ["%s:%d: hipLaunchKernelGGL on the default stream ('0')" % (path, line(old))]
+    old = 'launch_columns(k_ncape<decltype(z)>, a.ncol, s, a)'
+    assert doctored(old, old.replace(', s, a', ', 0, a')) == ["%s:%d: launch_columns on the default stream ('0')" % (path, line(old))]
+    # the launch header itself, and a launcher with a geometry of its own
+    for f, old in (('xp_launch.hpp', 'hipLaunchKernelGGL(k, dim3(blocks_for(n)), dim3(256), 0, s, args...)'),
+                   ('xp_humidity_tu.hip', 'hipLaunchKernelGGL((k_dewpoint_from<T, KIND(), VEC()>), gr, dim3(256), 0, s, a)')):
+        path = 'xarray_parcel_amd/csrc/' + f
+        src = sources[path]
+        assert doctored(old, old.replace(', 0, s, a', ', 0, 0, a')) == ["%s:%d: hipLaunchKernelGGL on the default stream ('0')" % (path, line(old))]

@@ -2,8 +2,7 @@
 // family units' flags (xarray_parcel_amd/_lib.py): ONE 1024-thread workgroup per CU, whose LDS holds the e_s / ln tables
 // (11.8 KB), the fp32 copy of the family table (22.8 KB) and the scan's slots (96 KB); an ordinary launch, or persistent
 // wavefronts where the fp64 family kernel takes them (CapeArgs::persist).
-#include <hip/hip_runtime.h>
-
+#include "xp_launch.hpp"
 #include "xp_cape_f32.hpp"
 
 namespace xp {
@@ -14,14 +13,10 @@ static_assert((LDS_TAB + SLOT_FIELDS * SLOT_STRIDE) * 8 + FAM_COEFS * 4 + 64 <= 
 void launch_cape_f32(const CapeArgs &a, hipStream_t s) {
     if (a.ncol == 0) return;
     const int b = XP_CAPE_THREADS;
-    unsigned nblk = (unsigned)((a.ncol + b - 1) / b);
-    if (a.persist) {                                       // persistent wavefronts: one workgroup per CU (as xp_cape_tu.hip)
-        static const int n_cu = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-        if (nblk > (unsigned)n_cu) nblk = (unsigned)n_cu;
-        hipLaunchKernelGGL((k_cape_f32<float, true>), dim3(nblk), dim3(b), 0, s, a);
-        return;
-    }
-    hipLaunchKernelGGL((k_cape_f32<float, false>), dim3(nblk), dim3(b), 0, s, a);
+    with_bool(a.persist, [&](auto PERSIST) {               // persistent wavefronts: one workgroup per CU (as xp_cape_tu.hip)
+        const unsigned nblk = PERSIST() ? persistent_blocks(a.ncol, b) : blocks_for(a.ncol, b);
+        hipLaunchKernelGGL((k_cape_f32<float, PERSIST()>), dim3(nblk), dim3(b), 0, s, a);
+    });
 }
 
 }  // namespace xp

@@ -2,10 +2,9 @@
 // moist mode (4 parcel modes x profile on/off x dewpoint / specific-humidity input, + the default-options specialisation of
 // the CAPE/CIN-only dewpoint-input kernels) and the launcher that picks one.
 // Compiled six times by the build (xarray_parcel_amd/_lib.py), e.g. -DXP_TU_T=double -DXP_TU_MODE=0.
-#include <hip/hip_runtime.h>
-
 #include <cstdlib>
 
+#include "xp_launch.hpp"
 #include "xp_kernels.hpp"
 
 #if !defined(XP_TU_T) || !defined(XP_TU_MODE)
@@ -20,31 +19,27 @@ int cape_block() {             // XP_CAPE_BLOCK: workgroup size for experiments 
     return b;
 }
 
+// k_cape_cin<T, PM, PROFILE, MODE, HUM, DEF, LEAN, PERSIST> for one call.  Which of the DEF / LEAN / LAZY instantiations a
+// moist mode has is stated here and nowhere else; tests/test_kernel_resources.py watches the numbers the rules rest on.
 template <typename T, int PM, int MODE, bool PERSIST> void launch_p(const CapeArgs &a, bool profile, hipStream_t s) {
     const int b = cape_block();
-    unsigned nblk = (unsigned)((a.ncol + b - 1) / b);
-    if (PERSIST) {                                     // persistent wavefronts: one workgroup's worth of waves per CU
-        static const int n_cu = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-        unsigned cap = (unsigned)(n_cu * (b >= 1024 ? 1 : 1024 / b));
-        if (nblk > cap) nblk = cap;
-    }
-    dim3 gr(nblk), bl(b);
-    if (a.hum) {
-        if (profile) hipLaunchKernelGGL((k_cape_cin<T, PM, true, MODE, true, false, false, PERSIST>), gr, bl, 0, s, a);
-        else hipLaunchKernelGGL((k_cape_cin<T, PM, false, MODE, true, false, false, PERSIST>), gr, bl, 0, s, a);
-        return;
-    }
+    // persistent wavefronts: one 1024-thread workgroup's worth of waves per CU
+    const unsigned nblk = PERSIST ? persistent_blocks(a.ncol, b, b >= 1024 ? 1 : 1024 / b) : blocks_for(a.ncol, b);
+    auto go = [&](auto PROFILE, auto HUM, auto DEF, auto LEAN) {
+        hipLaunchKernelGGL((k_cape_cin<T, PM, PROFILE(), MODE, HUM(), DEF(), LEAN(), PERSIST>), dim3(nblk), dim3(b), 0, s, a);
+    };
+    constexpr std::true_type yes;
+    constexpr std::false_type no;
+    if (a.hum) { with_bool(profile, [&](auto PROFILE) { go(PROFILE, yes, no, no); }); return; }
+    const bool dflt = a.vtc && a.pos_neg && a.log_interp;                           // the reference's defaults (pf.py:1396, 1293)
+    const bool lean = cape_cin_only(a);
     if (profile) {
         if constexpr (MODE == 2) {
             // the lifted index and nothing else of the profile, default options, CAPE / CIN only (the product bundle's
             // parcel passes): the LAZY instantiation (PROFILE + DEF + LEAN, see k_cape_cin)
-            const bool cc_only = !a.s.lfc_t && !a.s.el_t && !a.s.lfc_idx && !a.s.el_idx && !a.s.status;
-            if (a.prof.nlev_out == 0 && a.prof.li && a.vtc && a.pos_neg && a.log_interp && cc_only) {
-                hipLaunchKernelGGL((k_cape_cin<T, PM, true, MODE, false, true, true, PERSIST>), gr, bl, 0, s, a);
-                return;
-            }
+            if (a.prof.nlev_out == 0 && a.prof.li && dflt && lean) { go(yes, no, yes, yes); return; }
         }
-        hipLaunchKernelGGL((k_cape_cin<T, PM, true, MODE, false, false, false, PERSIST>), gr, bl, 0, s, a);
+        go(yes, no, no, no);
         return;
     }
     // Default-options (DEF) and CAPE/CIN-only (LEAN) specialisations: the reference's default option set as compile-time
@@ -54,31 +49,22 @@ template <typename T, int PM, int MODE, bool PERSIST> void launch_p(const CapeAr
     // of the register allocator without a spill for every parcel (121-128 VGPRs; round 2's code base spilled here and
     // always took the generic kernel) and runs 2.5-5 % faster than the generic one (same-box A/B); DEF
     // alone still spills for the searching parcels (40-55 VGPRs) and stays with the generic kernel.
-    // tests/test_kernel_resources.py watches the numbers this rule rests on.
-    const bool lean = !a.s.lfc_t && !a.s.el_t && !a.s.lfc_idx && !a.s.el_idx && !a.s.status;   // no LFC / EL temperatures, indices or status word wanted
-    const bool dflt = a.vtc && a.pos_neg && a.log_interp;                           // the reference's defaults (pf.py:1396, 1293)
-    if (dflt && lean) { hipLaunchKernelGGL((k_cape_cin<T, PM, false, MODE, false, true, true, PERSIST>), gr, bl, 0, s, a); return; }
+    if (dflt && lean) { go(no, no, yes, yes); return; }
     if constexpr (MODE != 2) {
-        if (dflt) { hipLaunchKernelGGL((k_cape_cin<T, PM, false, MODE, false, true, false, PERSIST>), gr, bl, 0, s, a); return; }
+        if (dflt) { go(no, no, yes, no); return; }
     }
-    hipLaunchKernelGGL((k_cape_cin<T, PM, false, MODE, false, false, false, PERSIST>), gr, bl, 0, s, a);
-}
-template <typename T, int PM, int MODE> void launch_t(const CapeArgs &a, bool profile, hipStream_t s) {
-    if constexpr (MODE == 2) {
-        if (a.persist) { launch_p<T, PM, MODE, true>(a, profile, s); return; }
-    }
-    launch_p<T, PM, MODE, false>(a, profile, s);
+    go(no, no, no, no);
 }
 
 }  // namespace
 
 template <> void launch_cape_mode<XP_TU_T, XP_TU_MODE>(const CapeArgs &a, int pm, bool profile, hipStream_t s) {
-    switch (pm) {
-        case PM_SURFACE: launch_t<XP_TU_T, PM_SURFACE, XP_TU_MODE>(a, profile, s); break;
-        case PM_MU: launch_t<XP_TU_T, PM_MU, XP_TU_MODE>(a, profile, s); break;
-        case PM_ML: launch_t<XP_TU_T, PM_ML, XP_TU_MODE>(a, profile, s); break;
-        default: launch_t<XP_TU_T, PM_EXPLICIT, XP_TU_MODE>(a, profile, s); break;
-    }
+    with_one_of<PM_SURFACE, PM_MU, PM_ML, PM_EXPLICIT>(pm, [&](auto PM) {
+        if constexpr (XP_TU_MODE == 2) {                   // persistent wavefronts are the family kernels' alone
+            if (a.persist) { launch_p<XP_TU_T, PM(), XP_TU_MODE, true>(a, profile, s); return; }
+        }
+        launch_p<XP_TU_T, PM(), XP_TU_MODE, false>(a, profile, s);
+    });
 }
 
 }  // namespace xp

@@ -27,6 +27,8 @@ struct CapeArgs {
     ScalarsOut s;
     ProfileOut prof;
 };
+// "CAPE / CIN only" (host side): no LFC / EL temperatures, interval indices or status word wanted, so nothing tracks them
+inline bool cape_cin_only(const CapeArgs &a) { return !a.s.lfc_t && !a.s.el_t && !a.s.lfc_idx && !a.s.el_idx && !a.s.status; }
 
 enum { PM_SURFACE = 0, PM_MU = 1, PM_ML = 2, PM_EXPLICIT = 3 };
 

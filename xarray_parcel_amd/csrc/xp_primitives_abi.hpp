@@ -1,5 +1,6 @@
 // xp_primitives_abi.hpp -- C ABI of the array primitives (kernels: xp_primitives.hpp; declarations and the reference
 // functions they replace: include/xparcel.h).  Included by xparcel.hip, whose staging helpers it uses.
+#include "xp_launch.hpp"
 #include "xp_primitives.hpp"
 
 extern "C" {
@@ -17,8 +18,8 @@ int xp_insert_level(const xp_view *coords, const xp_view *variable, const void *
     const size_t cb = rows_bytes(coords, 1);
     if ((rc = stage_view(st, coords, &cv)) || (rc = stage_view(st, variable, &vv)) || (rc = st.in(level_coord, cb, coords->mem, &lc)) ||
         (rc = st.in(level_value, cb, coords->mem, &lv)) || (rc = st.out(out, rows_bytes(coords, coords->nlev + 1), coords->mem, &od))) return rc;
-    by_dtype(coords->dtype, [&](auto z) {
-        launch(xp::k_insert_level<decltype(z)>, coords->ncol, st, cv, vv, coords->nlev, coords->ncol, lc, lv, fill_value, dense_out(od, coords->ncol));
+    with_type(coords->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_insert_level<decltype(z)>, coords->ncol, st.s, cv, vv, coords->nlev, coords->ncol, lc, lv, fill_value, dense_out(od, coords->ncol));
     });
     return st.finish();
 }
@@ -34,7 +35,7 @@ int xp_find_intersections(const xp_view *x, const xp_view *a, const xp_view *b, 
     xp::SixOut o;
     if ((rc = stage_view(st, x, &xv)) || (rc = stage_view(st, a, &av)) || (b && (rc = stage_view(st, b, &bv)))) return rc;
     for (int i = 0; i < 6; ++i) if ((rc = st.out(out[i], rows_bytes(x, x->nlev - 1), x->mem, &o.p[i]))) return rc;
-    by_dtype(x->dtype, [&](auto z) { launch(xp::k_find_intersections<decltype(z)>, x->ncol, st, xv, av, bv, x->nlev, x->ncol, (int)log_x, o); });
+    with_type(x->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_find_intersections<decltype(z)>, x->ncol, st.s, xv, av, bv, x->nlev, x->ncol, (int)log_x, o); });
     return st.finish();
 }
 
@@ -52,8 +53,8 @@ int xp_trapz(const xp_view *dat, const xp_view *x, const uint8_t *mask, int32_t 
     void *od;
     if ((rc = stage_view(st, dat, &dv)) || (rc = stage_view(st, x, &xv)) ||
         (rc = st.in(mask, (size_t)(dat->nlev - 1) * (size_t)dat->ncol, dat->mem, &dm)) || (rc = st.out(out, rows_bytes(dat, 1), dat->mem, &od))) return rc;
-    by_dtype(dat->dtype, [&](auto z) {
-        launch(xp::k_trapz<decltype(z)>, dat->ncol, st, dv, xv, (const uint8_t *)dm, dat->nlev, dat->ncol, (int)only_positive, (int)only_negative, od);
+    with_type(dat->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_trapz<decltype(z)>, dat->ncol, st.s, dv, xv, (const uint8_t *)dm, dat->nlev, dat->ncol, (int)only_positive, (int)only_negative, od);
     });
     return st.finish();
 }
@@ -70,7 +71,7 @@ int xp_trap_around_zeros(const xp_view *x, const xp_view *y, int32_t log_x, void
     if ((rc = stage_view(st, x, &xv)) || (rc = stage_view(st, y, &yv))) return rc;
     for (int i = 0; i < 5; ++i) if ((rc = st.out(areas[i], rows_bytes(x, 2 * x->nlev - 1), x->mem, &o.p[i]))) return rc;
     if ((rc = st.out(mask, (size_t)x->nlev * (size_t)x->ncol, x->mem, &dm))) return rc;
-    by_dtype(x->dtype, [&](auto z) { launch(xp::k_trap_around_zeros<decltype(z)>, x->ncol, st, xv, yv, x->nlev, x->ncol, (int)log_x, o, (uint8_t *)dm); });
+    with_type(x->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_trap_around_zeros<decltype(z)>, x->ncol, st.s, xv, yv, x->nlev, x->ncol, (int)log_x, o, (uint8_t *)dm); });
     return st.finish();
 }
 
@@ -85,7 +86,7 @@ int xp_bound_pressure(const xp_view *pressure, const void *bound, void *out, voi
     void *od;
     if ((rc = stage_view(st, pressure, &pv)) || (rc = st.in(bound, rows_bytes(pressure, 1), pressure->mem, &db)) ||
         (rc = st.out(out, rows_bytes(pressure, 1), pressure->mem, &od))) return rc;
-    by_dtype(pressure->dtype, [&](auto z) { launch(xp::k_bound_pressure<decltype(z)>, pressure->ncol, st, pv, pressure->nlev, pressure->ncol, db, od); });
+    with_type(pressure->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_bound_pressure<decltype(z)>, pressure->ncol, st.s, pv, pressure->nlev, pressure->ncol, db, od); });
     return st.finish();
 }
 
@@ -100,8 +101,8 @@ int xp_get_layer(const xp_view *pressure, const xp_view *variable, double depth,
     void *od;
     if ((rc = stage_view(st, pressure, &pv)) || (rc = stage_view(st, variable, &vv)) ||
         (rc = st.out(out, rows_bytes(pressure, pressure->nlev + (interpolate ? 1 : 0)), pressure->mem, &od))) return rc;
-    by_dtype(pressure->dtype, [&](auto z) {
-        launch(xp::k_get_layer<decltype(z)>, pressure->ncol, st, pv, vv, pressure->nlev, pressure->ncol, depth, (int)interpolate,
+    with_type(pressure->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_get_layer<decltype(z)>, pressure->ncol, st.s, pv, vv, pressure->nlev, pressure->ncol, depth, (int)interpolate,
                (int)variable_is_pressure, dense_out(od, pressure->ncol));
     });
     return st.finish();
@@ -117,7 +118,7 @@ int xp_shift_out_nans(const xp_view *name, const xp_view *variable, void *out, v
     void *od;
     if ((rc = stage_view(st, name, &nv)) || (rc = stage_view(st, variable, &vv)) ||
         (rc = st.out(out, rows_bytes(name, name->nlev), name->mem, &od))) return rc;
-    by_dtype(name->dtype, [&](auto z) { launch(xp::k_shift_out_nans<decltype(z)>, name->ncol, st, nv, vv, name->nlev, name->ncol, dense_out(od, name->ncol)); });
+    with_type(name->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_shift_out_nans<decltype(z)>, name->ncol, st.s, nv, vv, name->nlev, name->ncol, dense_out(od, name->ncol)); });
     return st.finish();
 }
 
@@ -147,11 +148,9 @@ int xp_rebase_profile(const xp_view *p, const xp_view *t, const xp_view *td, con
     xp::RebaseOut o;
     if ((rc = st.out(out_p, rows_bytes(p, rows), p->mem, &o.p)) || (rc = st.out(out_t, rows_bytes(p, rows), p->mem, &o.t)) ||
         (rc = st.out(out_td, rows_bytes(p, rows), p->mem, &o.td))) return rc;
-    by_dtype(p->dtype, [&](auto z) {
-        using T = decltype(z);
-        if (ml) launch(xp::k_rebase_select<T, xp::PM_ML>, ncol, st, a, thr, any);
-        else launch(xp::k_rebase_select<T, xp::PM_MU>, ncol, st, a, thr, any);
-    });
+    with_type(p->dtype == XP_F64, [&](auto z) { with_one_of<xp::PM_ML, xp::PM_MU>(parcel->mode, [&](auto PM) {
+        launch_columns(xp::k_rebase_select<decltype(z), PM()>, ncol, st.s, a, thr, any);
+    }); });
     std::vector<int32_t> kept((size_t)nlev, 0);
     HIP_TRY(hipMemcpyAsync(kept.data(), any, (size_t)nlev * 4, hipMemcpyDeviceToHost, st.s));
     HIP_TRY(hipStreamSynchronize(st.s));                                   // the number of surviving levels shapes the output
@@ -159,11 +158,9 @@ int xp_rebase_profile(const xp_view *p, const xp_view *t, const xp_view *td, con
     for (int64_t k = 0; k < nlev; ++k) nkept += kept[k] != 0;
     if (level_kept) memcpy(level_kept, kept.data(), (size_t)nlev * 4);
     *nlev_out = nkept + (ml ? 1 : 0);
-    by_dtype(p->dtype, [&](auto z) {
-        using T = decltype(z);
-        if (ml) launch(xp::k_rebase_write<T, xp::PM_ML>, ncol, st, a, thr, any, rows, o);
-        else launch(xp::k_rebase_write<T, xp::PM_MU>, ncol, st, a, thr, any, rows, o);
-    });
+    with_type(p->dtype == XP_F64, [&](auto z) { with_one_of<xp::PM_ML, xp::PM_MU>(parcel->mode, [&](auto PM) {
+        launch_columns(xp::k_rebase_write<decltype(z), PM()>, ncol, st.s, a, thr, any, rows, o);
+    }); });
     if ((rc = st.finish())) return rc;
     HIP_TRY(hipStreamSynchronize(st.s));
     return 0;
@@ -184,7 +181,7 @@ int xp_interp1d(const xp_view *at, const xp_view *xp_, const xp_view *fp, void *
         (rc = st.out(out, rows_bytes(at, at->nlev), at->mem, &od))) return rc;
     if (xp_->ncol == 1 && at->ncol != 1) { xv.cs = 0; xv.ls = xp_->mem == XP_MEM_HOST ? 1 : xp_->lev_stride; }   // one set of points for all columns
     if (fp->ncol == 1 && at->ncol != 1) { fv.cs = 0; fv.ls = fp->mem == XP_MEM_HOST ? 1 : fp->lev_stride; }
-    by_dtype(at->dtype, [&](auto z) { launch(xp::k_interp1d<decltype(z)>, at->ncol, st, av, xv, fv, at->nlev, xp_->nlev, at->ncol, od); });
+    with_type(at->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_interp1d<decltype(z)>, at->ncol, st.s, av, xv, fv, at->nlev, xp_->nlev, at->ncol, od); });
     return st.finish();
 }
 
@@ -209,7 +206,7 @@ int xp_wind_shear(const xp_view *wind_u, const xp_view *wind_v, const xp_view *h
         (rc = st.out(positive_shear, (size_t)wind_u->ncol * 4, wind_u->mem, &pos))) return rc;
     a.positive_shear = (int32_t *)pos;
     a.nwind = wind_u->nlev; a.ncol = wind_u->ncol; a.shear_height = shear_height;
-    by_dtype(wind_u->dtype, [&](auto z) { launch(xp::k_wind_shear<decltype(z)>, wind_u->ncol, st, a); });
+    with_type(wind_u->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_wind_shear<decltype(z)>, wind_u->ncol, st.s, a); });
     return st.finish();
 }
 
@@ -250,7 +247,7 @@ int xp_storm_proxies(int64_t n, int32_t dtype, int32_t mem, const xp_proxies_in 
         a.proxy[i] = (int32_t *)d;
     }
     if ((rc = st.out(out->ship, b, mem, &a.ship))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_storm_proxies<decltype(z)>, n, st, a); });
+    with_type(dtype == XP_F64, [&](auto z) { launch_columns(xp::k_storm_proxies<decltype(z)>, n, st.s, a); });
     return st.finish();
 }
 

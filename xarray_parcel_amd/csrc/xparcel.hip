@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/xparcel.h"
+#include "xp_launch.hpp"
 #include "xp_kernels.hpp"
 #include "xp_cape_f32.hpp"
 #include "xp_multi.hpp"
@@ -41,6 +42,8 @@ static_assert(xp::ISEN_MAX_LEVELS == XP_ISEN_MAX_LEVELS && xp::ISEN_MAX_VARS == 
 static_assert(xp::HY_MAX_LAYERS == sizeof(xp_hydrostatic_out::thickness) / sizeof(void *) && xp::HY_DEWPOINT == XP_HUM_DEWPOINT + 1 &&
               xp::HY_SPECIFIC == XP_HUM_SPECIFIC + 1, "the hydrostatic kernel's limits and moisture kinds follow the ABI's");
 static_assert(xp::HUM_RELATIVE == XP_HUM_RELATIVE && xp::HUM_MIXING_RATIO == XP_HUM_MIXING_RATIO, "the conversion kernel's moisture kinds are the ABI's");
+static_assert(xp::PM_SURFACE == XP_PARCEL_SURFACE && xp::PM_MU == XP_PARCEL_MOST_UNSTABLE && xp::PM_ML == XP_PARCEL_MIXED_LAYER &&
+              xp::PM_EXPLICIT == XP_PARCEL_EXPLICIT, "the kernels' parcel kinds are the ABI's");
 static_assert(xp::CCL_TOP == XP_CCL_TOP && xp::CCL_BOTTOM == XP_CCL_BOTTOM, "the kernel's CCL choices are the ABI's");
 static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
               xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
@@ -333,17 +336,12 @@ struct Entry : DevGuard, Stager {
     int rc;
     explicit Entry(void *stream) : Stager(stream), rc(ensure_init()) {}
 };
-unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// f(T()) with T the element type of dtype: a generic lambda names a kernel once for both instantiations
-template <typename F> void by_dtype(int dtype, F &&f) {
-    if (dtype == XP_F64) f(double());
-    else f(float());
-}
-// one thread per element of an n-element grid, 256 per workgroup, on the call's stream; n == 0 launches nothing
-template <typename... P, typename... A> void launch(void (*k)(P...), int64_t n, const Stager &st, const A &...args) {
-    if (n > 0) hipLaunchKernelGGL(k, dim3(blocks(n)), dim3(256), 0, st.s, args...);
-}
+// run-time values -> template arguments, and the launch geometry: xp_launch.hpp
+using xp::launch_columns;
+using xp::with_bool;
+using xp::with_int;
+using xp::with_one_of;
+using xp::with_type;
 
 // A per-point entry point (kernel and operations: xp_per_point.hpp): n points of dtype in mem.  The first n_required of
 // `in` must be given, the rest may be null, and so may the outputs unless out_required.
@@ -364,7 +362,7 @@ template <typename Op> int per_point(const char *entry, int64_t n, int32_t dtype
     for (const void *p : in) if ((rc = st.in(p, b, mem, &a.in[i++]))) return rc;
     i = 0;
     for (void *p : out) if ((rc = st.out(p, b, mem, &a.out[i++]))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_per_point<decltype(z), Op>, n, st, a); });
+    with_type(dtype == XP_F64, [&](auto z) { launch_columns(xp::k_per_point<decltype(z), Op>, n, st.s, a); });
     return st.finish();
 }
 
@@ -411,24 +409,17 @@ bool persist(int mode, int64_t ncol) {
 }
 
 // k_cape_cin's 96 instantiations are compiled in six translation units (xp_cape_tu.hip, one per dtype x moist mode) so
-// that the build parallelises; this file only dispatches to them.
-template <typename T, int PM> void launch_cape(const xp::CapeArgs &a, bool profile, hipStream_t s) {
+// that the build parallelises; this file only picks the unit.  pm: the parcel's XP_PARCEL_*, which is the units' PM_*
+// (launch_cape_mode makes it a template argument; any other value is the explicit parcel there).
+template <typename T> void launch_cape(const xp::CapeArgs &a, int pm, bool profile, hipStream_t s) {
     if (a.ncol == 0) return;
-    if (a.table_mode) xp::launch_cape_mode<T, 1>(a, PM, profile, s);
+    if (a.table_mode) xp::launch_cape_mode<T, 1>(a, pm, profile, s);
     else if (a.flags) {                                      // family mode: fast pass, then RK4 for the flagged columns
-        xp::launch_cape_mode<T, 2>(a, PM, profile, s);
+        xp::launch_cape_mode<T, 2>(a, pm, profile, s);
         xp::CapeArgs b = a;
         b.only_flagged = 1;
-        xp::launch_cape_mode<T, 0>(b, PM, profile, s);
-    } else xp::launch_cape_mode<T, 0>(a, PM, profile, s);
-}
-template <typename T> void launch_cape_pm(const xp::CapeArgs &a, int pm, bool profile, hipStream_t s) {
-    switch (pm) {
-        case XP_PARCEL_SURFACE: launch_cape<T, xp::PM_SURFACE>(a, profile, s); break;
-        case XP_PARCEL_MOST_UNSTABLE: launch_cape<T, xp::PM_MU>(a, profile, s); break;
-        case XP_PARCEL_MIXED_LAYER: launch_cape<T, xp::PM_ML>(a, profile, s); break;
-        default: launch_cape<T, xp::PM_EXPLICIT>(a, profile, s); break;
-    }
+        xp::launch_cape_mode<T, 0>(b, pm, profile, s);
+    } else xp::launch_cape_mode<T, 0>(a, pm, profile, s);
 }
 
 // the options of a call that passes none (the reference's defaults)
@@ -530,11 +521,9 @@ int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td
         if ((rc = st.in(ground->pressure, b, p->mem, &ga.ps)) || (rc = st.in(ground->temperature, b, p->mem, &ga.ts)) ||
             (rc = st.in(ground->dewpoint, b, p->mem, &ga.tds)) || (rc = st.alloc(rows_bytes(p, p->nlev + 1), &ga.op)) ||
             (rc = st.alloc(rows_bytes(p, p->nlev + 1), &ga.ot)) || (rc = st.alloc(rows_bytes(p, p->nlev + 1), &ga.otd))) return rc;
-        by_dtype(p->dtype, [&](auto z) {
-            using T = decltype(z);
-            if (a->hum) launch(xp::k_ground_rebase<T, true>, p->ncol, st, ga);
-            else launch(xp::k_ground_rebase<T, false>, p->ncol, st, ga);
-        });
+        with_type(p->dtype == XP_F64, [&](auto z) { with_bool(a->hum, [&](auto HUM) {
+            launch_columns(xp::k_ground_rebase<decltype(z), HUM()>, p->ncol, st.s, ga);
+        }); });
         a->nlev = p->nlev + 1; a->hum = 0;
         a->p = {ga.op, p->ncol, 1}; a->t = {ga.ot, p->ncol, 1}; a->td = {ga.otd, p->ncol, 1};
     } else if (!(same && a->p.cs >= 0 && a->p.ls >= 0 && (unsigned long long)a->p.cs * row < (1ull << 32))) {
@@ -544,7 +533,7 @@ int stage_cape(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td
             void *d;
             if (n == 0) break;
             if ((rc = st.alloc(rows_bytes(p, p->nlev), &d))) return rc;
-            by_dtype(p->dtype, [&](auto z) { using T = decltype(z); launch(xp::k_densify<T>, n, st, *v, p->nlev, p->ncol, (T *)d); });
+            with_type(p->dtype == XP_F64, [&](auto z) { using T = decltype(z); launch_columns(xp::k_densify<T>, n, st.s, *v, p->nlev, p->ncol, (T *)d); });
             *v = {d, p->ncol, 1};
         }
     }
@@ -611,7 +600,7 @@ int family_flags(Stager &st, const xp_opts &o, int64_t ncol, int32_t **flags) {
 void cape_pass(const Stager &st, xp::CapeArgs a, int dtype, int mode, bool profile, int32_t *flags) {
     a.flags = flags;
     a.persist = flags && persist(mode, a.ncol);
-    by_dtype(dtype, [&](auto z) { launch_cape_pm<decltype(z)>(a, mode, profile, st.s); });
+    with_type(dtype == XP_F64, [&](auto z) { launch_cape<decltype(z)>(a, mode, profile, st.s); });
 }
 
 // XP_PARCEL_MAX_CAPE (csrc/xp_max_cape.hpp), the selection on a call's staged views: k* per column into scratch of the call
@@ -672,22 +661,6 @@ void cape_pass32(const Stager &st, xp::CapeArgs a, int32_t *flags) {
     xp::launch_cape_mode<float, 0>(a, xp::PM_SURFACE, false, st.s);
 }
 
-template <typename T, int NV> void launch_interp_levels(int nt, const Stager &st, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg) {
-    switch (nt) {
-        case 1: launch(xp::k_interp_levels<T, NV, 1>, ncol, st, cv, m, nlev, ncol, lg); break;
-        case 2: launch(xp::k_interp_levels<T, NV, 2>, ncol, st, cv, m, nlev, ncol, lg); break;
-        case 3: launch(xp::k_interp_levels<T, NV, 3>, ncol, st, cv, m, nlev, ncol, lg); break;
-        default: launch(xp::k_interp_levels<T, NV, 4>, ncol, st, cv, m, nlev, ncol, lg); break;
-    }
-}
-template <typename T> void launch_interp_levels_v(int nv, int nt, const Stager &st, const xp::View &cv, const xp::InterpMany &m, int64_t nlev, int64_t ncol, int lg) {
-    switch (nv) {
-        case 1: launch_interp_levels<T, 1>(nt, st, cv, m, nlev, ncol, lg); break;
-        case 2: launch_interp_levels<T, 2>(nt, st, cv, m, nlev, ncol, lg); break;
-        case 3: launch_interp_levels<T, 3>(nt, st, cv, m, nlev, ncol, lg); break;
-        default: launch_interp_levels<T, 4>(nt, st, cv, m, nlev, ncol, lg); break;
-    }
-}
 // xp_interp_levels on checked views (xp_conv_properties calls it on its staged winds)
 int interp_levels(Stager &st, const xp_view *coords, int32_t nvar, const xp_view *const *variables, int32_t ntarget,
                   const double *at, int32_t log_coords, void *const *out) {
@@ -702,9 +675,9 @@ int interp_levels(Stager &st, const xp_view *coords, int32_t nvar, const xp_view
             if ((rc = st.out(out[v * ntarget + j], rows_bytes(coords, 1), coords->mem, &m.out[v * ntarget + j]))) return rc;
     }
     for (int j = 0; j < ntarget; ++j) m.at[j] = at[j];
-    by_dtype(coords->dtype, [&](auto z) {
-        launch_interp_levels_v<decltype(z)>(nvar, ntarget, st, cv, m, coords->nlev, coords->ncol, (int)log_coords);
-    });
+    with_type(coords->dtype == XP_F64, [&](auto z) { with_int<1, 4>(nvar, [&](auto NV) { with_int<1, 4>(ntarget, [&](auto NT) {
+        launch_columns(xp::k_interp_levels<decltype(z), NV(), NT()>, coords->ncol, st.s, cv, m, coords->nlev, coords->ncol, (int)log_coords);
+    }); }); });
     return 0;
 }
 
@@ -736,9 +709,9 @@ int helicity(const char *entry, const xp_view *z, const xp_view *u, const xp_vie
     }
     if ((rc = st.out(out->status, (size_t)z->ncol * 4, out->mem, &a.status))) return rc;
     a.nlev = z->nlev; a.ncol = z->ncol; a.n = n;
-    by_dtype(z->dtype, [&](auto t) {
-        if constexpr (LAYERS) launch(xp::k_helicity_layers<decltype(t)>, z->ncol, st, a);
-        else launch(xp::k_storm_relative_helicity<decltype(t)>, z->ncol, st, a);
+    with_type(z->dtype == XP_F64, [&](auto t) {
+        if constexpr (LAYERS) launch_columns(xp::k_helicity_layers<decltype(t)>, z->ncol, st.s, a);
+        else launch_columns(xp::k_storm_relative_helicity<decltype(t)>, z->ncol, st.s, a);
     });
     return st.finish();
 }
@@ -907,7 +880,7 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     if ((rc = st.alloc(sizeof(int32_t) * (size_t)ncol * (size_t)np, &flags))) return rc;
     for (int i = 0; i < np; ++i) m.flags[i] = flags + (size_t)i * (size_t)ncol;
     m.base.persist = persist(-1, ncol);
-    by_dtype(p->dtype, [&](auto z) {
+    with_type(p->dtype == XP_F64, [&](auto z) {
         using T = decltype(z);
         xp::launch_cape_multi<T, 2>(m, st.s);
         // columns a chain's family table could not serve: the single-parcel RK4 kernel redoes them, chain by chain
@@ -982,7 +955,7 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
     ca.nlev = nlev; ca.ncol = ncol; ca.td = td;
     ca.t850 = tp(T850); ca.t700 = tp(T700); ca.t500 = tp(T500); ca.td850 = tp(TD850); ca.z700 = tp(Z700); ca.z500 = tp(Z500);
     ca.freezing = o_[O_FRZ]; ca.melting = o_[O_MLT]; ca.valid = valid;
-    by_dtype(p->dtype, [&](auto z_) { launch(xp::k_conv_columns<decltype(z_)>, ncol, st, ca); });
+    with_type(p->dtype == XP_F64, [&](auto z_) { launch_columns(xp::k_conv_columns<decltype(z_)>, ncol, st.s, ca); });
     // 2. the three parcels (pf.py:1984-2006), lifted index out of the same passes
     xp_view tdv = dv[0];
     tdv.data = td; tdv.lev_stride = ncol; tdv.col_stride = 1;
@@ -1028,7 +1001,7 @@ int xp_conv_properties(const xp_conv_in *in, const xp_opts *o, int32_t ignore_na
     fa.mu_mixing_ratio = o_[O_MU_W]; fa.dci[0] = o_[O_MU_DCI]; fa.dci[1] = o_[O_M1_DCI]; fa.dci[2] = o_[O_M5_DCI];
     fa.lapse = o_[O_LAPSE]; fa.temp_500 = o_[O_T500]; fa.shear_u = o_[O_SHU]; fa.shear_v = o_[O_SHV]; fa.shear_mag = o_[O_SHM];
     fa.positive_shear = (int32_t *)o_[O_POS];
-    by_dtype(p->dtype, [&](auto z_) { launch(xp::k_conv_finish<decltype(z_)>, ncol, st, fa); });
+    with_type(p->dtype == XP_F64, [&](auto z_) { launch_columns(xp::k_conv_finish<decltype(z_)>, ncol, st.s, fa); });
     return st.finish();
 }
 
@@ -1046,11 +1019,9 @@ int xp_select_parcel(const xp_view *p, const xp_view *t, const xp_view *td, cons
     if (parcel_mode(*parcel) != XP_PARCEL_MOST_UNSTABLE && parcel_mode(*parcel) != XP_PARCEL_MIXED_LAYER)
         return fail(XP_E_ARG, "xp_select_parcel: mode must be most-unstable or mixed-layer");
     if ((rc = stage_scalars(st, out, a.ncol, &a.s))) return rc;
-    by_dtype(p->dtype, [&](auto z) {
-        using T = decltype(z);
-        if (parcel_mode(*parcel) == XP_PARCEL_MOST_UNSTABLE) launch(xp::k_select_parcel<T, xp::PM_MU>, a.ncol, st, a);
-        else launch(xp::k_select_parcel<T, xp::PM_ML>, a.ncol, st, a);
-    });
+    with_type(p->dtype == XP_F64, [&](auto z) { with_one_of<xp::PM_MU, xp::PM_ML>(parcel_mode(*parcel), [&](auto PM) {
+        launch_columns(xp::k_select_parcel<decltype(z), PM()>, a.ncol, st.s, a);
+    }); });
     return st.finish();
 }
 
@@ -1063,7 +1034,7 @@ int xp_mixed_layer(const xp_view *p, const xp_view *v, double depth, void *out, 
     xp::View pv, vv;
     void *od;
     if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, v, &vv)) || (rc = st.out(out, rows_bytes(p, 1), p->mem, &od))) return rc;
-    by_dtype(p->dtype, [&](auto z) { launch(xp::k_mixed_layer<decltype(z)>, p->ncol, st, pv, vv, p->nlev, p->ncol, depth, od, (int)(p->dtype == XP_F64)); });
+    with_type(p->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_mixed_layer<decltype(z)>, p->ncol, st.s, pv, vv, p->nlev, p->ncol, depth, od, (int)(p->dtype == XP_F64)); });
     return st.finish();
 }
 
@@ -1081,7 +1052,7 @@ int xp_lcl(int64_t n, int32_t dtype, int32_t mem, const void *pp, const void *pt
     if ((rc = st.in(pp, b, mem, &dp)) || (rc = st.in(pt, b, mem, &dt)) || (rc = st.in(ptd, b, mem, &dtd)) ||
         (rc = st.out(lp, b, mem, &op)) || (rc = st.out(lt, b, mem, &ot)) || (rc = st.out(ltv, b, mem, &otv)) ||
         (rc = st.out(status, (size_t)n * 4, mem, &os))) return rc;
-    by_dtype(dtype, [&](auto z) { launch(xp::k_lcl<decltype(z)>, n, st, n, dp, dt, dtd, op, ot, otv, os); });
+    with_type(dtype == XP_F64, [&](auto z) { launch_columns(xp::k_lcl<decltype(z)>, n, st.s, n, dp, dt, dtd, op, ot, otv, os); });
     return st.finish();
 }
 
@@ -1096,7 +1067,7 @@ int xp_dry_lapse(const xp_view *p, const void *pt, const void *pp, void *out, vo
     void *od;
     if ((rc = stage_view(st, p, &pv)) || (rc = st.in(pt, rows_bytes(p, 1), p->mem, &dt)) || (rc = st.in(pp, rows_bytes(p, 1), p->mem, &dp)) ||
         (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
-    by_dtype(p->dtype, [&](auto z) { launch(xp::k_dry_lapse<decltype(z)>, p->ncol, st, pv, p->nlev, p->ncol, dt, dp, out_like(od, p)); });
+    with_type(p->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_dry_lapse<decltype(z)>, p->ncol, st.s, pv, p->nlev, p->ncol, dt, dp, out_like(od, p)); });
     return st.finish();
 }
 
@@ -1114,8 +1085,8 @@ int xp_moist_lapse(const xp_view *p, const void *pt, const void *pp, int32_t moi
     void *od;
     if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &pv)) || (rc = st.in(pt, rows_bytes(p, 1), p->mem, &dt)) ||
         (rc = st.in(pp, rows_bytes(p, 1), p->mem, &dp)) || (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
-    by_dtype(p->dtype, [&](auto z) {
-        launch(xp::k_moist_lapse<decltype(z)>, p->ncol, st, pv, p->nlev, p->ncol, dt, dp, tm, ts.tb, ts.es, out_like(od, p));
+    with_type(p->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_moist_lapse<decltype(z)>, p->ncol, st.s, pv, p->nlev, p->ncol, dt, dp, tm, ts.tb, ts.es, out_like(od, p));
     });
     return st.finish();
 }
@@ -1137,8 +1108,8 @@ int xp_parcel_profile(const xp_view *p, const void *pp, const void *pt, const vo
         (rc = st.in(pt, cb, p->mem, &dpt)) || (rc = st.in(ptd, cb, p->mem, &dptd)) || (rc = st.out(t_out, fb, p->mem, &d1)) ||
         (rc = st.out(tv_out, fb, p->mem, &d2)) || (rc = st.out(lp, cb, p->mem, &d3)) || (rc = st.out(lt, cb, p->mem, &d4)) ||
         (rc = st.out(ltv, cb, p->mem, &d5))) return rc;
-    by_dtype(p->dtype, [&](auto z) {
-        launch(xp::k_parcel_profile<decltype(z)>, p->ncol, st, pv, p->nlev, p->ncol, dpp, dpt, dptd, tm, ts.tb, ts.es,
+    with_type(p->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_parcel_profile<decltype(z)>, p->ncol, st.s, pv, p->nlev, p->ncol, dpp, dpt, dptd, tm, ts.tb, ts.es,
                out_like(d1, p), out_like(d2, p), d3, d4, d5);
     });
     return st.finish();
@@ -1157,7 +1128,7 @@ int xp_lfc_el(const xp_view *p, const xp_view *par, const xp_view *env, const vo
     if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, par, &pav)) || (rc = stage_view(st, env, &ev)) ||
         (rc = st.in(lcl_p, rows_bytes(p, 1), p->mem, &dlp)) || (rc = st.in(lcl_t, rows_bytes(p, 1), p->mem, &dlt)) ||
         (rc = stage_scalars(st, out, p->ncol, &so))) return rc;
-    by_dtype(p->dtype, [&](auto z) { launch(xp::k_lfc_el<decltype(z)>, p->ncol, st, pv, pav, ev, p->nlev, p->ncol, dlp, dlt, so); });
+    with_type(p->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_lfc_el<decltype(z)>, p->ncol, st.s, pv, pav, ev, p->nlev, p->ncol, dlp, dlt, so); });
     return st.finish();
 }
 
@@ -1176,8 +1147,8 @@ int xp_cape_cin_base(const xp_view *p, const xp_view *env, const xp_view *par, c
         (rc = st.in(lfc_p, cb, p->mem, &dl)) || (rc = st.in(el_p, cb, p->mem, &de)) || (rc = st.out(cape, cb, p->mem, &dc)) ||
         (rc = st.out(cin, cb, p->mem, &dn))) return rc;
     const xp_opts oo = o ? *o : default_opts();
-    by_dtype(p->dtype, [&](auto z) {
-        launch(xp::k_cape_cin_base<decltype(z)>, p->ncol, st, pv, ev, pav, p->nlev, p->ncol, dl, de, oo.pos_cape_neg_cin, oo.post_zero_cin, dc, dn);
+    with_type(p->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_cape_cin_base<decltype(z)>, p->ncol, st.s, pv, ev, pav, p->nlev, p->ncol, dl, de, oo.pos_cape_neg_cin, oo.post_zero_cin, dc, dn);
     });
     return st.finish();
 }
@@ -1195,8 +1166,8 @@ int xp_wet_bulb_temperature(const xp_view *p, const xp_view *t, const xp_view *t
     void *od;
     if ((rc = snapshot_tables(tm, &ts)) || (rc = stage_view(st, p, &pv)) || (rc = stage_view(st, t, &tv)) ||
         (rc = stage_view(st, td, &tdv)) || (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
-    by_dtype(p->dtype, [&](auto z) {
-        launch(xp::k_wet_bulb<decltype(z)>, p->nlev * p->ncol, st, pv, tv, tdv, p->nlev, p->ncol, tm, ts.tb, ts.es, out_like(od, p));
+    with_type(p->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_wet_bulb<decltype(z)>, p->nlev * p->ncol, st.s, pv, tv, tdv, p->nlev, p->ncol, tm, ts.tb, ts.es, out_like(od, p));
     });
     return st.finish();
 }
@@ -1227,7 +1198,7 @@ int xp_downdraft_cape(const xp_view *p, const xp_view *t, const xp_view *td, dou
     a.nlev = p->nlev; a.ncol = p->ncol;
     a.bottom = layer_bottom; a.top = layer_bottom - layer_depth;
     a.table_mode = tm; a.tb = ts.tb; a.es_tab = ts.es;
-    by_dtype(p->dtype, [&](auto z) { launch(xp::k_downdraft_cape<decltype(z)>, p->ncol, st, a); });
+    with_type(p->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_downdraft_cape<decltype(z)>, p->ncol, st.s, a); });
     return st.finish();
 }
 
@@ -1314,7 +1285,7 @@ int xp_bunkers_storm_motion(const xp_view *p, const xp_view *u, const xp_view *v
         (rc = st.out(out->mean_v, cb, out->mem, &a.mean_v)) ||
         (rc = st.out(out->status, (size_t)p->ncol * 4, out->mem, &a.status))) return rc;
     a.nlev = p->nlev; a.ncol = p->ncol;
-    by_dtype(p->dtype, [&](auto t) { launch(xp::k_bunkers_storm_motion<decltype(t)>, p->ncol, st, a); });
+    with_type(p->dtype == XP_F64, [&](auto t) { launch_columns(xp::k_bunkers_storm_motion<decltype(t)>, p->ncol, st.s, a); });
     return st.finish();
 }
 
@@ -1680,8 +1651,8 @@ int xp_interp_level(const xp_view *coords, const xp_view *x, const void *at, int
     if ((rc = stage_view(st, coords, &cv)) || (rc = stage_view(st, x, &xv)) ||
         (rc = st.in(at, at_is_scalar ? esize(coords->dtype) : rows_bytes(coords, 1), coords->mem, &da)) ||
         (rc = st.out(out, rows_bytes(coords, 1), coords->mem, &od))) return rc;
-    by_dtype(coords->dtype, [&](auto z) {
-        launch(xp::k_interp_level<decltype(z)>, coords->ncol, st, cv, xv, coords->nlev, coords->ncol, da, (int)at_is_scalar, (int)log_coords, od);
+    with_type(coords->dtype == XP_F64, [&](auto z) {
+        launch_columns(xp::k_interp_level<decltype(z)>, coords->ncol, st.s, cv, xv, coords->nlev, coords->ncol, da, (int)at_is_scalar, (int)log_coords, od);
     });
     return st.finish();
 }
@@ -1709,7 +1680,7 @@ int xp_dewpoint_from_specific_humidity(const xp_view *p, const xp_view *t, const
     void *od;
     if ((rc = stage_view(st, p, &pv)) || (rc = stage_view(st, t, &tv)) || (rc = stage_view(st, q, &qv)) ||
         (rc = st.out(out, rows_bytes(p, p->nlev), p->mem, &od))) return rc;
-    by_dtype(p->dtype, [&](auto z) { launch(xp::k_dewpoint_from_q<decltype(z)>, p->nlev * p->ncol, st, pv, tv, qv, p->nlev, p->ncol, out_like(od, p)); });
+    with_type(p->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_dewpoint_from_q<decltype(z)>, p->nlev * p->ncol, st.s, pv, tv, qv, p->nlev, p->ncol, out_like(od, p)); });
     return st.finish();
 }
 
@@ -1722,7 +1693,7 @@ int xp_crossing_level(const xp_view *x, const xp_view *a, double value, void *ou
     xp::View xv, av;
     void *od;
     if ((rc = stage_view(st, x, &xv)) || (rc = stage_view(st, a, &av)) || (rc = st.out(out, rows_bytes(x, 1), x->mem, &od))) return rc;
-    by_dtype(x->dtype, [&](auto z) { launch(xp::k_crossing_level<decltype(z)>, x->ncol, st, xv, av, x->nlev, x->ncol, value, od); });
+    with_type(x->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_crossing_level<decltype(z)>, x->ncol, st.s, xv, av, x->nlev, x->ncol, value, od); });
     return st.finish();
 }
 
@@ -1736,7 +1707,7 @@ int xp_mixing_ratio(const xp_view *t, const xp_view *td, const xp_view *p, void 
     void *od;
     if ((rc = stage_view(st, t, &tv)) || (rc = stage_view(st, td, &tdv)) || (rc = stage_view(st, p, &pv)) ||
         (rc = st.out(out, rows_bytes(t, t->nlev), t->mem, &od))) return rc;
-    by_dtype(t->dtype, [&](auto z) { launch(xp::k_mixing_ratio<decltype(z)>, t->nlev * t->ncol, st, tv, tdv, pv, t->nlev, t->ncol, out_like(od, t)); });
+    with_type(t->dtype == XP_F64, [&](auto z) { launch_columns(xp::k_mixing_ratio<decltype(z)>, t->nlev * t->ncol, st.s, tv, tdv, pv, t->nlev, t->ncol, out_like(od, t)); });
     return st.finish();
 }
 
