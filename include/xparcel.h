@@ -144,6 +144,55 @@ enum { XP_LCL_INTERP_LINEAR = 0, XP_LCL_INTERP_LOG = 1 };
 /* xp_opts.flags.  XP_OPT_FUSE_PARCELS: xp_cape_cin_multi lifts its parcels in ONE pass over the grid where it can (see
    there); same results bit for bit, measured SLOWER than one pass per parcel on MI355X, so off by default. */
 enum { XP_OPT_FUSE_PARCELS = 1 };
+/* xp_opts.flags, bits 4-6: WHICH POSITIVE LAYER the CAPE / CIN and the LFC / EL of a call describe.  The reference's rule
+   (lfc_el, pf.py:1124-1138) takes the bottom LFC and the top EL: on a sounding with several separate positive areas --
+   capping inversions, elevated convection, dry intrusions -- it adds them all up.  MetPy lets the caller say which one is
+   meant (which_lfc / which_el = 'bottom' | 'top' | 'wide' | 'most_cape'); this field does the same for a whole LFC / EL pair.
+   The rule is defined on exactly the nodes xp_cape_cin scans for the chosen parcel (the LCL-augmented profile from the parcel
+   on), with F+ and F- the running sums of the positive and the negative area of parcel minus environment over ln p
+   (xp_cape_cin_layers' formalism, below).
+   EVENTS, in the order of the ascent: an UP is an increasing crossing that qualifies as an LFC candidate of lfc_el (above
+     the LCL, in the selected set of pf.py:1117-1120), a DOWN a decreasing crossing that qualifies as an EL candidate (above
+     the LCL, not in the first interval) -- every one of them, not only the bottom UP and the top DOWN.  A crossing lies at
+     the ln p, with the parcel temperature and the interval index, that xp_cape_cin computes for it; F+ and F- "at" a
+     crossing are the sums up to it (the interval's triangle below the crossing included).
+   POSITIVE LAYERS, numbered 1 ... K upward: an UP while no layer is open opens one: its bottom is this crossing, with
+     cL = F+ and nL = F- there; an UP while one is open is ignored.  A DOWN while a layer is open closes it: its top is this
+     crossing, with cE = F+ there.  A DOWN while none is open and none has been opened before closes a layer whose bottom is
+     the LCL: L = the LCL pressure, lfc_temperature = the LCL's (virtual) temperature, lfc_index = -2, cL and nL the sums at
+     the LCL node -- the existing replacement of pf.py:1161-1180 -- unless the crossing lies ON the LCL, within 2e-9 in ln p
+     (the window in which xp_cape_cin itself decides "above the LCL" on the last bit of exp / log: a saturated parcel that
+     turns negative right above its own level): that layer would have no depth, and the DOWN is ignored.  Any other DOWN is
+     ignored.  A layer still open after the
+     last node closes at the lowest valid pressure: cE = the final F+, el_pressure / el_temperature NaN, el_index = -1, as
+     the existing rule has it when there is no EL.
+   SELECTION (K >= 2): XP_OPT_LAYER_LOWEST layer 1, XP_OPT_LAYER_HIGHEST layer K, XP_OPT_LAYER_DEEPEST the largest
+     ln L - ln E -- depth in ln p, roughly geometric depth, NOT MetPy's difference in hPa, which favours low layers --
+     XP_OPT_LAYER_MOST_CAPE the largest cE - cL.  Walking upward the first layer is taken and then replaced only on a strictly
+     greater metric: the lower of equals wins, a NaN metric never wins.
+   RESULT (K >= 2): cape = (E < L) ? Rd (cE - cL) : 0, cin = Rd nL (post_zero_cin as ever), lfc_* / el_* the chosen
+     layer's, the pressures through the routine that forms xp_cape_cin's; every other scalar -- lcl_*, parcel_*,
+     parcel_index, status -- what the default call writes.  Equivalently: cape and cin are xp_cape_cin_base's for the chosen
+     lfc_pressure / el_pressure (the lowest valid pressure for an open layer).
+   K <= 1: there is nothing to choose, and every choice stores exactly what the default call stores, fallbacks of
+     pf.py:1161-1180 included -- bit for bit in XP_MOIST_EXACT and XP_MOIST_TABLE.  (One class apart: a saturated parcel's
+     crossing ON its LCL, where xp_cape_cin's own answer hangs on the last bit of exp / log and on the other columns of
+     the wavefront; this call always breaks that tie as the reference's expressions do.)
+   Honoured by xp_cape_cin and xp_cape_cin_multi (one choice per call; every parcel takes the per-parcel path,
+   XP_OPT_FUSE_PARCELS is ignored as for explicit parcels), with all five parcel kinds, XP_PARCEL_OVER_GROUND, and every
+   XP_HUM_* (XP_HUM_RELATIVE, XP_HUM_MIXING_RATIO and the ground cut are passes in front: the call IS the call on what they
+   produce, bit for bit; XP_HUM_SPECIFIC is converted on load by xp_dewpoint_from_specific_humidity's chain).
+   XP_MOIST_EXACT and XP_MOIST_TABLE; XP_MOIST_FAMILY is treated as exact, as in xp_cape_cin_layers.  f32 views are
+   converted exactly, all arithmetic is fp64.  pos_cape_neg_cin must be set (F+ and F- are the sign-filtered sums).
+   XP_E_ARG, nothing written, for a non-zero field with: a value 5 ... 7; pos_cape_neg_cin == 0; a non-NULL profile (the
+   profile does not depend on the choice: the default call provides it); compute = XP_F32; or any other entry point that
+   takes an xp_opts (xp_cape_cin_layers, xp_effective_inflow_layer, xp_conv_properties, xp_cape_cin_base).
+   With the field 0 nothing changes by a bit and the same kernels run.
+   COST (csrc/xp_cape_pick.hpp): one ascent in xp_cape_cin_layers' kernel form, at half the exact-mode kernels' occupancy.
+   Measured on 64 x 1 Mi fp64 columns, surface parcel: 1.7 x the XP_MOIST_EXACT default call. */
+enum { XP_OPT_LAYER_SHIFT = 4, XP_OPT_LAYER_MASK = 7 << 4,
+       XP_OPT_LAYER_ENVELOPE = 0 << 4,   /* bottom LFC, top EL: the reference's rule, the default */
+       XP_OPT_LAYER_LOWEST = 1 << 4, XP_OPT_LAYER_HIGHEST = 2 << 4, XP_OPT_LAYER_DEEPEST = 3 << 4, XP_OPT_LAYER_MOST_CAPE = 4 << 4 };
 
 /* error codes */
 enum {

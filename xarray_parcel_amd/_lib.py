@@ -19,6 +19,12 @@ LCL_INTERP = {'linear': 0, 'log': 1}
 HUMIDITY = {'dewpoint': 0, 'specific': 1, 'relative': 2, 'mixing_ratio': 3}     # xp_opts.humidity: what the moisture view holds
 COMPUTE = {'float32': XP_F32, 'float64': XP_F64}      # xp_opts.compute: the arithmetic type
 OPT_FUSE_PARCELS = 1
+# xp_opts.flags, bits 4-6 (XP_OPT_LAYER_*): which positive layer a CAPE / CIN call describes; 'envelope' is the reference's rule
+OPT_LAYER_SHIFT, OPT_LAYER_MASK = 4, 7 << 4
+POSITIVE_LAYER = {'envelope': 0 << 4, 'lowest': 1 << 4, 'highest': 2 << 4, 'deepest': 3 << 4, 'most_cape': 4 << 4}
+# ... and MetPy's (which_lfc, which_el) pairs that name one
+WHICH_LFC_EL = {('bottom', 'top'): 'envelope', ('bottom', 'bottom'): 'lowest', ('top', 'top'): 'highest', ('wide', 'wide'): 'deepest',
+                ('most_cape', 'most_cape'): 'most_cape'}
 ST_TOP_NAN, ST_LCL_NOT_CONVERGED, ST_NAN_PRESSURE, ST_BAD_PRESSURE = 1, 2, 4, 8
 
 # every symbol include/xparcel.h declares
@@ -371,6 +377,8 @@ THERMO_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
 # The layer CAPE / CIN kernel (csrc/xp_cape_layers.hpp): the ascent of the effective-inflow kernel, and its flag for its reason
 # (104-111 VGPRs without a spill).
 CAPE_LAYERS_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The positive-layer kernel (csrc/xp_cape_pick.hpp): the same ascent with two more records per column, the same flag.
+CAPE_PICK_FLAGS = ['-mllvm', '-disable-machine-licm']
 # The sounding-indices kernel (csrc/xp_sounding.hpp) takes no flag: 59-84 VGPRs without winds, 81-105 with them, no scratch.
 # The isentropic-interpolation kernel (csrc/xp_isentropic.hpp) takes none either: 50-52 VGPRs without extras, 86-87 with them, no scratch.
 # The hydrostatic kernel (csrc/xp_hydrostatic.hpp), instantiated on dtype x {dry, dewpoint, specific humidity} x the number of
@@ -396,7 +404,7 @@ UNITS = [('xparcel', 'xparcel.hip', []), ('cape_f32', 'xp_cape_f32_tu.hip', CAPE
          ('effective', 'xp_effective_tu.hip', EFFECTIVE_FLAGS), ('max_cape', 'xp_max_cape_tu.hip', EFFECTIVE_FLAGS),
          ('wind_layers', 'xp_wind_layers_tu.hip', WIND_LAYERS_FLAGS),
          ('thermo_layers', 'xp_thermo_layers_tu.hip', THERMO_LAYERS_FLAGS),
-         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),
+         ('cape_layers', 'xp_cape_layers_tu.hip', CAPE_LAYERS_FLAGS), ('cape_pick', 'xp_cape_pick_tu.hip', CAPE_PICK_FLAGS), ('ecape', 'xp_ecape_tu.hip', []),
          ('sounding', 'xp_sounding_tu.hip', []), ('isentropic', 'xp_isentropic_tu.hip', []),
          ('hydrostatic', 'xp_hydrostatic_tu.hip', HYDROSTATIC_FLAGS), ('humidity', 'xp_humidity_tu.hip', [])] + [
     (f'cape_{t[0]}{m}', 'xp_cape_tu.hip', [f'-DXP_TU_T={t}', f'-DXP_TU_MODE={m}'] + TU_FLAGS[m])

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace xp {
 
 // MetPy 1.4.1 constants (the reference's un-vendored dependency)
@@ -1010,7 +1012,12 @@ struct Scan {
     // first node, or an interval whose end points differ in sign / are NaN (pf.py:1019-1022)
     // ABOVE: the caller guarantees that this node and the one before it lie strictly above the LCL (the kernel's phase B):
     // every crossing then is "above the LCL" and none can tie with it
-    template <bool LEAN, bool ABOVE> XP_DEV void special(double X, double par, double env, double y, double a_reg) {
+    // OBS (the positive-layer kernel, xp_cape_pick.hpp; void: nobody): an observer of EVERY crossing that qualifies as an LFC
+    // or an EL candidate, not only the bottom LFC and the top EL kept here: obs->up / obs->down get the crossing's ln p, the
+    // parcel temperature there, the interval index and the running sums as they stand after the lower triangle.
+    template <bool LEAN, bool ABOVE, typename OBS = void>
+    XP_DEV void special(double X, double par, double env, double y, double a_reg, OBS *obs = nullptr) {
+        static_assert(!ABOVE || std::is_void<OBS>::value, "the observer sits in the general form only");
         if (!ABOVE && j == 0) { use_all = (env != par); return; }
         int i = j - 1;
         // Some lane of a wavefront has a crossing in most iterations when neighbouring columns are unrelated (the
@@ -1075,6 +1082,10 @@ struct Scan {
         double ys = frac * (par - parp) + parp;                             // pf.py:1050
         if (!isnan_(xs)) {
             bool in_sel = ABOVE || use_all || i >= 1;
+            if constexpr (!std::is_void<OBS>::value) {
+                if (y > 0.0 && in_sel && above) obs->up(*this, xs, ys, i);
+                if (y < 0.0 && i >= 1 && above) obs->down(*this, xs, ys, i);
+            }
             if (y > 0.0 && in_sel) {                                        // increasing crossing
                 any_inc = 1;
                 if (above && !(xs <= slot[SL_LFC_X * SLOT_STRIDE])) {        // bottom LFC above the LCL (pf.py:1127-1132)
@@ -1095,7 +1106,8 @@ struct Scan {
     // LEAN: only CAPE / CIN (and the LCL / LFC / EL pressures) are wanted -- no LFC / EL temperatures, interval indices or status word:
     // they are not
     // recorded, and the lowest valid pressure is left to the caller (three LDS writes less per crossing, one per level)
-    template <bool LEAN = false, bool ABOVE = false> XP_DEV void node(double P, double X, double par, double env, bool is_lcl) {
+    template <bool LEAN = false, bool ABOVE = false, typename OBS = void>
+    XP_DEV void node(double P, double X, double par, double env, bool is_lcl, OBS *obs = nullptr) {
         if (is_lcl) {                                                       // the bracket is spent: SL_A* become the LFC record
             slot[SL_LFC_X * SLOT_STRIDE] = qnan(); slot[SL_LFC_T * SLOT_STRIDE] = qnan();
             slot[SL_CAPE_LFC * SLOT_STRIDE] = 0.0; slot[SL_CIN_LFC * SLOT_STRIDE] = 0.0;
@@ -1113,11 +1125,11 @@ struct Scan {
         double a = fabs(X - Xp) * ((yp + y) * 0.5);                         // pf.py:186-198
         add(same ? a : 0.0);
 #ifdef XP_NODE_BALLOT
-        if (__builtin_amdgcn_ballot_w64(!same) != 0ull && !same) special<LEAN, ABOVE>(X, par, env, y, a);
+        if (__builtin_amdgcn_ballot_w64(!same) != 0ull && !same) special<LEAN, ABOVE, OBS>(X, par, env, y, a, obs);
 #else
         // (a plain divergent branch: s_and_saveexec + s_cbranch_execz skip it when no lane needs it; the explicit ballot in
         // front of it cost five instructions per node to rebuild a mask the comparison had already produced)
-        if (!same) special<LEAN, ABOVE>(X, par, env, y, a);
+        if (!same) special<LEAN, ABOVE, OBS>(X, par, env, y, a, obs);
 #endif
         pos_parcel = pos_parcel || ((ABOVE || P < p_lcl) && par > env);     // pf.py:1166-1169 (ABOVE: a NaN pressure comes with a NaN parcel)
         if (!LEAN) {                                                        // status bits (LEAN: the caller did not ask for `status`)

@@ -200,8 +200,10 @@ XP_DEV bool start_column(const double *es, const Parcel &pc, bool need_w, bool v
 // the parcel's temperature and virtual temperature at the node; for a node ON the LCL (above = false) tp = the
 // moist-adiabat temperature there, nothing else.
 // status: takes ST_NAN_PRESSURE for a NaN pressure below the LCL (see xparcel.h).
-template <typename A> XP_DEV bool below_lcl_node(const double *es, Scan &sc, const BelowLcl &n, bool vtc, bool log_interp,
-                                                 double P, double T_, double Td_, bool skew, bool last, int &status, A adiabat) {
+// obs: an observer of the scan's crossings (Scan::special), for the positive-layer kernel; nobody by default.
+template <typename A, typename OBS = void>
+XP_DEV bool below_lcl_node(const double *es, Scan &sc, const BelowLcl &n, bool vtc, bool log_interp,
+                           double P, double T_, double Td_, bool skew, bool last, int &status, A adiabat, OBS *obs = nullptr) {
     const bool need_w = vtc;
     double X;
     snap_to_lcl(es, n.lp, n.x_lcl, P, X);
@@ -224,7 +226,7 @@ template <typename A> XP_DEV bool below_lcl_node(const double *es, Scan &sc, con
     }
     double tve = need_w ? virt_env_ranged(es, T_, Td_, P) : T_;
     lcl_ties(need_w, cross, n.sat, P, n.lp, tp, T_, Td_, [&]() __attribute__((always_inline)) { double t, tv; adiabat(false, P, X, t, tv); return t; }, tvp, tve);
-    sc.template node<false, false>(P, X, vtc ? tvp : tp, vtc ? tve : T_, cross);
+    sc.template node<false, false, OBS>(P, X, vtc ? tvp : tp, vtc ? tve : T_, cross, obs);
     if (!isnan_(P) && !skew && !cross) store_bracket(sc.slot, P, X, T_, Td_);
     return skew || cross;
 }

@@ -23,6 +23,7 @@
 #include "xp_effective.hpp"
 #include "xp_max_cape.hpp"
 #include "xp_cape_layers.hpp"
+#include "xp_cape_pick.hpp"
 #include "xp_wind_layers.hpp"
 #include "xp_thermo_layers.hpp"
 #include "xp_sounding.hpp"
@@ -44,6 +45,9 @@ static_assert(xp::HY_MAX_LAYERS == sizeof(xp_hydrostatic_out::thickness) / sizeo
 static_assert(xp::HUM_RELATIVE == XP_HUM_RELATIVE && xp::HUM_MIXING_RATIO == XP_HUM_MIXING_RATIO, "the conversion kernel's moisture kinds are the ABI's");
 static_assert(xp::PM_SURFACE == XP_PARCEL_SURFACE && xp::PM_MU == XP_PARCEL_MOST_UNSTABLE && xp::PM_ML == XP_PARCEL_MIXED_LAYER &&
               xp::PM_EXPLICIT == XP_PARCEL_EXPLICIT, "the kernels' parcel kinds are the ABI's");
+static_assert(xp::PICK_LOWEST == XP_OPT_LAYER_LOWEST >> XP_OPT_LAYER_SHIFT && xp::PICK_HIGHEST == XP_OPT_LAYER_HIGHEST >> XP_OPT_LAYER_SHIFT &&
+              xp::PICK_DEEPEST == XP_OPT_LAYER_DEEPEST >> XP_OPT_LAYER_SHIFT && xp::PICK_MOST_CAPE == XP_OPT_LAYER_MOST_CAPE >> XP_OPT_LAYER_SHIFT,
+              "the positive-layer kernel's choices are the ABI's");
 static_assert(xp::CCL_TOP == XP_CCL_TOP && xp::CCL_BOTTOM == XP_CCL_BOTTOM, "the kernel's CCL choices are the ABI's");
 static_assert(xp::WL_PRESSURE == XP_LAYER_PRESSURE && xp::WL_PRESSURE_DEPTH == XP_LAYER_PRESSURE_DEPTH &&
               xp::WL_HEIGHT == XP_LAYER_HEIGHT, "the kernel's layer kinds are the ABI's");
@@ -429,8 +433,17 @@ xp_opts default_opts() {
     o.virtual_temperature_correction = 1; o.lcl_interp = XP_LCL_INTERP_LOG; o.pos_cape_neg_cin = 1; o.compute = XP_F64;
     return o;
 }
-// f32_ok: the caller implements xp_opts.compute == XP_F32 (xp_cape_cin alone, which then holds the call to check_compute32)
-int check_opts(const xp_opts &o, bool f32_ok = false) {
+// the XP_OPT_LAYER_* field of xp_opts.flags as the kernel's PICK_* (0: the envelope, the default)
+int layer_of(const xp_opts &o) { return (o.flags & XP_OPT_LAYER_MASK) >> XP_OPT_LAYER_SHIFT; }
+// f32_ok: the caller implements xp_opts.compute == XP_F32 (xp_cape_cin alone, which then holds the call to check_compute32);
+// layer_ok: it implements XP_OPT_LAYER_* (xp_cape_cin and xp_cape_cin_multi, without profile output)
+int check_opts(const xp_opts &o, bool f32_ok = false, bool layer_ok = false) {
+    if (layer_of(o)) {
+        if (!layer_ok) return fail(XP_E_ARG, "xp_opts.flags: XP_OPT_LAYER_* is honoured by xp_cape_cin and xp_cape_cin_multi without profile output only");
+        if (layer_of(o) > xp::PICK_MOST_CAPE) return fail(XP_E_ARG, "xp_opts.flags: bad XP_OPT_LAYER_* value %d", layer_of(o));
+        if (!o.pos_cape_neg_cin) return fail(XP_E_ARG, "xp_opts.flags: XP_OPT_LAYER_* is defined for pos_cape_neg_cin only");
+        if (o.compute == XP_F32) return fail(XP_E_ARG, "xp_opts.flags: XP_OPT_LAYER_* does not combine with xp_opts.compute = XP_F32");
+    }
     if (o.lcl_interp != XP_LCL_INTERP_LINEAR && o.lcl_interp != XP_LCL_INTERP_LOG)
         return fail(XP_E_INTERP, "interpolator must be linear or log");
     if (o.moist_mode != XP_MOIST_EXACT && o.moist_mode != XP_MOIST_TABLE && o.moist_mode != XP_MOIST_FAMILY)
@@ -468,7 +481,7 @@ int check_parcel(const xp_parcel *parcel, bool ground_ok = false, bool max_cape_
 }
 // the arguments of the CAPE family: p / T / Td, each of np parcels, the options
 int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, const xp_parcel *parcels, const xp_opts &o, bool f32_ok = false,
-               bool ground_ok = false, bool max_cape_ok = false) {
+               bool ground_ok = false, bool max_cape_ok = false, bool layer_ok = false) {
     if (int rc = check_views({{p, "pressure"}, {t, "temperature"}, {td, "dewpoint"}})) return rc;
     for (int i = 0; i < np; ++i) {
         if (int rc = check_parcel(parcels + i, ground_ok, max_cape_ok)) return rc;
@@ -481,7 +494,7 @@ int check_cape(const xp_view *p, const xp_view *t, const xp_view *td, int np, co
         if (over_ground(a) != over_ground(b) || (over_ground(a) && (a.pressure != b.pressure || a.temperature != b.temperature || a.dewpoint != b.dewpoint)))
             return fail(XP_E_ARG, "parcels: XP_PARCEL_OVER_GROUND must be set on every parcel, with the same surface arrays, or on none");
     }
-    return check_opts(o, f32_ok);
+    return check_opts(o, f32_ok, layer_ok);
 }
 
 // XP_HUM_RELATIVE / XP_HUM_MIXING_RATIO (csrc/xp_humidity.hpp): the staged moisture view *m becomes the dewpoint D of the
@@ -553,9 +566,9 @@ int set_parcel(Stager &st, const xp_parcel &parcel, const xp_view *p, xp::CapeAr
     return 0;
 }
 int fill_common(Stager &st, const xp_view *p, const xp_view *t, const xp_view *td, const xp_parcel *parcel,
-                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false, bool ground_ok = false, bool max_cape_ok = false) {
+                const xp_opts &o, xp::CapeArgs *a, bool f32_ok = false, bool ground_ok = false, bool max_cape_ok = false, bool layer_ok = false) {
     int rc;
-    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok, ground_ok, max_cape_ok)) ||
+    if ((rc = check_cape(p, t, td, 1, parcel, o, f32_ok, ground_ok, max_cape_ok, layer_ok)) ||
         (rc = stage_cape(st, p, t, td, o, a, over_ground(*parcel) ? parcel : nullptr)) || (rc = set_parcel(st, *parcel, p, a)))
         return rc;
     return 0;
@@ -597,7 +610,10 @@ int family_flags(Stager &st, const xp_opts &o, int64_t ncol, int32_t **flags) {
     return st.alloc(sizeof(int32_t) * (size_t)ncol, flags);
 }
 // one parcel's CAPE / CIN on staged arguments; the parcels of one call share the family flags (one stream orders them)
-void cape_pass(const Stager &st, xp::CapeArgs a, int dtype, int mode, bool profile, int32_t *flags) {
+// layer: the call's XP_OPT_LAYER_* choice (layer_of) -- not the envelope: the positive-layer kernel (csrc/xp_cape_pick.hpp)
+// in place of the CAPE kernels, XP_MOIST_FAMILY as exact, no flags and no redo pass
+void cape_pass(const Stager &st, xp::CapeArgs a, int dtype, int mode, bool profile, int32_t *flags, int layer = 0) {
+    if (layer) { xp::launch_cape_pick(a, mode, layer, dtype == XP_F64, a.table_mode != 0, st.s); return; }
     a.flags = flags;
     a.persist = flags && persist(mode, a.ncol);
     with_type(dtype == XP_F64, [&](auto z) { launch_cape<decltype(z)>(a, mode, profile, st.s); });
@@ -823,16 +839,18 @@ int xp_cape_cin(const xp_view *p, const xp_view *t, const xp_view *td, const xp_
     int32_t *flags;
     int rc;
     const bool f32 = oo.compute == XP_F32;                   // (held to its contract before anything is staged or looked up)
-    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true, true, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
-    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true, true, true)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
+    if (f32 && ((rc = check_cape(p, t, td, 1, parcel, oo, true, true, true, true)) || (rc = check_compute32(p, parcel, oo, scalars, profile)))) return rc;
+    const int layer = layer_of(oo);
+    if (layer && profile) return fail(XP_E_ARG, "xp_cape_cin: XP_OPT_LAYER_*: profile must be NULL (the profile does not depend on the choice)");
+    if ((rc = fill_common(st, p, t, td, parcel, oo, &a, true, true, true, profile == nullptr)) || (rc = stage_cape_out(st, p->dtype, scalars, profile, &a)) ||
         (rc = family_flags(st, oo, a.ncol, &flags))) return rc;
     if (f32) cape_pass32(st, a, flags);
     else if (parcel->mode == XP_PARCEL_MAX_CAPE) {           // the surface call on the columns from k* on
         int32_t *kstar;
         if ((rc = max_cape_front(st, *parcel, p, &a, &kstar))) return rc;
-        cape_pass(st, a, p->dtype, XP_PARCEL_SURFACE, profile != nullptr, flags);
+        cape_pass(st, a, p->dtype, XP_PARCEL_SURFACE, profile != nullptr, flags, layer);
         if ((rc = copy_kstar(st, kstar, a))) return rc;
-    } else cape_pass(st, a, p->dtype, parcel_mode(*parcel), profile != nullptr, flags);
+    } else cape_pass(st, a, p->dtype, parcel_mode(*parcel), profile != nullptr, flags, layer);
     return st.finish();
 }
 
@@ -846,7 +864,9 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
     xp::CapeArgs a, pa[xp::MULTI_MAX];
     int rc;
     // every parcel is checked, and its outputs staged, before anything runs; p / T / Td are staged once
-    if ((rc = check_cape(p, t, td, np, parcels, oo, false, true, true)) ||
+    const int layer = layer_of(oo);
+    if (layer && profiles) return fail(XP_E_ARG, "xp_cape_cin_multi: XP_OPT_LAYER_*: profiles must be NULL (a profile does not depend on the choice)");
+    if ((rc = check_cape(p, t, td, np, parcels, oo, false, true, true, profiles == nullptr)) ||
         (rc = stage_cape(st, p, t, td, oo, &a, over_ground(parcels[0]) ? parcels : nullptr))) return rc;   // re-based once per call
     for (int i = 0; i < np; ++i) {
         pa[i] = a;
@@ -854,14 +874,14 @@ int xp_cape_cin_multi(const xp_view *p, const xp_view *t, const xp_view *td, int
             (rc = stage_cape_out(st, p->dtype, &scalars[i], profiles ? &profiles[i] : nullptr, &pa[i]))) return rc;
     }
     const int64_t ncol = a.ncol;
-    if (!multi_fused_ok(np, parcels, oo, profiles)) {        // one pass per parcel
+    if (layer || !multi_fused_ok(np, parcels, oo, profiles)) {   // one pass per parcel
         int32_t *flags;
         if ((rc = family_flags(st, oo, ncol, &flags))) return rc;
         for (int i = 0; i < np; ++i) {
             const bool mc = parcels[i].mode == XP_PARCEL_MAX_CAPE;           // its own selection and re-based views of the shared grid
             int32_t *kstar = nullptr;
             if (mc && (rc = max_cape_front(st, parcels[i], p, &pa[i], &kstar))) return rc;
-            cape_pass(st, pa[i], p->dtype, mc ? XP_PARCEL_SURFACE : parcel_mode(parcels[i]), profiles != nullptr, flags);
+            cape_pass(st, pa[i], p->dtype, mc ? XP_PARCEL_SURFACE : parcel_mode(parcels[i]), profiles != nullptr, flags, layer);
             if ((rc = copy_kstar(st, kstar, pa[i]))) return rc;
         }
         return st.finish();
@@ -1139,6 +1159,7 @@ int xp_cape_cin_base(const xp_view *p, const xp_view *env, const xp_view *par, c
     int rc;
     if ((rc = check_views({{p, "pressure"}, {par, "parcel_temperature"}, {env, "temperature"}}))) return rc;
     if (!lfc_p || !el_p) return fail(XP_E_ARG, "xp_cape_cin_base: null argument");
+    if (o && layer_of(*o)) return fail(XP_E_ARG, "xp_cape_cin_base: xp_opts.flags: XP_OPT_LAYER_* is honoured by xp_cape_cin and xp_cape_cin_multi only");
     xp::View pv, pav, ev;
     const size_t cb = rows_bytes(p, 1);
     const void *dl, *de;

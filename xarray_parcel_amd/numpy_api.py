@@ -169,6 +169,24 @@ def _opts(virtual_temperature_correction=True, lcl_interp='log', pos_cape_neg_ci
                   int(bool(post_zero_cin)), L.MOIST[moist], L.COMPUTE[compute], L.HUMIDITY[humidity], 0)
 
 
+def _layer_flags(positive_layer=None, which_lfc=None, which_el=None):
+    """The XP_OPT_LAYER_* bits of xp_opts.flags (include/xparcel.h) for positive_layer= 'envelope' (the default: the
+    reference's bottom LFC and top EL), 'lowest', 'highest', 'deepest' or 'most_cape', or for MetPy's pair which_lfc= /
+    which_el= that names the same layer; any other pair, or both spellings at once, is a ValueError."""
+    if which_lfc is None and which_el is None:
+        name = 'envelope' if positive_layer is None else positive_layer
+        if name not in L.POSITIVE_LAYER:
+            raise ValueError('positive_layer must be one of %s, got %r' % (', '.join(map(repr, L.POSITIVE_LAYER)), positive_layer))
+    else:
+        pairs = ', '.join('(%r, %r) = %r' % (a, b, n) for (a, b), n in L.WHICH_LFC_EL.items())
+        if positive_layer is not None:
+            raise ValueError('give positive_layer= or the pair which_lfc= / which_el=, not both; the pairs are ' + pairs)
+        if (which_lfc, which_el) not in L.WHICH_LFC_EL:
+            raise ValueError('(which_lfc, which_el) = (%r, %r) names no positive layer; the pairs are %s' % (which_lfc, which_el, pairs))
+        name = L.WHICH_LFC_EL[(which_lfc, which_el)]
+    return L.POSITIVE_LAYER[name]
+
+
 _DEFAULT = {'moist': 'exact', 'compute': 'float64'}
 
 # what a compute='float32' call can return (include/xparcel.h at xp_opts.compute): everything but the LFC / EL temperatures,
@@ -273,7 +291,8 @@ def _parcel(c, name, depth=None, parcel_values=None, surface=None):
 
 
 def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=None, parcel_values=None,
-                     want_profile=False, want=None, moist=None, lifted_index_at=None, compute=None, ground=None, **kwargs):
+                     want_profile=False, want=None, moist=None, lifted_index_at=None, compute=None, ground=None,
+                     positive_layer=None, which_lfc=None, which_el=None, **kwargs):
     """pf.py:1394-1475 with the three drivers.  Returns a dict of per-column arrays (and 'profile').
     want_profile: True for the six profile arrays of pf.py:806-931, or an iterable of their names for a subset (the ones
     not named are neither allocated nor written: lifted_index needs three of the six).
@@ -297,17 +316,26 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
     parcel='max_cape' (XP_PARCEL_MAX_CAPE, include/xparcel.h): the departure level of the lowest `depth` hPa (default 300)
     whose parcel has the largest CAPE -- every level of the window is lifted.  The results are those of the surface call on
     the column from that level on, 'parcel_index' the level.  Not with ground=, humidity='specific' or compute='float32'
-    (humidity='relative' and 'mixing_ratio' are fine)."""
+    (humidity='relative' and 'mixing_ratio' are fine).
+    positive_layer='envelope' | 'lowest' | 'highest' | 'deepest' | 'most_cape' (XP_OPT_LAYER_*, include/xparcel.h): which
+    positive layer of a sounding with several of them CAPE, CIN, the LFC and the EL describe.  'envelope', the default, is
+    the reference's rule -- the bottom LFC and the top EL, every positive area between them added up; the others pick one
+    LFC / EL pair: the lowest layer, the highest, the deepest in ln p, or the one with the most CAPE.  A column with at most
+    one positive layer returns the default's numbers whatever the choice.  which_lfc= / which_el= take MetPy's spelling of
+    the same five: ('bottom', 'top'), ('bottom', 'bottom'), ('top', 'top'), ('wide', 'wide'), ('most_cape', 'most_cape').
+    Not with want_profile, lifted_index_at or compute='float32'; moist='family' runs as 'exact'."""
+    layer = _layer_flags(positive_layer, which_lfc, which_el)
     c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     moist = moist or _DEFAULT['moist']
     if compute is None:
         compute = _DEFAULT['compute']
-        if compute == 'float32' and not (ground is None and
+        if compute == 'float32' and not (ground is None and layer == 0 and
                                          _compute32_applies(c, parcel, moist, want, want_profile, lifted_index_at, kwargs)):
             compute = 'float64'
     if compute == 'float32' and want is None:
         want = COMPUTE32_WANT
     o = _opts(moist=moist, compute=compute, **kwargs)
+    o.flags |= layer
     pc = _parcel(c, parcel, depth, parcel_values, surface)
     so, res = c.scalars(L.SCALAR_F + L.SCALAR_I + L.SCALAR_P if want is None else tuple(want), c.hshape)
     po = None
@@ -324,7 +352,7 @@ def cape_cin_columns(pressure, temperature, dewpoint, parcel='surface', depth=No
 
 
 def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=None, lifted_index_at=None, fused=False,
-                   ground=None, **kwargs):
+                   ground=None, positive_layer=None, which_lfc=None, which_el=None, **kwargs):
     """Several parcels of one grid in ONE call (xp_cape_cin_multi): `parcels` is a sequence of names or (name, depth)
     pairs out of 'surface', 'most_unstable', 'mixed_layer', 'max_cape' -- e.g. [('most_unstable', 300), ('mixed_layer', 100)] for
     BASELINE config 5, [('most_unstable', 250), ('mixed_layer', 100), ('mixed_layer', 50)] for conv_properties
@@ -332,10 +360,13 @@ def cape_cin_multi(pressure, temperature, dewpoint, parcels, want=None, moist=No
     fused=True (XP_OPT_FUSE_PARCELS; moist='family', two parcels): one pass over the grid for both -- same numbers,
     measured slower than a pass per parcel on MI355X, hence opt-in.
     humidity (keyword): as in cape_cin_columns; 'relative' and 'mixing_ratio' are converted once for all the parcels.
-    ground: as in cape_cin_columns; the grid is cut at the ground once for all the parcels."""
+    ground: as in cape_cin_columns; the grid is cut at the ground once for all the parcels.
+    positive_layer / which_lfc, which_el: as in cape_cin_columns, one choice for all the parcels (then a pass per parcel,
+    whatever `fused` says; not with lifted_index_at)."""
+    layer = _layer_flags(positive_layer, which_lfc, which_el)
     c, views, surface = _sounding(pressure, temperature, dewpoint, ground)
     o = _opts(moist=moist or _DEFAULT['moist'], **kwargs)
-    o.flags = L.OPT_FUSE_PARCELS if fused else 0
+    o.flags = (L.OPT_FUSE_PARCELS if fused else 0) | layer
     pcs = []
     for pc in parcels:
         name, depth = (pc, None) if isinstance(pc, str) else (pc[0], pc[1])
